@@ -44,6 +44,7 @@ sys.path.insert(0, REF)
 
 from oracle import eavsr_oracle as O  # noqa: E402  (only for the mmcv DCNv2 stand-in)
 from eavsr_amd.utils.synthetic import fill_state_dict, shapes_of, keys_digest  # noqa: E402
+from tests import helpers as H  # noqa: E402
 from tests.golden import cases  # noqa: E402
 
 
@@ -145,10 +146,8 @@ def load_filled(module: nn.Module, preset: str, prefix: str = ""):
 
 
 def save(name, **arrays):
-    path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **{k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v))
-                                 for k, v in arrays.items()})
-    print(f"wrote {path}  ({os.path.getsize(path) / 1e3:.0f} kB)")
+    H.save_golden(name, {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()})
+    print(f"wrote {os.path.join(HERE, name)}*.npz")
 
 
 def main():

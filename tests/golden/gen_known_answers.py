@@ -26,6 +26,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import c_ref  # noqa: E402
 from oracle import eavsr_oracle as O  # noqa: E402
+from tests import helpers as H  # noqa: E402
 from tests.golden import cases  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,10 +57,11 @@ def main():
         dx, dflow = torch.autograd.grad((out * G).sum(), leaves)
         g9[f"warp_{name}__dx"] = dx.float().numpy()
         g9[f"warp_{name}__dflow"] = dflow.float().numpy()
-    np.savez_compressed(os.path.join(HERE, "g4_dcnv2.npz"), **g4)
-    np.savez_compressed(os.path.join(HERE, "g9_gradients.npz"), **g9)
-    for f in ("g4_dcnv2.npz", "g9_gradients.npz"):
-        print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")
+    H.save_golden("g4_dcnv2", g4)
+    H.save_golden("g9_gradients", g9)
+    for f in sorted(os.listdir(HERE)):
+        if f.startswith(("g4_dcnv2", "g9_gradients")):
+            print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")
 
 
 if __name__ == "__main__":

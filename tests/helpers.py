@@ -2,6 +2,7 @@
 state dicts keyed exactly as tests/golden/gen_golden.py keyed them."""
 from __future__ import annotations
 
+import glob
 import json
 import os
 from typing import Dict, Tuple
@@ -12,12 +13,35 @@ import torch
 from eavsr_amd.utils.synthetic import fill_state_dict
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+PART_BYTES = 1_000_000      # raw array bytes per fixture file: every committed file stays under 1 MiB
 REGULAR = torch.tensor([[-1, -1, -1, 0, 0, 0, 1, 1, 1], [-1, 0, 1, -1, 0, 1, -1, 0, 1]], dtype=torch.float32)
 
 
 def golden(name: str) -> Dict[str, torch.Tensor]:
+    """GOLDEN/name.npz merged with name.part1.npz, name.part2.npz, ... where save_golden split the fixture"""
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    return {k: torch.from_numpy(z[k]) for k in z.files}
+    out = {k: torch.from_numpy(z[k]) for k in z.files}
+    i = 1
+    while os.path.exists(os.path.join(GOLDEN, f"{name}.part{i}.npz")):
+        z = np.load(os.path.join(GOLDEN, f"{name}.part{i}.npz"))
+        out.update({k: torch.from_numpy(z[k]) for k in z.files})
+        i += 1
+    return out
+
+
+def save_golden(name: str, arrays: Dict[str, np.ndarray]) -> None:
+    """`arrays` as GOLDEN/name.npz; once PART_BYTES of raw data are in a file, the next arrays go to name.part1.npz, ..."""
+    for f in glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")):
+        os.remove(f)
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        if parts[-1] and size + v.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN, name + (f".part{i}" if i else "") + ".npz"), **p)
 
 
 def golden_keys(tag: str = "x4") -> dict:

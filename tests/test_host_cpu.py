@@ -187,6 +187,26 @@ def test_harness_ssim_follows_skimage_and_frames_are_written_as_png(tmp_path):
     assert torch.equal(Hn.read_png(out[1]), b.to(torch.uint8))
 
 
+def test_bench_dump_outputs_writes_small_arrays_whole_and_large_ones_as_a_seeded_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: two dumps of the same outputs are identical file for file, within the 64 MB budget"""
+    import numpy as np
+    import bench
+    big = torch.rand(5, 3, 600, 800, generator=torch.Generator().manual_seed(1))      # 28.8 MB: above the whole-array limit
+    loss = torch.tensor([0.25], dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"sr": big.clone(), "loss": loss, "small": big[0, 0, :8].double()})
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss.npy", "small.npy", "sr_plane_mean.npy", "sr_sample.npy", "sr_sample_index.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)) for n in names)
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+    assert got["loss"].dtype == np.float64 and got["loss"][0] == 0.25 and np.array_equal(got["small"], big[0, 0, :8].double().numpy())
+    idx = got["sr_sample_index"].astype(np.int64)
+    assert got["sr_sample"].dtype == np.float32 and got["sr_sample"].shape == (bench.DUMP_SAMPLE,)
+    assert np.array_equal(got["sr_sample"], big.reshape(-1).numpy()[idx]) and np.all(np.diff(idx) >= 0)
+    assert np.allclose(got["sr_plane_mean"], big.double().mean((-2, -1)).numpy(), rtol=0, atol=1e-12)
+
+
 # ---- the bench contract, checked on the committed line of the last GPU visit -------------------------------------
 def test_committed_bench_line_follows_the_contract():
     import json

@@ -11,7 +11,7 @@ root = sys.argv[1]
 out = {}
 stats = glob.glob(os.path.join(root, "bench", "*", "*kernel_stats.csv"))
 if stats:
-    print("== rocprofv3 --kernel-trace --stats of `bench.py --steps 2 --warmup 1` (top kernels)")
+    print("== rocprofv3 --kernel-trace --stats of `bench.py --full --steps 2 --warmup 1` (top kernels)")
     rows = list(csv.DictReader(open(stats[0])))
     for r in rows[:16]:
         print(f"{float(r['Percentage']):6.2f}%  calls {int(r['Calls']):6d}  avg {float(r['AverageNs'])/1e3:10.1f} us  {r['Name'][:110]}")
