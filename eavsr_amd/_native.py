@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EAVSR_LIB_PATH") or os.path.join(
     _HERE, "lib", "libeavsr_lab.so" if os.environ.get("EAVSR_BUILD_LAB", "0") == "1" else "libeavsr_hip.so")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 p_f32 = C.c_void_p  # device pointers travel as integers
 i32 = C.c_int32
@@ -166,6 +166,13 @@ SIGNATURES = {
     "eavsr_nchw_f32_to_nhwc_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     "eavsr_nhwc_h16_to_nchw_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "eavsr_scale_residual_h16": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    # PWC-Net of the late-training validity mask (ABI 31)
+    "eavsr_pwc_conv3x3_weight_elems": (C.c_int64, [i32, i32]),
+    "eavsr_pwc_pack_conv3x3_f32": (C.c_int, [vp, vp, i32, i32, vp]),
+    "eavsr_pwc_conv3x3_f32": (C.c_int, [vp, i64, vp, vp, vp, i64] + [i32] * 8 + [f32, vp]),
+    "eavsr_pwc_deconv4x4s2_f32": (C.c_int, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "eavsr_pwc_correlation_f32": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
+    "eavsr_pwc_backwarp_f32": (C.c_int, [vp, i64, vp, i64, vp, i64, vp] + [i32] * 6 + [f32, vp]),
 }
 
 # Entry points of the LAB build only (`python -m eavsr_amd.build --lab`; the header's EXPERIMENTAL section): bound when the

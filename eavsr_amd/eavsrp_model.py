@@ -393,7 +393,10 @@ class EAVSRPModel:
     checkpoint format ({'state_dict': ...}, base_model.py:159-217).  One process per GPU; with several
     processes (torch.distributed initialised) the training step averages the loss gradients with one
     bucketed RCCL all-reduce (eavsr_amd.shard.GradientAllReducer) instead of nn.DataParallel.
-    The reference's late-training PWC-Net mask (epoch >= opt.npost, eavsrp_model.py:85-97) is out of scope."""
+    From epoch opt.npost on (eavsrp_model.py:85-97) the training forward multiplies the SR output by the validity mask of the HR
+    frames warped by a frozen PWC-Net's flow (eavsr_amd.pwc), loaded from opt.pwc_path at the first such forward; PWC-Net gets no
+    gradients and is not part of the checkpoint.  The reference also calls netGF there and discards its output (the x4 model
+    even fails inside it, eavsrp_model.py:686): it is not computed here."""
 
     def __init__(self, opt):
         self.opt = opt
@@ -409,6 +412,7 @@ class EAVSRPModel:
         self.netEAVSRP = N.init_net(EAVSRP(opt, getattr(opt, "spynet_pretrained", None)), gpu_ids=gpu_ids)
         self.time, self.isfirst, self.num = 0.0, True, 0
         self.epoch = 0
+        self.netPWCNET = None      # loaded at the first training forward with epoch >= opt.npost (_pwc_net)
         self.start_epoch = 0
         self.metric = 0            # learning-rate policy 'plateau' (base_model.py:34)
         self.optimizers, self.schedulers = [], []
@@ -478,11 +482,11 @@ class EAVSRPModel:
 
     def forward(self):
         if self.isTrain and self.netEAVSRP.training:
-            if self.epoch >= getattr(self.opt, "npost", 350):
-                raise NotImplementedError("the PWC-Net validity mask of epochs >= npost (eavsrp_model.py:85-97) is "
-                                          "outside the hot path")
             self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
             self.data_sr = self.data_sr_seq[:, self.idx]
+            if self.masked_phase():
+                self.data_hr_align, self.mask = self.hr_align_and_mask()
+                self.data_sr_seq = self.data_sr_seq * self.mask
             return
         start = time.time()
         self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
@@ -492,6 +496,45 @@ class EAVSRPModel:
             self.time += end - start
             self.num += 1
         self.isfirst = False
+
+    def masked_phase(self) -> bool:
+        """epoch >= opt.npost: the training forward masks the SR output (eavsrp_model.py:85)"""
+        return self.epoch >= getattr(self.opt, "npost", 350)
+
+    def _pwc_net(self):
+        """The frozen PWC-Net, read from opt.pwc_path (default ./pwc/pwc-default, models/pwc_net.py:246) once.  Several
+        processes: every rank reads its file and the ranks agree (`shard.all_ranks_ok`) before any of them goes on."""
+        if self.netPWCNET is not None:
+            return self.netPWCNET
+        from . import pwc
+        from .shard import all_ranks_ok
+        path = getattr(self.opt, "pwc_path", "./pwc/pwc-default")
+        net, err = None, None
+        try:
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"PWC-Net weights {path!r} not found (opt.pwc_path): training at epoch {self.epoch} >= "
+                                        f"opt.npost = {getattr(self.opt, 'npost', 350)} masks the loss with PWC-Net's flow")
+            net = pwc.load_pwc_weights(pwc.PWCNET(), path).to(self.device).eval()
+            for p in net.parameters():
+                p.requires_grad_(False)
+        except Exception as e:      # noqa: BLE001 -- re-raised below, on every rank
+            err = e
+        if not all_ranks_ok(err is None):
+            if err is not None:
+                raise err
+            raise RuntimeError("another rank failed to load the PWC-Net weights (opt.pwc_path); aborting on every rank")
+        self.netPWCNET = net
+        return net
+
+    def hr_align_and_mask(self):
+        """(hr_align (n,t,3,H,W), mask (n,t,1,H,W)) of every frame: BaseModel.get_backwarp(lr, hr, PWC-Net, scale)
+        (base_model.py:338-354), all n*t frame pairs in one PWC-Net call"""
+        from . import pwc
+        lr, hr = self.data_lr_seq, self.data_hr_seq
+        n, t = lr.shape[:2]
+        hr_align, mask = pwc.get_backwarp(lr.reshape((n * t,) + tuple(lr.shape[2:])), hr.reshape((n * t,) + tuple(hr.shape[2:])),
+                                          self._pwc_net(), self.scale)
+        return hr_align.view((n, t) + tuple(hr_align.shape[1:])), mask.view((n, t) + tuple(mask.shape[1:]))
 
     def test(self):
         with torch.no_grad():

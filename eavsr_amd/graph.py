@@ -144,6 +144,8 @@ class GraphedTrainStep:
     static buffers and replays.  `model.loss_*` are the graph's static loss tensors.
     """
 
+    masked = False       # the captured forward holds the PWC-Net mask of epochs >= opt.npost (set by _capture)
+
     def __init__(self, model, warmup: int = 2):
         import torch.distributed as dist
         self.model = model
@@ -167,11 +169,31 @@ class GraphedTrainStep:
             if "step" in st and not st["step"].is_cuda:
                 st["step"] = st["step"].to(dev, torch.float32)
         model.data_lr_seq, model.data_hr_seq = self.static_lr, self.static_hr
+        self._capture(warmup, optimizer_steps=True)
+
+    def _capture(self, warmup: int, optimizer_steps: bool):
+        """Warm up and capture the step.  optimizer_steps=False (a recapture in the middle of training): the warm-up runs forward
+        and backward only, so that recapturing leaves the parameters and the optimizer state as they are."""
+        model, dev, opt = self.model, self.model.device, self.model.optimizer_EAVSRP
+        # whether the captured forward holds the PWC-Net mask of epochs >= opt.npost: step() recaptures when the phase changes
+        self.masked = model.masked_phase()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(warmup, 1)):          # allocator warm-up, kernel attributes, optimizer state
-                model.optimize_parameters()
+                if optimizer_steps:
+                    model.optimize_parameters()
+                else:                                # no collective either: the ranks exchange nothing for this warm-up
+                    model.grad_sync.paused = True
+                    try:
+                        model.forward()
+                        opt.zero_grad(set_to_none=True)
+                        self._backward()
+                    finally:
+                        model.grad_sync.paused = False
+                        model.grad_sync.reset()
+            if not optimizer_steps:
+                opt.zero_grad(set_to_none=True)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         clear_weight_caches()
@@ -222,8 +244,13 @@ class GraphedTrainStep:
         with AG.grad_sink():
             m.loss_EAVSRP_Total.backward()
 
-    def step(self, batch=None):
+    def step(self, batch=None, epoch=None):
+        """Copy `batch` into the static buffers and replay.  `epoch` (default: model.epoch) decides the phase: a graph captured
+        before opt.npost holds no PWC-Net mask, one captured after it does, so crossing npost recaptures once (its warm-up
+        runs forward and backward without an optimizer step)."""
         m = self.model
+        if epoch is not None:
+            m.epoch = epoch
         if batch is not None:
             lr, hr = batch["lr_seq"], batch["hr_seq"]
             if lr.shape != self.static_lr.shape or hr.shape != self.static_hr.shape:
@@ -233,6 +260,10 @@ class GraphedTrainStep:
         if self.graph is None:
             raise RuntimeError("GraphedTrainStep: closed")
         m.data_lr_seq, m.data_hr_seq = self.static_lr, self.static_hr
+        phase = getattr(m, "masked_phase", None)
+        if phase is not None and phase() != self.masked:
+            self.graph = None
+            self._capture(1, optimizer_steps=False)
         for p, g in self._grads:
             p.grad = g
         if self.world == 1:      # the replayed Adam reads its learning rates from these device scalars

@@ -1431,13 +1431,18 @@ def avg_pool2(x: Tensor) -> Tensor:
     return out
 
 
-def resize_bilinear(x: Tensor, size: Tuple[int, int], channel_mul: Optional[Tuple[float, float]] = None) -> Tensor:
+def resize_bilinear(x: Tensor, size: Tuple[int, int], channel_mul: Optional[Tuple[float, float]] = None,
+                    out: Optional[Tensor] = None) -> Tensor:
     """F.interpolate(x, size, mode='bilinear', align_corners=False); `channel_mul` = (m0, m1) multiplies channels 0 / 1 of the
-    result (the flow rescaling of models/eavsrp_model.py:519-521)"""
+    result (the flow rescaling of models/eavsrp_model.py:519-521); `out`: an existing contiguous fp32 tensor of the result's
+    shape to write into (e.g. one half of a stacked batch) instead of a new one"""
     x = _chk(x, "x")
     n, c, hin, win = x.shape
     hout, wout = int(size[0]), int(size[1])
-    out = torch.empty((n, c, hout, wout), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((n, c, hout, wout), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, c, hout, wout) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("resize_bilinear: `out` must be a contiguous fp32 GPU tensor of the result's shape")
     m0, m1 = (1.0, 1.0) if channel_mul is None else (float(channel_mul[0]), float(channel_mul[1]))
     st = _stream(x)
     _launch("resize_bilinear", 8.0 * out.numel(), 4.0 * (x.numel() + out.numel()), x,
@@ -2277,3 +2282,130 @@ def scale_residual_h16(r: Tensor, scale: Tensor, x: Tensor) -> Tensor:
             lambda: lib().eavsr_scale_residual_h16(_p(r), _p(scale), _p(x), _p(out), n, c, h * w, code, st),
             "scale_residual_h16")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# PWC-Net of the late-training validity mask (models/pwc_net.py, models/base_model.py:294-354; csrc/pwc.hip).  Operands may be
+# channel slices of a larger buffer: (c, h, w) contiguous, any batch stride.
+# ------------------------------------------------------------------------------------------
+def _batch_stride(t: Tensor, name: str) -> int:
+    """batch stride (elements) of a 4-D fp32 GPU tensor whose (c, h, w) part is contiguous -- a channel slice of an NCHW buffer"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: dtype {t.dtype} unsupported (fp32 only)")
+    if t.dim() != 4:
+        raise ValueError(f"{name}: expected (n, c, h, w), got {tuple(t.shape)}")
+    n, c, h, w = t.shape
+    s = t.stride()
+    if (c > 1 and s[1] != h * w) or (h > 1 and s[2] != w) or (w > 1 and s[3] != 1):
+        raise ValueError(f"{name}: (c, h, w) must be contiguous (a channel slice of an NCHW buffer), strides {s}")
+    chw = c * h * w
+    if n == 1:
+        return max(int(s[0]), chw)
+    if s[0] < chw:
+        raise ValueError(f"{name}: batch stride {s[0]} < c*h*w = {chw}")
+    return int(s[0])
+
+
+def _out_or_new(out: Optional[Tensor], shape, like: Tensor, name: str) -> Tuple[Tensor, int]:
+    if out is None:
+        out = torch.empty(shape, device=like.device, dtype=torch.float32)
+    elif tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{name}: `out` has shape {tuple(out.shape)}, expected {tuple(shape)}")
+    return out, _batch_stride(out, name)
+
+
+_pwc_pack_cache = register_weight_cache({})
+
+
+def _packed_pwc_conv3x3(weight: Tensor) -> Tensor:
+    """[9][cin even][cout padded] form of a (cout, cin, 3, 3) weight for eavsr_pwc_conv3x3_f32; cached per weight object and
+    version, verified by identity."""
+    key = (id(weight), weight._version)
+    hit = _pwc_pack_cache.get(key)
+    if hit is not None and hit[0]() is weight:
+        return hit[1]
+    w = _chk(weight.detach(), "weight")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise NotImplementedError(f"pwc_conv3x3: weight shape {tuple(w.shape)} (3x3 only)")
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    elems = lib().eavsr_pwc_conv3x3_weight_elems(cout, cin)
+    if elems <= 0:
+        raise NotImplementedError(f"pwc_conv3x3: weight shape {tuple(w.shape)} unsupported")
+    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
+    with _DeviceOf(w):
+        N.check(lib().eavsr_pwc_pack_conv3x3_f32(_p(w), _p(packed), cout, cin, _stream(w)), "pwc_pack_conv3x3")
+    for k in [k for k in _pwc_pack_cache if k[0] == id(weight)]:
+        _pwc_pack_cache.pop(k, None)
+    _pwc_pack_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_pwc_pack_cache: c.pop(k, None)), packed)
+    return packed
+
+
+def pwc_conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, stride: int = 1, dilation: int = 1,
+                act: Optional[str] = "lrelu", slope: float = 0.1, out: Optional[Tensor] = None) -> Tensor:
+    """act(F.conv2d(x, weight, bias, stride, padding=dilation, dilation)) for act None | 'lrelu'; `x` and `out` may be channel
+    slices of larger buffers (models/pwc_net.py Extractor / Decoder / Refiner)"""
+    xs = _batch_stride(x, "x")
+    n, cin, h, w = x.shape
+    cout = int(weight.shape[0])
+    if int(weight.shape[1]) != cin:
+        raise ValueError(f"pwc_conv3x3: weight takes {int(weight.shape[1])} channels, input has {cin}")
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    wp = _packed_pwc_conv3x3(weight)
+    b = None if bias is None else _chk(bias.detach(), "bias")
+    out, os_ = _out_or_new(out, (n, cout, ho, wo), x, "out")
+    st = _stream(x)
+    px = float(n) * ho * wo
+    _launch("pwc_conv3x3", 2.0 * 9 * cin * cout * px, 4.0 * px * (cin + cout), x,
+            lambda: lib().eavsr_pwc_conv3x3_f32(_p(x), xs, _p(wp), _p(b), _p(out), os_, n, cin, h, w, cout, int(stride),
+                                                 int(dilation), ACT[act], float(slope), st), "pwc_conv3x3")
+    return out
+
+
+def pwc_deconv4x4s2(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """F.conv_transpose2d(x, weight (cin, 2, 4, 4), bias, stride=2, padding=1): netUpflow / netUpfeat (pwc_net.py:113-116)"""
+    xs = _batch_stride(x, "x")
+    n, cin, h, w = x.shape
+    if tuple(weight.shape) != (cin, 2, 4, 4):
+        raise ValueError(f"pwc_deconv4x4s2: weight {tuple(weight.shape)}, expected ({cin}, 2, 4, 4)")
+    wt = _chk(weight.detach(), "weight")
+    b = None if bias is None else _chk(bias.detach(), "bias")
+    out, os_ = _out_or_new(out, (n, 2, 2 * h, 2 * w), x, "out")
+    st = _stream(x)
+    _launch("pwc_deconv4x4s2", 2.0 * 4 * 4 * cin * 2 * n * h * w, 4.0 * n * h * w * (cin + 8), x,
+            lambda: lib().eavsr_pwc_deconv4x4s2_f32(_p(x), xs, _p(wt), _p(b), _p(out), os_, n, cin, h, w, st), "pwc_deconv4x4s2")
+    return out
+
+
+def pwc_correlation(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """leaky_relu(FunctionCorrelation(a, b), 0.1) (pwc/correlation/correlation.py:35-103, pwc_net.py:157-167): (n, 81, h, w)"""
+    as_, bs_ = _batch_stride(a, "a"), _batch_stride(b, "b")
+    if a.shape != b.shape:
+        raise ValueError(f"pwc_correlation: shapes {tuple(a.shape)} / {tuple(b.shape)} differ")
+    n, c, h, w = a.shape
+    out, os_ = _out_or_new(out, (n, 81, h, w), a, "out")
+    st = _stream(a)
+    _launch("pwc_correlation", 2.0 * 81 * c * n * h * w, 4.0 * n * h * w * (2 * c + 81), a,
+            lambda: lib().eavsr_pwc_correlation_f32(_p(a), as_, _p(b), bs_, _p(out), os_, n, c, h, w, st), "pwc_correlation")
+    return out
+
+
+def pwc_backwarp(x: Tensor, flow: Tensor, flow_mul: float = 1.0, out: Optional[Tensor] = None, with_mask: bool = False):
+    """Decoder.backwarp (pwc_net.py:184-207) / BaseModel.backwarp + get_backwarp's threshold (base_model.py:321-354): x warped by
+    flow_mul x flow (read nearest-upsampled by h / flow_h) on the align_corners=False grid, times the validity mask.  Returns
+    `out`, or (out, mask (n, 1, h, w)) with `with_mask`."""
+    xs, fs = _batch_stride(x, "x"), _batch_stride(flow, "flow")
+    n, c, h, w = x.shape
+    if flow.shape[0] != n or flow.shape[1] != 2:
+        raise ValueError(f"pwc_backwarp: flow {tuple(flow.shape)} for x {tuple(x.shape)}")
+    fh, fw = int(flow.shape[2]), int(flow.shape[3])
+    out, os_ = _out_or_new(out, (n, c, h, w), x, "out")
+    mask = torch.empty((n, 1, h, w), device=x.device, dtype=torch.float32) if with_mask else None
+    st = _stream(x)
+    _launch("pwc_backwarp", 8.0 * (c + 1) * n * h * w, 4.0 * n * h * w * (2 * c + 2 + (1 if with_mask else 0)), x,
+            lambda: lib().eavsr_pwc_backwarp_f32(_p(x), xs, _p(flow), fs, _p(out), os_, _p(mask), n, c, h, w, fh, fw,
+                                                  float(flow_mul), st), "pwc_backwarp")
+    return (out, mask) if with_mask else out

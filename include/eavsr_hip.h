@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define EAVSR_ABI_VERSION 30
+#define EAVSR_ABI_VERSION 31
 
 /* activation codes for eavsr_conv2d_f32 */
 #define EAVSR_ACT_NONE 0
@@ -620,6 +620,38 @@ int eavsr_nhwc_h16_to_nchw_f32(const void* in, const float* residual, float* out
 /* NHWC 16-bit RCAB tail: out = r * scale[n,c] + x  (scale fp32) */
 int eavsr_scale_residual_h16(const void* r, const float* scale, const void* x, void* out, int32_t n,
                              int32_t c, int32_t hw, int32_t dtype, void* stream);
+
+/* ---- PWC-Net of the late-training validity mask (ABI 31; csrc/pwc.hip) ----------------------------------------------------
+ * From epoch opt.npost on, the training forward (models/eavsrp_model.py:85-97, models/eavsrpx2_model.py:88-100) estimates the
+ * flow LR -> downscaled HR with a frozen PWC-Net (models/pwc_net.py) and multiplies the SR output by the validity mask of the HR
+ * frame warped by it (models/base_model.py:294-354).  All tensors fp32 NCHW; every operand has an explicit BATCH STRIDE (elements)
+ * with the channel stride h * w, so that the decoder's dense concatenations (pwc_net.py:170-174) are channel slices of one
+ * buffer per level. */
+/* every Conv2d of Extractor / Decoder / Refiner (pwc_net.py:30-90,126-157,212-229): 3x3, padding = dilation, stride 1 or 2
+ * (output (h - 1) / stride + 1), + bias, act EAVSR_ACT_NONE or EAVSR_ACT_LRELU (slope).  weight_packed:
+ * eavsr_pwc_conv3x3_weight_elems(cout, cin) floats written by eavsr_pwc_pack_conv3x3_f32 from the (cout, cin, 3, 3) weight. */
+int64_t eavsr_pwc_conv3x3_weight_elems(int32_t cout, int32_t cin);
+int eavsr_pwc_pack_conv3x3_f32(const float* weight, float* packed, int32_t cout, int32_t cin, void* stream);
+int eavsr_pwc_conv3x3_f32(const float* x, int64_t x_batch_stride, const float* weight_packed, const float* bias, float* out,
+                          int64_t out_batch_stride, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t stride,
+                          int32_t dilation, int32_t act, float slope, void* stream);
+/* netUpflow / netUpfeat (pwc_net.py:113-116): ConvTranspose2d(cin -> 2, kernel 4, stride 2, padding 1), (n, cin, h, w) ->
+ * (n, 2, 2h, 2w); weight (cin, 2, 4, 4) as the module stores it, bias (2) nullable. */
+int eavsr_pwc_deconv4x4s2_f32(const float* x, int64_t x_batch_stride, const float* weight, const float* bias, float* out,
+                              int64_t out_batch_stride, int32_t n, int32_t cin, int32_t h, int32_t w, void* stream);
+/* FunctionCorrelation (pwc/correlation/correlation.py:35-103) + leaky_relu(0.1) (pwc_net.py:157-167):
+ * out[n, (dy+4)*9 + (dx+4), y, x] = lrelu((1/c) sum_c a[n,c,y,x] b[n,c,y+dy,x+dx]), |dx|, |dy| <= 4, zero outside the image. */
+int eavsr_pwc_correlation_f32(const float* a, int64_t a_batch_stride, const float* b, int64_t b_batch_stride, float* out,
+                              int64_t out_batch_stride, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
+/* Decoder.backwarp (pwc_net.py:184-207) and BaseModel.backwarp + get_backwarp (base_model.py:321-354):
+ * grid_sample(x, linspace(-1 + 1/w, 1 - 1/w) + flow / ((w - 1) / 2), bilinear, zeros, align_corners=False) -- the pixel
+ * x + f w / (w - 1), not x + f -- with the flow read nearest-upsampled by s = h / flow_h (h == s flow_h, w == s flow_w) and
+ * multiplied by flow_mul (decoder: fltBackwarp at s = 1; final: the LR flow with s = flow_mul = scale, base_model.py:348).  A
+ * ones channel warped alongside is thresholded (> 0.999 -> 1, else 0); out = warped x mask (n, c, h, w); mask (nullable,
+ * contiguous (n, 1, h, w)) receives it.  h, w > 1. */
+int eavsr_pwc_backwarp_f32(const float* x, int64_t x_batch_stride, const float* flow, int64_t flow_batch_stride, float* out,
+                           int64_t out_batch_stride, float* mask, int32_t n, int32_t c, int32_t h, int32_t w, int32_t flow_h,
+                           int32_t flow_w, float flow_mul, void* stream);
 
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
