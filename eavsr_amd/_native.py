@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EAVSR_LIB_PATH") or os.path.join(
     _HERE, "lib", "libeavsr_lab.so" if os.environ.get("EAVSR_BUILD_LAB", "0") == "1" else "libeavsr_hip.so")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 p_f32 = C.c_void_p  # device pointers travel as integers
 i32 = C.c_int32
@@ -173,6 +173,13 @@ SIGNATURES = {
     "eavsr_pwc_deconv4x4s2_f32": (C.c_int, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "eavsr_pwc_correlation_f32": (C.c_int, [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
     "eavsr_pwc_backwarp_f32": (C.c_int, [vp, i64, vp, i64, vp, i64, vp] + [i32] * 6 + [f32, vp]),
+    # the opt-in bf16 training mode (ABI 32)
+    "eavsr_conv_weight_bf16x1_bytes": (C.c_size_t, [i32, i32, i32]),
+    "eavsr_pack_conv_weight_bf16x1": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "eavsr_pack_conv_weight_bf16x1_dgrad": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "eavsr_pack_conv_weight_bf16x1_multi": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+    "eavsr_conv3x3_bf16x1s": (C.c_int, [vp, vp, vp]),
+    "eavsr_conv_wgrad_bias_multi_bf16": (C.c_int, [vp, vp, i32, vp, vp, vp] + [i32] * 11 + [vp]),
 }
 
 # Entry points of the LAB build only (`python -m eavsr_amd.build --lab`; the header's EXPERIMENTAL section): bound when the

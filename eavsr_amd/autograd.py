@@ -77,11 +77,12 @@ class grad_sink:
     # their activations would otherwise stay alive until backward ends (peak memory, baked into the graph's pool)
     _last_uses = {}
 
-    def add_use(self, ws, bs, k, g, srcs):
+    def add_use(self, ws, bs, k, g, srcs, precision="fp32"):
         """One use of the weights `ws` (+ biases `bs`): dY = g over the sources `srcs`.  The gradient launch is DEFERRED: uses of
         the same call site and shapes wait until BATCH of them are there (or backward ends) and go through
         ops.conv_wgrad_multi / channel_sum_multi as segments of ONE launch -- a weight of the recurrent path is used once per
-        frame, and a 2 x 96 x 96 crop fills 72 tiles into 256 CUs per use.  Same sums, K extended over the uses; fixed order."""
+        frame, and a 2 x 96 x 96 crop fills 72 tiles into 256 CUs per use.  Same sums, K extended over the uses; fixed order.
+        precision: the mode of the forward that recorded the use (ops.conv_wgrad_multi); uses of two modes never share a launch."""
         key = tuple(id(w) for w in ws)
         e = self.entries.get(key)
         if e is None:
@@ -92,8 +93,10 @@ class grad_sink:
                  "uses": 0, "key": key}
             self.entries[key] = e
         if e["pending"] and (tuple(e["pending"][0][0].shape) != tuple(g.shape)
-                             or [tuple(s_.shape) for s_ in e["pending"][0][1]] != [tuple(s_.shape) for s_ in srcs]):
-            self._launch(e)       # another shape at the same call site: what waits goes first
+                             or [tuple(s_.shape) for s_ in e["pending"][0][1]] != [tuple(s_.shape) for s_ in srcs]
+                             or e.get("prec", "fp32") != precision):
+            self._launch(e)       # another shape (or precision) at the same call site: what waits goes first
+        e["prec"] = precision
         e["pending"].append((g, list(srcs)))
         e["uses"] += 1
         if len(e["pending"]) >= self.BATCH or e["uses"] == grad_sink._last_uses.get(key, -1):
@@ -106,7 +109,8 @@ class grad_sink:
             return
         acc = e["written"]
         # (the bias gradient rides in the weight-gradient launch: the 3x3 kernel stages dY anyway)
-        ops.conv_wgrad_multi([g for g, _ in pend], [ss for _, ss in pend], e["k"], out=e["dW"], accumulate=acc, bias_out=e["db"])
+        ops.conv_wgrad_multi([g for g, _ in pend], [ss for _, ss in pend], e["k"], out=e["dW"], accumulate=acc, bias_out=e["db"],
+                             precision=e.get("prec", "fp32"))
         e["written"] = True
         e["pending"] = []
 
@@ -164,6 +168,14 @@ def _dgrad_weight(ws, c0: int, cs: int) -> Tensor:
     return wt
 
 
+def _train_precision(ws, srcs) -> str:
+    """the precision of a recorded 3x3 64 -> 64 convolution: ops.TRAIN_PRECISION (networks.set_train_precision); "fp32" for every
+    other shape.  ops decides per launch whether the crop-sized kernel (the only one with a bf16 form) takes it."""
+    if ops.TRAIN_PRECISION == "fp32" or len(ws) != 1 or len(srcs) != 1 or tuple(ws[0].shape) != (64, 64, 3, 3):
+        return "fp32"
+    return ops.TRAIN_PRECISION
+
+
 class _ConvFn(Function):
     @staticmethod
     def forward(ctx, act, slope, n_w, has_bias, has_res, n_src, *ts):
@@ -175,8 +187,10 @@ class _ConvFn(Function):
         srcs = list(ts[o:o + n_src])
         if act is not None and has_res:
             raise NotImplementedError("conv2d backward: activation together with a residual is not used on the path")
-        out = ops.conv2d(srcs, ws, bs if has_bias else None, act=act, slope=slope, residual=res)
+        prec = _train_precision(ws, srcs)
+        out = ops.conv2d(srcs, ws, bs if has_bias else None, act=act, slope=slope, residual=res, precision=prec)
         ctx.meta = (act, slope, n_w, has_bias, has_res, n_src)
+        ctx.prec = prec      # the backward's input-gradient convolution and weight gradient run in the forward's mode
         ctx.params = (ws, bs if has_bias else None)    # the caller's tensor objects (grad_sink keys on them)
         ctx.save_for_backward(*ws, *srcs, *( [out] if act is not None else []))
         return out
@@ -198,13 +212,13 @@ class _ConvFn(Function):
         dws: List[Optional[Tensor]] = [None] * n_w
         pw, pb = ctx.params
         if all(need_w) and (not has_bias or all(need[n_w:2 * n_w])) and grad_sink.eligible(pw + (pb or [])):
-            grad_sink._active.add_use(pw, pb if has_bias else None, k, g, srcs)      # launched in batches of uses (grad_sink)
+            grad_sink._active.add_use(pw, pb if has_bias else None, k, g, srcs, precision=ctx.prec)      # launched in batches of uses (grad_sink)
             need_w = [False] * n_w
             has_bias_grad = False
         else:
             has_bias_grad = has_bias
         if any(need_w):
-            dW = ops.conv_wgrad(g, srcs, k)
+            dW = ops.conv_wgrad(g, srcs, k, precision=ctx.prec)
             c0 = 0
             for i, w_ in enumerate(ws):
                 dws[i] = dW[c0:c0 + w_.shape[0]] if need_w[i] else None
@@ -223,7 +237,7 @@ class _ConvFn(Function):
         for i, s in enumerate(srcs):
             cs = int(s.shape[1])
             if need_src[i]:
-                dsrcs.append(ops.conv2d(g, _dgrad_weight(ws, c0, cs), None))
+                dsrcs.append(ops.conv2d(g, _dgrad_weight(ws, c0, cs), None, precision=ctx.prec))
             else:
                 dsrcs.append(None)
             c0 += cs
@@ -505,8 +519,9 @@ class _RcabFn(Function):
     @staticmethod
     def forward(ctx, x, r_prev, w1, b1, w2, b2, wa, ba, wb, bb):
         n, c, h, w = x.shape
-        t = ops.conv2d([x], [w1], [b1], act="relu")
-        r, partial = ops.conv2d([t], [w2], [b2], chan_partial=True)
+        prec = ctx.prec = _train_precision([w1], [x])      # (both convolutions are 64 -> 64: rcab_supported)
+        t = ops.conv2d([x], [w1], [b1], act="relu", precision=prec)
+        r, partial = ops.conv2d([t], [w2], [b2], chan_partial=True, precision=prec)
         # the tail as ONE launch (every workgroup redoes the 64 -> 4 -> 64 MLP of its sample from the per-tile sums: 9 KB at a crop;
         # in the one-stream training graph the launch it saves is a pure gain -- unlike the two-stream inference step)
         out, scale, mean = ops.ca_tail(r, partial, wa, ba, wb, bb, x, with_stats=True)
@@ -520,6 +535,7 @@ class _RcabFn(Function):
     def backward(ctx, d, _dr_unused=None):
         x, t, r, mean, scale, w1, w2, wa, ba, wb, bb, r_prev = ctx.saved_tensors
         pw1, pb1, pw2, pb2, pca = ctx.params
+        prec = ctx.prec
         if d is None:      # (the block's output reached no loss term)
             return (None,) * 10
         d = d.contiguous()
@@ -536,23 +552,23 @@ class _RcabFn(Function):
             dr, *dca = ops.rcab_tail_bwd(d, r, mean, scale, wa, ba, wb, bb, dsum=dsum)
         # second convolution
         if sink is not None:
-            sink.add_use(pw2, pb2, 3, dr, [t])
+            sink.add_use(pw2, pb2, 3, dr, [t], precision=prec)
             dW2 = db2 = None
         else:
-            dW2, db2 = ops.conv_wgrad(dr, [t], 3), ops.channel_sum(dr)
+            dW2, db2 = ops.conv_wgrad(dr, [t], 3, precision=prec), ops.channel_sum(dr)
         # the ReLU's backward mask (t > 0) leaves in the epilogue of conv-2's input-gradient convolution
-        g1 = ops.conv2d(dr, w2, None, act="relu_mask", residual=t, dgrad=True)
+        g1 = ops.conv2d(dr, w2, None, act="relu_mask", residual=t, dgrad=True, precision=prec)
         # first convolution; the residual path's gradient d rides in its input-gradient convolution
         if sink is not None:
-            sink.add_use(pw1, pb1, 3, g1, [x])
+            sink.add_use(pw1, pb1, 3, g1, [x], precision=prec)
             dW1 = db1 = None
         else:
-            dW1, db1 = ops.conv_wgrad(g1, [x], 3), ops.channel_sum(g1)
+            dW1, db1 = ops.conv_wgrad(g1, [x], 3, precision=prec), ops.channel_sum(g1)
         if r_prev is not None and RCAB_CHAIN:      # x is the previous block's output: its backward starts with sum_hw dx * r_prev
-            dx, rows = ops.conv2d(g1, w1, None, residual=d, dgrad=True, sum_mul=r_prev)
+            dx, rows = ops.conv2d(g1, w1, None, residual=d, dgrad=True, sum_mul=r_prev, precision=prec)
             _chain.put_sums(dx, rows)
         else:
-            dx = ops.conv2d(g1, w1, None, residual=d, dgrad=True)
+            dx = ops.conv2d(g1, w1, None, residual=d, dgrad=True, precision=prec)
         return (dx, None, dW1, db1, dW2, db2) + tuple(dca)
 
 

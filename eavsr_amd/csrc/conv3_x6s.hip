@@ -22,6 +22,13 @@
 //   * epilogue in registers: bias (the accumulators' initial value), activation, residual / ReLU-mask (EAVSR_ACT_RELU_MASK),
 //     per-tile channel sums for the channel attention.
 // LDS: 130,560 (patch) + 30,720 (two weight slabs) + 1,152 = 162,432 bytes.
+//
+// NP = 1 (eavsr_conv3x3_bf16x1s, the opt-in bf16 training mode): every operand rounded ONCE to nearest even (v_cvt_pk_bf16_f32, =
+// torch's .to(torch.bfloat16)) into one plane, one MFMA per k-step.  LDS 43,520 (patch) + 10,240 + 1,152 = 54,912 bytes and 88-98
+// VGPRs: two workgroups fit a CU, so a launch's workgroups share CUs with the next launch's (the graph's chains overlap) instead
+// of waiting for a whole CU.  The 8 x 32 tile is kept: the chan_partial rows stay those of eavsr_conv3x3_x6s_tiles, and in the
+// configs[3] step (tools/gpu_train_precision_time.py, rocprofv3) a launch is 11.1 us against the exact kernel's 17.6 -- what is
+// left is the prologue load and the epilogue, so a smaller tile is the next thing to measure.
 #include "common.h"
 
 #include <mutex>
@@ -36,19 +43,22 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int Q_NW = 8, Q_TW = 32, Q_TH = 8;
 constexpr int Q_IW = Q_TW + 2, Q_IH = Q_TH + 2, Q_NPIX = Q_IW * Q_IH;      // 34 x 10 = 340 patch pixels
 constexpr int Q_PLANE_B = Q_NPIX * 16;                                     // one bf16 plane of one 8-channel chunk
-constexpr int Q_CHUNK_B = 3 * Q_PLANE_B;
 constexpr int Q_KSTEPS = 5;                                                // tap pairs per chunk: 9 taps + a zero tap
-constexpr int Q_SLAB_U4 = Q_KSTEPS * 3 * 64;                               // 16-byte elements of one chunk's A operands (32 channels)
 
-template <int NCH> struct QCfg {
-  static constexpr int PATCH_B = NCH * Q_CHUNK_B;
-  static constexpr size_t LDS_BYTES = (size_t)PATCH_B + 2 * (size_t)Q_SLAB_U4 * 16 + 32 * 4 + Q_NW * 32 * 4;
+// NP: bf16 planes per operand -- 3 = the exact split (eavsr_conv3x3_f32x6s), 1 = one bf16 rounded to nearest even
+// (eavsr_conv3x3_bf16x1s, the opt-in bf16 training mode)
+template <int NCH, int NP> struct QCfg {
+  static constexpr int CHUNK_B = NP * Q_PLANE_B;
+  static constexpr int SLAB_U4 = Q_KSTEPS * NP * 64;                       // 16-byte elements of one chunk's A operands (32 channels)
+  static constexpr int PATCH_B = NCH * CHUNK_B;
+  static constexpr size_t LDS_BYTES = (size_t)PATCH_B + 2 * (size_t)SLAB_U4 * 16 + 32 * 4 + Q_NW * 32 * 4;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+  static_assert(PATCH_B >= Q_NW * 32 * 36 * 4, "the VEC epilogue's transpose tiles live in the patch region");
 };
 
 struct QArgs {
   const float* x;        // (n, 8 NCH, h, w)
-  const u32x4* wsplit;   // eavsr_pack_conv_weight_x6(ksize 3): [cot][chunk][k-step][plane][mt][lane] 16-byte elements
+  const u32x4* wsplit;   // eavsr_pack_conv_weight_x6 / _bf16x1 (ksize 3): [cot][chunk][k-step][plane][mt][lane] 16-byte elements
   const float* bias;
   const float* residual; // added to the output -- or, act == EAVSR_ACT_RELU_MASK, the mask source
   float* out;            // (n, cout, h, w)
@@ -71,6 +81,20 @@ __device__ __forceinline__ void q_split2(float a, float b, unsigned& hi, unsigne
   lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
 }
 
+// two fp32 values rounded to nearest even into one packed bf16 pair (low half = first value): v_cvt_pk_bf16_f32, what
+// torch.Tensor.to(torch.bfloat16) computes (no truncation)
+__device__ __forceinline__ unsigned q_rne2(float a, float b) {
+  typedef float f2_ __attribute__((ext_vector_type(2)));
+  typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{a, b}, b2_));
+}
+
+// the NP bf16 planes of two fp32 values
+template <int NP> __device__ __forceinline__ void q_planes2(float a, float b, unsigned (&pl)[NP]) {
+  if constexpr (NP == 3) q_split2(a, b, pl[0], pl[1], pl[2]);
+  else pl[0] = q_rne2(a, b);
+}
+
 __device__ __forceinline__ f32x16 q_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -88,34 +112,36 @@ __device__ unsigned long long g_q_stamps[8];
 #define Q_STAMP(i) do { } while (0)
 #endif
 
-// eight channels of four consecutive pixels (one float4 per channel) -> the four pixels' 16-byte units of the three planes
-__device__ __forceinline__ void q_store_quad(const f32x4 (&q)[8], unsigned char* dst) {
+// eight channels of four consecutive pixels (one float4 per channel) -> the four pixels' 16-byte units of the NP planes
+template <int NP> __device__ __forceinline__ void q_store_quad(const f32x4 (&q)[8], unsigned char* dst) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    u32x4 pl[3];
+    u32x4 pl[NP];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      unsigned h2, m2, l2;
-      q_split2(q[2 * c][i], q[2 * c + 1][i], h2, m2, l2);
-      pl[0][c] = h2; pl[1][c] = m2; pl[2][c] = l2;
+      unsigned t[NP];
+      q_planes2<NP>(q[2 * c][i], q[2 * c + 1][i], t);
+#pragma unroll
+      for (int p3 = 0; p3 < NP; ++p3) pl[p3][c] = t[p3];
     }
 #pragma unroll
-    for (int p3 = 0; p3 < 3; ++p3) *reinterpret_cast<u32x4*>(dst + i * 16 + p3 * Q_PLANE_B) = pl[p3];
+    for (int p3 = 0; p3 < NP; ++p3) *reinterpret_cast<u32x4*>(dst + i * 16 + p3 * Q_PLANE_B) = pl[p3];
   }
 }
 
 // VEC: w % 4 == 0 and 16-byte aligned x / out / residual -- the patch is requested as float4 row segments (a wave's load
 // instruction costs the texture path 16 cycles whatever its width: 64 dword requests per thread were 6 K cycles of a 32 K-cycle
 // workgroup) and the output tile leaves through an LDS transpose as float4 row segments (16 dword stores per lane: 5.8 K cycles).
-template <int NCH, bool VEC>
+template <int NCH, bool VEC, int NP>
 __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
-  using K = QCfg<NCH>;
+  using K = QCfg<NCH, NP>;
+  constexpr int Q_CHUNK_B = K::CHUNK_B, Q_SLAB_U4 = K::SLAB_U4;
 #ifdef EAVSR_X6S_STAMPS
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long st_last = __builtin_amdgcn_s_memtime();
 #endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smemq[];
-  unsigned char* s_patch = smemq;                                            // [NCH][3 planes][10][34][16 B]
+  unsigned char* s_patch = smemq;                                            // [NCH][NP planes][10][34][16 B]
   u32x4* s_w = reinterpret_cast<u32x4*>(smemq + K::PATCH_B);                 // [2][Q_SLAB_U4]
   float* s_bias = reinterpret_cast<float*>(smemq + K::PATCH_B + 2 * Q_SLAB_U4 * 16);
   float* s_red = s_bias + 32;                                                // [8 waves][32 channels]
@@ -141,9 +167,9 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
     const char* wsrc = reinterpret_cast<const char*>(a.wsplit + ((size_t)wcot * NCH + ch) * (size_t)(Q_SLAB_U4 * a.wmt));
     u32x4* dst = s_w + (ch & 1) * Q_SLAB_U4;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int seg = i * Q_NW + wave;              // piece (k-step, plane) of this workgroup's 32 channels; 15 of them
-      if (seg < Q_KSTEPS * 3)                       // wave-uniform
+    for (int i = 0; i < (Q_KSTEPS * NP + Q_NW - 1) / Q_NW; ++i) {
+      const int seg = i * Q_NW + wave;              // piece (k-step, plane) of this workgroup's 32 channels; 5 NP of them
+      if (seg < Q_KSTEPS * NP)                      // wave-uniform
         __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + (unsigned)((seg * a.wmt + wsub) * 64 + lane) * 16u), (lptr_t)(dst + seg * 64), 16, 0, 0);
     }
   };
@@ -155,15 +181,16 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
   float pv[NCH][8];
   auto store_patch = [&](int ch) __attribute__((always_inline)) {
     if (tid < Q_NPIX) {
-      u32x4 pl[3];
+      u32x4 pl[NP];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        unsigned h2, m2, l2;
-        q_split2(pv[ch][2 * c], pv[ch][2 * c + 1], h2, m2, l2);
-        pl[0][c] = h2; pl[1][c] = m2; pl[2][c] = l2;
+        unsigned t[NP];
+        q_planes2<NP>(pv[ch][2 * c], pv[ch][2 * c + 1], t);
+#pragma unroll
+        for (int p3 = 0; p3 < NP; ++p3) pl[p3][c] = t[p3];
       }
 #pragma unroll
-      for (int p3 = 0; p3 < 3; ++p3) *reinterpret_cast<u32x4*>(s_patch + ch * Q_CHUNK_B + p3 * Q_PLANE_B + tid * 16) = pl[p3];
+      for (int p3 = 0; p3 < NP; ++p3) *reinterpret_cast<u32x4*>(s_patch + ch * Q_CHUNK_B + p3 * Q_PLANE_B + tid * 16) = pl[p3];
     }
   };
 
@@ -173,11 +200,11 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
   const int bbase = (wave * Q_IW + l31) * 16;
   const int b_same = bbase + (kg ? 16 : 0);
   const int b_wrap = bbase + (kg ? (Q_IW - 2) * 16 : 0);
-  auto read_b = [&](int ch, int s, u32x4 (&b)[3]) __attribute__((always_inline)) {
+  auto read_b = [&](int ch, int s, u32x4 (&b)[NP]) __attribute__((always_inline)) {
     const int tap0 = 2 * s, ky = tap0 / 3, kx = tap0 - 3 * ky;
     const unsigned char* base = s_patch + ch * Q_CHUNK_B + ((s == Q_KSTEPS - 1 ? bbase : kx == 2 ? b_wrap : b_same) + (ky * Q_IW + kx) * 16);
 #pragma unroll
-    for (int p3 = 0; p3 < 3; ++p3) {
+    for (int p3 = 0; p3 < NP; ++p3) {
       b[p3] = *reinterpret_cast<const u32x4*>(base + p3 * Q_PLANE_B);
       if (s == Q_KSTEPS - 1) {
 #pragma unroll
@@ -185,10 +212,10 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
       }
     }
   };
-  auto read_a = [&](int ch, int s, u32x4 (&av)[3]) __attribute__((always_inline)) {
-    const u32x4* ws = s_w + (ch & 1) * Q_SLAB_U4 + s * (3 * 64) + lane;
+  auto read_a = [&](int ch, int s, u32x4 (&av)[NP]) __attribute__((always_inline)) {
+    const u32x4* ws = s_w + (ch & 1) * Q_SLAB_U4 + s * (NP * 64) + lane;
 #pragma unroll
-    for (int p3 = 0; p3 < 3; ++p3) av[p3] = ws[p3 * 64];
+    for (int p3 = 0; p3 < NP; ++p3) av[p3] = ws[p3 * 64];
   };
 
   // ---- prologue --------------------------------------------------------------------------------------------------
@@ -229,18 +256,19 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
       s_bias[tid] = (a.bias && co < a.cout) ? a.bias[co] : 0.f;
     }
     Q_STAMP(0);      // requests issued
-    if (tid < 80 * NCH) q_store_quad(qa, s_patch + lds_a);
-    if (has_b) q_store_quad(qb, s_patch + lds_b);
+    if (tid < 80 * NCH) q_store_quad<NP>(qa, s_patch + lds_a);
+    if (has_b) q_store_quad<NP>(qb, s_patch + lds_b);
     if (has_h) {
-      u32x4 pl[3];
+      u32x4 pl[NP];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        unsigned h2, m2, l2;
-        q_split2(hv[2 * c], hv[2 * c + 1], h2, m2, l2);
-        pl[0][c] = h2; pl[1][c] = m2; pl[2][c] = l2;
+        unsigned t[NP];
+        q_planes2<NP>(hv[2 * c], hv[2 * c + 1], t);
+#pragma unroll
+        for (int p3 = 0; p3 < NP; ++p3) pl[p3][c] = t[p3];
       }
 #pragma unroll
-      for (int p3 = 0; p3 < 3; ++p3) *reinterpret_cast<u32x4*>(s_patch + lds_h + p3 * Q_PLANE_B) = pl[p3];
+      for (int p3 = 0; p3 < NP; ++p3) *reinterpret_cast<u32x4*>(s_patch + lds_h + p3 * Q_PLANE_B) = pl[p3];
     }
   } else {
     const float* sp = a.x + (size_t)bn * (NCH * 8) * plane + (pok ? (size_t)pgy * w + pgx : 0);
@@ -262,7 +290,7 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = s_bias[(r & 3) + 8 * (r >> 2) + 4 * kg];
-  u32x4 acur[3], bcur[3];
+  u32x4 acur[NP], bcur[NP];
   read_a(0, 0, acur);
   read_b(0, 0, bcur);
 
@@ -282,7 +310,7 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
       }
       if constexpr (!VEC)
         if (ks == 1 && more) store_patch(ch + 1);
-      u32x4 anext[3], bnext[3];
+      u32x4 anext[NP], bnext[NP];
       if (!last) {
         read_a(ch, ks + 1, anext);
         read_b(ch, ks + 1, bnext);
@@ -290,24 +318,32 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
         read_a(ch + 1, 0, anext);
         read_b(ch + 1, 0, bnext);
       }
-      // the six partial products, smallest first: (A plane, B plane) = (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-      acc = q_mfma(acur[2], bcur[0], acc);
-      acc = q_mfma(acur[0], bcur[2], acc);
-      acc = q_mfma(acur[1], bcur[1], acc);
-      acc = q_mfma(acur[1], bcur[0], acc);
-      acc = q_mfma(acur[0], bcur[1], acc);
-      acc = q_mfma(acur[0], bcur[0], acc);
-      if (!last || more) {
+      if constexpr (NP == 3) {
+        // the six partial products, smallest first: (A plane, B plane) = (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
+        acc = q_mfma(acur[2], bcur[0], acc);
+        acc = q_mfma(acur[0], bcur[2], acc);
+        acc = q_mfma(acur[1], bcur[1], acc);
+        acc = q_mfma(acur[1], bcur[0], acc);
+        acc = q_mfma(acur[0], bcur[1], acc);
+        acc = q_mfma(acur[0], bcur[0], acc);
+        if (!last || more) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA, one read, ..
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          for (int i = 0; i < 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA, one read, ..
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+        }
+      } else {
+        acc = q_mfma(acur[0], bcur[0], acc);                      // the one product of the rounded operands
+        if (!last || more) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // the MFMA, then the next k-step's two reads
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
       if (!last || more) {
 #pragma unroll
-        for (int p3 = 0; p3 < 3; ++p3) {
+        for (int p3 = 0; p3 < NP; ++p3) {
           acur[p3] = anext[p3];
           bcur[p3] = bnext[p3];
         }
@@ -456,26 +492,26 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
   }
 }
 
-template <int NCH, bool VEC>
-int launch_q(const QArgs& a, void* stream) {
-  using K = QCfg<NCH>;
+template <int NCH, bool VEC, int NP>
+int launch_q(const QArgs& a, void* stream, const char* name) {
+  using K = QCfg<NCH, NP>;
   static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
   const int dev_ = eavsr::current_device();
   static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
   hipError_t& attr_err = attr_err_pd[dev_];
   std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_x6s_kernel<NCH, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_x6s_kernel<NCH, VEC, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)K::LDS_BYTES);
   });
   if (attr_err != hipSuccess) {
-    eavsr::set_error("conv3x3_f32x6s: hipFuncSetAttribute(%zu B of LDS): %s", K::LDS_BYTES, hipGetErrorString(attr_err));
+    eavsr::set_error("%s: hipFuncSetAttribute(%zu B of LDS): %s", name, K::LDS_BYTES, hipGetErrorString(attr_err));
     return (int)attr_err;
   }
   const long blocks = (long)a.tiles_x * a.tiles_y * a.n;
-  EAVSR_REQUIRE(blocks < (1L << 31), -1, "conv3x3_f32x6s: too many tiles");
+  EAVSR_REQUIRE(blocks < (1L << 31), -1, "%s: too many tiles", name);
   dim3 grid((unsigned)blocks, eavsr::cdiv(a.cout, 32));
-  hipLaunchKernelGGL((conv3x3_x6s_kernel<NCH, VEC>), grid, dim3(64 * Q_NW), K::LDS_BYTES, eavsr::as_stream(stream), a);
-  return eavsr::launch_status("conv3x3_f32x6s");
+  hipLaunchKernelGGL((conv3x3_x6s_kernel<NCH, VEC, NP>), grid, dim3(64 * Q_NW), K::LDS_BYTES, eavsr::as_stream(stream), a);
+  return eavsr::launch_status(name);
 }
 
 }  // namespace
@@ -497,35 +533,56 @@ extern "C" int32_t eavsr_conv3x3_x6s_tiles(int32_t h, int32_t w) {
   return eavsr::cdiv(h, Q_TH) * eavsr::cdiv(w, Q_TW);
 }
 
-extern "C" int eavsr_conv3x3_f32x6s(const eavsr_conv2d_desc* d, const void* weight_x6, void* stream) {
-  EAVSR_REQUIRE(d && weight_x6, -1, "conv3x3_f32x6s: NULL pointer");
-  EAVSR_REQUIRE(d->ksize == 3 && d->n_src == 1 && d->src_c[0] == d->cin, -2, "conv3x3_f32x6s: one source, 3x3");
-  EAVSR_REQUIRE(d->cin == 64, -2, "conv3x3_f32x6s: cin %d (64 only; use eavsr_conv2d_f32)", d->cin);
-  EAVSR_REQUIRE(d->n >= 0 && d->cout > 0 && d->h > 0 && d->w > 0, -1, "conv3x3_f32x6s: bad dims");
-  if (d->n == 0) return 0;
-  EAVSR_REQUIRE(d->src[0] && d->out, -1, "conv3x3_f32x6s: NULL pointer");
+namespace {
+
+// the checks and the argument block shared by both entry points (`name` prefixes every message)
+int q_args(const eavsr_conv2d_desc* d, const void* wpacked, const char* name, QArgs& a, bool& vec) {
+  EAVSR_REQUIRE(d && wpacked, -1, "%s: NULL pointer", name);
+  EAVSR_REQUIRE(d->ksize == 3 && d->n_src == 1 && d->src_c[0] == d->cin, -2, "%s: one source, 3x3", name);
+  EAVSR_REQUIRE(d->cin == 64, -2, "%s: cin %d (64 only; use eavsr_conv2d_f32)", name, d->cin);
+  EAVSR_REQUIRE(d->n >= 0 && d->cout > 0 && d->h > 0 && d->w > 0, -1, "%s: bad dims", name);
+  if (d->n == 0) return 1;
+  EAVSR_REQUIRE(d->src[0] && d->out, -1, "%s: NULL pointer", name);
   EAVSR_REQUIRE(d->ca_scale == nullptr && d->ca_x == nullptr && d->ca_out == nullptr && d->out_shuffle == 0 && d->res_scale == nullptr && d->border_pieces == nullptr, -2,
-                "conv3x3_f32x6s: no channel-attention prologue, no pixel-shuffle store");
-  EAVSR_REQUIRE(d->act >= 0 && d->act <= EAVSR_ACT_RELU_MASK, -1, "conv3x3_f32x6s: act %d", d->act);
+                "%s: no channel-attention prologue, no pixel-shuffle store", name);
+  EAVSR_REQUIRE(d->act >= 0 && d->act <= EAVSR_ACT_RELU_MASK, -1, "%s: act %d", name, d->act);
   EAVSR_REQUIRE(d->act != EAVSR_ACT_LRELU || (d->slope >= 0.f && d->slope <= 1.f), -2,
-                "conv3x3_f32x6s: leaky-ReLU slope %g outside [0, 1] (the epilogue evaluates max(v, slope v))", (double)d->slope);
+                "%s: leaky-ReLU slope %g outside [0, 1] (the epilogue evaluates max(v, slope v))", name, (double)d->slope);
   EAVSR_REQUIRE(d->act != EAVSR_ACT_RELU_MASK || (d->residual != nullptr && d->chan_partial == nullptr), -1,
-                "conv3x3_f32x6s: EAVSR_ACT_RELU_MASK takes the mask source in `residual` (no channel sums)");
-  EAVSR_REQUIRE(d->sum_mul == nullptr || d->act != EAVSR_ACT_RELU_MASK, -1, "conv3x3_f32x6s: sum_mul with EAVSR_ACT_RELU_MASK");
-  EAVSR_REQUIRE((long)d->h * d->w < (1L << 31), -1, "conv3x3_f32x6s: image plane too large for 32-bit pixel offsets");
-  QArgs a;
-  a.x = d->src[0]; a.wsplit = reinterpret_cast<const u32x4*>(weight_x6); a.bias = d->bias; a.residual = d->residual;
+                "%s: EAVSR_ACT_RELU_MASK takes the mask source in `residual` (no channel sums)", name);
+  EAVSR_REQUIRE(d->sum_mul == nullptr || d->act != EAVSR_ACT_RELU_MASK, -1, "%s: sum_mul with EAVSR_ACT_RELU_MASK", name);
+  EAVSR_REQUIRE((long)d->h * d->w < (1L << 31), -1, "%s: image plane too large for 32-bit pixel offsets", name);
+  a.x = d->src[0]; a.wsplit = reinterpret_cast<const u32x4*>(wpacked); a.bias = d->bias; a.residual = d->residual;
   a.out = d->out; a.chan_partial = d->chan_partial; a.sum_mul = d->sum_mul;
   a.n = d->n; a.cout = d->cout; a.h = d->h; a.w = d->w;
   a.tiles_x = eavsr::cdiv(d->w, Q_TW); a.tiles_y = eavsr::cdiv(d->h, Q_TH);
   a.wmt = d->cout > 32 ? 2 : 1;
   a.act = d->act; a.slope = d->slope;
-  const bool vec = d->w % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.out) |
-                                       reinterpret_cast<uintptr_t>(a.residual)) & 15) == 0;
+  vec = d->w % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.out) |
+                           reinterpret_cast<uintptr_t>(a.residual)) & 15) == 0;
   EAVSR_REQUIRE(a.sum_mul == nullptr || (a.chan_partial != nullptr && vec && (reinterpret_cast<uintptr_t>(a.sum_mul) & 15) == 0), -2,
-                "conv3x3_f32x6s: sum_mul needs chan_partial, w %% 4 == 0 and 16-byte aligned tensors");
+                "%s: sum_mul needs chan_partial, w %% 4 == 0 and 16-byte aligned tensors", name);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int eavsr_conv3x3_f32x6s(const eavsr_conv2d_desc* d, const void* weight_x6, void* stream) {
+  QArgs a;
+  bool vec = false;
+  const int rc = q_args(d, weight_x6, "conv3x3_f32x6s", a, vec);
+  if (rc) return rc > 0 ? 0 : rc;      // (1: an empty batch)
 #ifdef EAVSR_X6S_NO_VEC
-  return launch_q<8, false>(a, stream);
+  return launch_q<8, false, 3>(a, stream, "conv3x3_f32x6s");
 #endif
-  return vec ? launch_q<8, true>(a, stream) : launch_q<8, false>(a, stream);
+  return vec ? launch_q<8, true, 3>(a, stream, "conv3x3_f32x6s") : launch_q<8, false, 3>(a, stream, "conv3x3_f32x6s");
+}
+
+// the opt-in bf16 training mode: the same launches with every operand rounded once (nearest even) to bf16, one product per k-step
+extern "C" int eavsr_conv3x3_bf16x1s(const eavsr_conv2d_desc* d, const void* weight_bf16x1, void* stream) {
+  QArgs a;
+  bool vec = false;
+  const int rc = q_args(d, weight_bf16x1, "conv3x3_bf16x1s", a, vec);
+  if (rc) return rc > 0 ? 0 : rc;
+  return vec ? launch_q<8, true, 1>(a, stream, "conv3x3_bf16x1s") : launch_q<8, false, 1>(a, stream, "conv3x3_bf16x1s");
 }

@@ -332,11 +332,16 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad3_kernel(WgradArgs a) {
 // channel shifted by the tap: elements c0 + kx + 1 .. c0 + kx + 8 of a row, c0 = 16 s + 8 g.  One aligned ds_read_b128 at c0 plus
 // a ds_read_b64 behind it give dwords D0..D5; kx = 1 is D1..D4 as they are, kx = 0 / 2 are funnel shifts by 16 bits
 // (v_alignbyte_b32), five per row and plane for both.
-struct Wx6Cfg {
+//
+// NP = 1 (eavsr_conv_wgrad_bias_multi_bf16, the opt-in bf16 training mode): dY and X rounded ONCE to nearest even
+// (v_cvt_pk_bf16_f32) on their way into LDS, one plane each, one product per k-step and tap; the same tiles, slabs and fixed-order
+// reduction.  Its operand tiles are a third (24,576 bytes); the cross-wave sum of the epilogue sets its LDS size (49,152).
+template <int NP> struct Wx6Cfg {
   static constexpr int TH = 4, TW = 32, IH = TH + 2;
   static constexpr int A_PITCH = TH * 64 + 16, A_PLANE = 32 * A_PITCH;          // 272, 8,704
   static constexpr int B_ROW = 80, B_PITCH = IH * B_ROW + 16, B_PLANE = 32 * B_PITCH;   // 496, 15,872
-  static constexpr size_t LDS_BYTES = 3 * (size_t)A_PLANE + 3 * (size_t)B_PLANE;        // 73,728
+  static constexpr size_t OPERAND_BYTES = NP * (size_t)A_PLANE + NP * (size_t)B_PLANE;  // NP = 3: 73,728
+  static constexpr size_t LDS_BYTES = OPERAND_BYTES > 3 * 4 * 1024 * 4 ? OPERAND_BYTES : 3 * 4 * 1024 * 4;
 };
 
 typedef unsigned wx_u32x4 __attribute__((ext_vector_type(4)));
@@ -371,18 +376,32 @@ __device__ __forceinline__ f32x4 wx_ld4(wx_rsrc r, unsigned voff, unsigned soff)
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
 
+// two fp32 values rounded to nearest even into one packed bf16 pair (low half = first value): v_cvt_pk_bf16_f32
+__device__ __forceinline__ unsigned wx_rne2(float a, float b) {
+  typedef float f2_ __attribute__((ext_vector_type(2)));
+  typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{a, b}, b2_));
+}
+
+// the NP bf16 planes of two fp32 values: NP = 3 the exact split, NP = 1 the rounded value
+template <int NP> __device__ __forceinline__ void wx_planes2(float a, float b, unsigned (&pl)[NP]) {
+  if constexpr (NP == 3) wx_split2(a, b, pl[0], pl[1], pl[2]);
+  else pl[0] = wx_rne2(a, b);
+}
+
 __device__ __forceinline__ f32x16 wx_mfma(const wx_u32x4& a, const wx_u32x4& b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wx_bf16x8, a), __builtin_bit_cast(wx_bf16x8, b), c, 0, 0, 0);
 }
 
+template <int NP>
 __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
-  using Cfg = Wx6Cfg;
-  constexpr int KK = 9, TH = Cfg::TH, TW = Cfg::TW, IH = Cfg::IH;
+  using Cfg = Wx6Cfg<NP>;
+  constexpr int KK = 9, TH = Cfg::TH, TW = Cfg::TW;
   constexpr int A_PITCH = Cfg::A_PITCH, A_PLANE = Cfg::A_PLANE, B_ROW = Cfg::B_ROW, B_PITCH = Cfg::B_PITCH, B_PLANE = Cfg::B_PLANE;
   static_assert(4 * 1024 * 4 <= Cfg::LDS_BYTES, "the cross-wave sum reuses the operand tiles");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   unsigned char* sA = reinterpret_cast<unsigned char*>(smem);
-  unsigned char* sB = sA + 3 * A_PLANE;
+  unsigned char* sB = sA + NP * A_PLANE;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -448,31 +467,34 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      unsigned h0, m0, l0, h1, m1, l1;
-      wx_split2(va[i][0], va[i][1], h0, m0, l0);
-      wx_split2(va[i][2], va[i][3], h1, m1, l1);
+      unsigned p0[NP], p1[NP];
+      wx_planes2<NP>(va[i][0], va[i][1], p0);
+      wx_planes2<NP>(va[i][2], va[i][3], p1);
       unsigned char* d = lds_a + i * 64;
-      *reinterpret_cast<wx_u32x2*>(d) = wx_u32x2{h0, h1};
-      *reinterpret_cast<wx_u32x2*>(d + A_PLANE) = wx_u32x2{m0, m1};
-      *reinterpret_cast<wx_u32x2*>(d + 2 * A_PLANE) = wx_u32x2{l0, l1};
+#pragma unroll
+      for (int p3 = 0; p3 < NP; ++p3) *reinterpret_cast<wx_u32x2*>(d + p3 * A_PLANE) = wx_u32x2{p0[p3], p1[p3]};
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      unsigned h0, m0, l0, h1, m1, l1;
-      wx_split2(vb[i][0], vb[i][1], h0, m0, l0);
-      wx_split2(vb[i][2], vb[i][3], h1, m1, l1);
+      unsigned p0[NP], p1[NP];
+      wx_planes2<NP>(vb[i][0], vb[i][1], p0);
+      wx_planes2<NP>(vb[i][2], vb[i][3], p1);
       unsigned* d = reinterpret_cast<unsigned*>(lds_b + i * B_ROW);
-      d[0] = h0; d[1] = h1;
-      d[B_PLANE / 4] = m0; d[B_PLANE / 4 + 1] = m1;
-      d[2 * (B_PLANE / 4)] = l0; d[2 * (B_PLANE / 4) + 1] = l1;
+#pragma unroll
+      for (int p3 = 0; p3 < NP; ++p3) {
+        d[p3 * (B_PLANE / 4)] = p0[p3];
+        d[p3 * (B_PLANE / 4) + 1] = p1[p3];
+      }
     }
     if (q8 < 6) {
-      unsigned h0, m0, l0;
-      wx_split2(vh[0], vh[1], h0, m0, l0);      // low halves: patch column 0 (element 1), high halves: column 33 (element 34)
+      unsigned ph[NP];
+      wx_planes2<NP>(vh[0], vh[1], ph);      // low halves: patch column 0 (element 1), high halves: column 33 (element 34)
       unsigned short* d = reinterpret_cast<unsigned short*>(lds_h);
-      d[1] = (unsigned short)h0; d[34] = (unsigned short)(h0 >> 16);
-      d[B_PLANE / 2 + 1] = (unsigned short)m0; d[B_PLANE / 2 + 34] = (unsigned short)(m0 >> 16);
-      d[2 * (B_PLANE / 2) + 1] = (unsigned short)l0; d[2 * (B_PLANE / 2) + 34] = (unsigned short)(l0 >> 16);
+#pragma unroll
+      for (int p3 = 0; p3 < NP; ++p3) {
+        d[p3 * (B_PLANE / 2) + 1] = (unsigned short)ph[p3];
+        d[p3 * (B_PLANE / 2) + 34] = (unsigned short)(ph[p3] >> 16);
+      }
     }
   };
 
@@ -502,12 +524,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
     // scheduler hoists every read of the tile to the top and spills the accumulators)
     const unsigned char* ap = sA + l31 * A_PITCH + wave * 64 + kg * 16;
     const unsigned char* bp = sB + l31 * B_PITCH + wave * B_ROW + kg * 16;
-    wx_u32x4 av[3], d03[3], n03[3];
-    wx_u32x2 d45[3], n45[3];
-    auto read_raw = [&](int g, wx_u32x4 (&r03)[3], wx_u32x2 (&r45)[3]) __attribute__((always_inline)) {
+    wx_u32x4 av[NP], d03[NP], n03[NP];
+    wx_u32x2 d45[NP], n45[NP];
+    auto read_raw = [&](int g, wx_u32x4 (&r03)[NP], wx_u32x2 (&r45)[NP]) __attribute__((always_inline)) {
       const int s_ = g / 3, ky = g - 3 * s_;
 #pragma unroll
-      for (int p3 = 0; p3 < 3; ++p3) {
+      for (int p3 = 0; p3 < NP; ++p3) {
         r03[p3] = *reinterpret_cast<const wx_u32x4*>(bp + p3 * B_PLANE + ky * B_ROW + s_ * 32);
         r45[p3] = *reinterpret_cast<const wx_u32x2*>(bp + p3 * B_PLANE + ky * B_ROW + s_ * 32 + 16);
       }
@@ -520,16 +542,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
       const int s_ = g / 3, ky = g - 3 * s_;
       if (ky == 0) {
 #pragma unroll
-        for (int p3 = 0; p3 < 3; ++p3) av[p3] = *reinterpret_cast<const wx_u32x4*>(ap + p3 * A_PLANE + s_ * 32);
+        for (int p3 = 0; p3 < NP; ++p3) av[p3] = *reinterpret_cast<const wx_u32x4*>(ap + p3 * A_PLANE + s_ * 32);
       }
 #ifdef EAVSR_WX6_NO_READAHEAD      // A/B (with EAVSR_WX6_PREFETCH: 18 registers less)
       read_raw(g, d03, d45);
 #else
       if (g + 1 < 6) read_raw(g + 1, n03, n45);
 #endif
-      wx_u32x4 b0[3], b1[3], b2[3];
+      wx_u32x4 b0[NP], b1[NP], b2[NP];
 #pragma unroll
-      for (int p3 = 0; p3 < 3; ++p3) {
+      for (int p3 = 0; p3 < NP; ++p3) {
         const unsigned s10 = __builtin_amdgcn_alignbyte(d03[p3][1], d03[p3][0], 2), s21 = __builtin_amdgcn_alignbyte(d03[p3][2], d03[p3][1], 2);
         const unsigned s32 = __builtin_amdgcn_alignbyte(d03[p3][3], d03[p3][2], 2), s43 = __builtin_amdgcn_alignbyte(d45[p3][0], d03[p3][3], 2);
         const unsigned s54 = __builtin_amdgcn_alignbyte(d45[p3][1], d45[p3][0], 2);
@@ -537,17 +559,21 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
         b1[p3] = wx_u32x4{d03[p3][1], d03[p3][2], d03[p3][3], d45[p3][0]};      // c0 + 2 .. c0 + 9:  kx = 1
         b2[p3] = wx_u32x4{s21, s32, s43, s54};                                  // c0 + 3 .. c0 + 10: kx = 2
       }
-      // the six partial products, smallest first: (A plane, B plane) = (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-#define WX_TAP(T, B)                             \
-      acc[T] = wx_mfma(av[2], B[0], acc[T]);     \
-      acc[T] = wx_mfma(av[0], B[2], acc[T]);     \
-      acc[T] = wx_mfma(av[1], B[1], acc[T]);     \
-      acc[T] = wx_mfma(av[1], B[0], acc[T]);     \
-      acc[T] = wx_mfma(av[0], B[1], acc[T]);     \
-      acc[T] = wx_mfma(av[0], B[0], acc[T]);
+      // the six partial products, smallest first: (A plane, B plane) = (2,0) (0,2) (1,1) (1,0) (0,1) (0,0); NP = 1: the one product
+#define WX_TAP(T, B)                               \
+      if constexpr (NP == 3) {                     \
+        acc[T] = wx_mfma(av[2], B[0], acc[T]);     \
+        acc[T] = wx_mfma(av[0], B[2], acc[T]);     \
+        acc[T] = wx_mfma(av[1], B[1], acc[T]);     \
+        acc[T] = wx_mfma(av[1], B[0], acc[T]);     \
+        acc[T] = wx_mfma(av[0], B[1], acc[T]);     \
+        acc[T] = wx_mfma(av[0], B[0], acc[T]);     \
+      } else {                                     \
+        acc[T] = wx_mfma(av[0], B[0], acc[T]);     \
+      }
 #ifdef EAVSR_WX6_EXP_NO_MFMA      // ablation (tools/gpu_wgrad_diag.py): operands read and shifted, not multiplied
 #pragma unroll
-      for (int p3 = 0; p3 < 3; ++p3) asm volatile("" ::"v"(b0[p3]), "v"(b1[p3]), "v"(b2[p3]), "v"(av[p3]));
+      for (int p3 = 0; p3 < NP; ++p3) asm volatile("" ::"v"(b0[p3]), "v"(b1[p3]), "v"(b2[p3]), "v"(av[p3]));
 #else
       WX_TAP(ky * 3 + 0, b0)
       WX_TAP(ky * 3 + 1, b1)
@@ -558,7 +584,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
 #ifndef EAVSR_WX6_NO_READAHEAD
       if (g + 1 < 6) {
 #pragma unroll
-        for (int p3 = 0; p3 < 3; ++p3) {
+        for (int p3 = 0; p3 < NP; ++p3) {
           d03[p3] = n03[p3];
           d45[p3] = n45[p3];
         }
@@ -694,6 +720,7 @@ int launch_wgrad3(const WgradArgs& a, int blocks, hipStream_t st) {
   return eavsr::launch_status("conv_wgrad");
 }
 
+template <int NP>
 int launch_wgrad3_x6(const WgradArgs& a, int blocks, hipStream_t st) {
   static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
   const int dev_ = eavsr::current_device();
@@ -701,14 +728,14 @@ int launch_wgrad3_x6(const WgradArgs& a, int blocks, hipStream_t st) {
   static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
   hipError_t& attr_err = attr_err_pd[dev_];
   std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3_x6_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wx6Cfg::LDS_BYTES);
+    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3_x6_kernel<NP>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wx6Cfg<NP>::LDS_BYTES);
   });
   if (attr_err != hipSuccess) {
     eavsr::set_error("conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
     return (int)attr_err;
   }
-  hipLaunchKernelGGL(conv_wgrad3_x6_kernel, dim3(blocks, 4), dim3(256), Wx6Cfg::LDS_BYTES, st, a);
+  hipLaunchKernelGGL(conv_wgrad3_x6_kernel<NP>, dim3(blocks, 4), dim3(256), Wx6Cfg<NP>::LDS_BYTES, st, a);
   return eavsr::launch_status("conv_wgrad");
 }
 
@@ -742,10 +769,13 @@ extern "C" int eavsr_conv_wgrad_multi_f32(const void* const* dy_list, const void
                                          cin_total, ci_dst0, ksize, accumulate, stream);
 }
 
-extern "C" int eavsr_conv_wgrad_bias_multi_f32(const void* const* dy_list, const void* const* x_list, int32_t nseg, float* dweight,
-                                               float* dbias, float* workspace, int32_t n, int32_t h, int32_t w, int32_t cout_total,
-                                               int32_t co0, int32_t cin_src, int32_t ci0, int32_t cin_total, int32_t ci_dst0,
-                                               int32_t ksize, int32_t accumulate, void* stream) {
+namespace {
+
+// bf16: the one-plane kernel (eavsr_conv_wgrad_bias_multi_bf16) -- 3x3, w % 4 == 0 and 16-byte aligned segments only; anything
+// else is an error there, not a quiet change of precision
+int wgrad_multi(const void* const* dy_list, const void* const* x_list, int32_t nseg, float* dweight, float* dbias, float* workspace,
+                int32_t n, int32_t h, int32_t w, int32_t cout_total, int32_t co0, int32_t cin_src, int32_t ci0, int32_t cin_total,
+                int32_t ci_dst0, int32_t ksize, int32_t accumulate, void* stream, bool bf16) {
   EAVSR_REQUIRE(dy_list && x_list && dweight && workspace, -1, "conv_wgrad: NULL pointer");
   EAVSR_REQUIRE(nseg >= 1 && nseg <= WG_MAX_SEG, -1, "conv_wgrad: %d segments (1..%d)", nseg, WG_MAX_SEG);
   EAVSR_REQUIRE(ksize == 1 || ksize == 3 || ksize == 5, -2, "conv_wgrad: kernel size %d unsupported (1, 3, 5)", ksize);
@@ -773,19 +803,26 @@ extern "C" int eavsr_conv_wgrad_bias_multi_f32(const void* const* dy_list, const
   hipStream_t st = eavsr::as_stream(stream);
   int rc, slabs = blocks;
   // the bf16x6 kernel: float4 row segments, i.e. w % 4 == 0 and 16-byte aligned tensors (anything else: the fp32 kernel)
-  bool x6 = ksize == 3 && n > 0 && w % 4 == 0 && (long)h * w * 128 < (1L << 31) && wgrad3_x6_enabled();
+  bool x6 = ksize == 3 && n > 0 && w % 4 == 0 && (long)h * w * 128 < (1L << 31) && (bf16 || wgrad3_x6_enabled());
   for (int s = 0; x6 && s < nseg; ++s)
     x6 = ((reinterpret_cast<uintptr_t>(a.dyv[s]) | reinterpret_cast<uintptr_t>(a.xv[s])) & 15) == 0;
+  if (bf16) {
+    EAVSR_REQUIRE(ksize == 3, -2, "conv_wgrad_bf16: kernel size %d (3 only)", ksize);
+    EAVSR_REQUIRE(n == 0 || x6, -2, "conv_wgrad_bf16: needs w %% 4 == 0 (w = %d), 16-byte aligned segments and h w 128 < 2^31", w);
+  }
   const int kk = ksize * ksize;
   if (x6) {
     WgradArgs b = a;
     if (dbias != nullptr) b.ws_bias = workspace + (size_t)blocks * 64 * 64 * kk;      // behind the slabs (the caller sized it)
-    b.tiles_y = eavsr::cdiv(h, Wx6Cfg::TH);
+    b.tiles_y = eavsr::cdiv(h, Wx6Cfg<3>::TH);
     EAVSR_REQUIRE((long)b.tiles_x * b.tiles_y * n * nseg < (1L << 31), -1, "conv_wgrad: too many tiles");
     b.num_tiles = b.tiles_x * b.tiles_y * n * nseg;
     slabs = b.num_tiles < 128 ? b.num_tiles : 128;      // two 4-wave workgroups per CU; never more slabs than `blocks`
     if (slabs > blocks) slabs = blocks;
-    rc = launch_wgrad3_x6(b, slabs, st);
+    rc = bf16 ? launch_wgrad3_x6<1>(b, slabs, st) : launch_wgrad3_x6<3>(b, slabs, st);
+  } else if (bf16) {      // (an empty batch: the reduction below writes zeros, or leaves an accumulated result as it is)
+    rc = 0;
+    slabs = 0;
   } else {
     switch (ksize) {
       case 1: rc = launch_wgrad<1>(a, blocks, st); break;
@@ -794,9 +831,9 @@ extern "C" int eavsr_conv_wgrad_bias_multi_f32(const void* const* dy_list, const
     }
   }
   if (rc) return rc;
-  const bool bias_in_kernel = x6 && dbias != nullptr;
+  const bool bias_in_kernel = (x6 || bf16) && dbias != nullptr;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(64 * kk + (bias_in_kernel ? 1 : 0)), dim3(512), 0, st, workspace, dweight,
-                     n == 0 ? 0 : slabs, kk, co0, a.co_valid, ci_dst0, a.ci_valid, cin_total, accumulate, x6 ? 1 : 0,
+                     n == 0 ? 0 : slabs, kk, co0, a.co_valid, ci_dst0, a.ci_valid, cin_total, accumulate, (x6 || bf16) ? 1 : 0,
                      bias_in_kernel ? workspace + (size_t)blocks * 64 * 64 * kk : nullptr, dbias);
   rc = eavsr::launch_status("conv_wgrad_reduce");
   if (rc) return rc;
@@ -804,6 +841,24 @@ extern "C" int eavsr_conv_wgrad_bias_multi_f32(const void* const* dy_list, const
   if (dbias != nullptr && !bias_in_kernel && co0 == 0)
     return eavsr_channel_sum_multi_f32(dy_list, nseg, dbias, n, cout_total, h * w, accumulate, stream);
   return 0;
+}
+
+}  // namespace
+
+extern "C" int eavsr_conv_wgrad_bias_multi_f32(const void* const* dy_list, const void* const* x_list, int32_t nseg, float* dweight,
+                                               float* dbias, float* workspace, int32_t n, int32_t h, int32_t w, int32_t cout_total,
+                                               int32_t co0, int32_t cin_src, int32_t ci0, int32_t cin_total, int32_t ci_dst0,
+                                               int32_t ksize, int32_t accumulate, void* stream) {
+  return wgrad_multi(dy_list, x_list, nseg, dweight, dbias, workspace, n, h, w, cout_total, co0, cin_src, ci0, cin_total, ci_dst0, ksize,
+                     accumulate, stream, false);
+}
+
+extern "C" int eavsr_conv_wgrad_bias_multi_bf16(const void* const* dy_list, const void* const* x_list, int32_t nseg, float* dweight,
+                                                float* dbias, float* workspace, int32_t n, int32_t h, int32_t w, int32_t cout_total,
+                                                int32_t co0, int32_t cin_src, int32_t ci0, int32_t cin_total, int32_t ci_dst0,
+                                                int32_t ksize, int32_t accumulate, void* stream) {
+  return wgrad_multi(dy_list, x_list, nseg, dweight, dbias, workspace, n, h, w, cout_total, co0, cin_src, ci0, cin_total, ci_dst0, ksize,
+                     accumulate, stream, true);
 }
 
 // ksize 1 over a span of 64-channel source blocks in ONE launch (+ one reduction): DCNv2's weight gradient is the 1x1 weight gradient

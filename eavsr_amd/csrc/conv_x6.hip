@@ -421,6 +421,8 @@ struct PackMultiArgs {
   u32x4* dst[PM_MAX];
   unsigned long long tr_mask;      // bit t: weight t is packed transposed and flipped (its input-gradient form)
 };
+// NP = 3: the exact split (eavsr_pack_conv_weight_x6_multi); NP = 1: one bf16 rounded to nearest even (_bf16x1_multi)
+template <int NP>
 __global__ void pack7_multi_kernel(PackMultiArgs a, int cout, int cin, int kk, int mt_n, long total) {
   const int t = blockIdx.y;
   const int tr = (int)((a.tr_mask >> t) & 1ull);
@@ -432,7 +434,7 @@ __global__ void pack7_multi_kernel(PackMultiArgs a, int cout, int cin, int kk, i
   long q = e;
   const int lane = (int)(q % 64); q /= 64;
   const int mt = (int)(q % mt_n); q /= mt_n;
-  const int pl = (int)(q % 3); q /= 3;
+  const int pl = (int)(q % NP); q /= NP;
   const int s = (int)(q % ksteps); q /= ksteps;
   const int nch = cin / 8;
   const int ch = (int)(q % nch);
@@ -448,9 +450,13 @@ __global__ void pack7_multi_kernel(PackMultiArgs a, int cout, int cin, int kk, i
       const int ci = ch * 8 + 2 * c + u;
       v[u] = (co < cout && tap < kk) ? (tr ? wt[((size_t)ci * cout + co) * kk + (kk - 1 - tap)] : wt[((size_t)co * cin + ci) * kk + tap]) : 0.f;
     }
-    unsigned h2, m2, l2;
-    s_split2(v[0], v[1], h2, m2, l2);
-    o[c] = pl == 0 ? h2 : pl == 1 ? m2 : l2;
+    if constexpr (NP == 3) {
+      unsigned h2, m2, l2;
+      s_split2(v[0], v[1], h2, m2, l2);
+      o[c] = pl == 0 ? h2 : pl == 1 ? m2 : l2;
+    } else {
+      o[c] = s_round2<2>(v[0], v[1]);
+    }
   }
   p[e] = o;
 }
@@ -558,10 +564,58 @@ extern "C" int eavsr_pack_conv_weight_x6_multi(const float* const* weights, void
       a.dst[t] = reinterpret_cast<u32x4*>(packed[u]);
       if (t < m && transposed[u]) a.tr_mask |= 1ull << t;
     }
-    hipLaunchKernelGGL(pack7_multi_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)m), dim3(256), 0, eavsr::as_stream(stream), a, c, c,
-                       ksize * ksize, mt_of(c), total);
+    hipLaunchKernelGGL(pack7_multi_kernel<3>, dim3((unsigned)((total + 255) / 256), (unsigned)m), dim3(256), 0, eavsr::as_stream(stream), a, c,
+                       c, ksize * ksize, mt_of(c), total);
   }
   return eavsr::launch_status("pack_conv_weight_x6_multi");
+}
+
+// ---- the bf16 training mode's form of the 3x3 weight (eavsr_conv3x3_bf16x1s): one plane, every value rounded to nearest even ----
+extern "C" size_t eavsr_conv_weight_bf16x1_bytes(int32_t ksize, int32_t cout, int32_t cin) {
+  return ksize == 3 ? eavsr_conv_weight_x6_bytes(ksize, cout, cin) / 3 : 0;
+}
+
+extern "C" int eavsr_pack_conv_weight_bf16x1(const float* weight, void* packed, int32_t ksize, int32_t cout, int32_t cin, void* stream) {
+  EAVSR_REQUIRE(weight && packed, -1, "pack_conv_weight_bf16x1: NULL pointer");
+  EAVSR_REQUIRE(ksize == 3, -2, "pack_conv_weight_bf16x1: kernel size %d (3 only)", ksize);
+  EAVSR_REQUIRE(cout > 0 && cin > 0 && cin % 8 == 0, -1, "pack_conv_weight_bf16x1: cin %d must be a multiple of 8", cin);
+  const long total = (long)(eavsr_conv_weight_bf16x1_bytes(ksize, cout, cin) / 16);
+  hipLaunchKernelGGL(pack7_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, eavsr::as_stream(stream), weight,
+                     reinterpret_cast<u32x4*>(packed), cout, cin, ksize * ksize, mt_of(cout), total, 1, 2);
+  return eavsr::launch_status("pack_conv_weight_bf16x1");
+}
+
+extern "C" int eavsr_pack_conv_weight_bf16x1_dgrad(const float* weight, void* packed, int32_t ksize, int32_t cout_w, int32_t cin_w, void* stream) {
+  EAVSR_REQUIRE(weight && packed, -1, "pack_conv_weight_bf16x1_dgrad: NULL pointer");
+  EAVSR_REQUIRE(ksize == 3, -2, "pack_conv_weight_bf16x1_dgrad: kernel size %d (3 only)", ksize);
+  EAVSR_REQUIRE(cout_w > 0 && cin_w > 0 && cout_w % 8 == 0, -1, "pack_conv_weight_bf16x1_dgrad: cout %d must be a multiple of 8", cout_w);
+  const long total = (long)(eavsr_conv_weight_bf16x1_bytes(ksize, cin_w, cout_w) / 16);
+  hipLaunchKernelGGL(pack7_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, eavsr::as_stream(stream), weight,
+                     reinterpret_cast<u32x4*>(packed), cin_w, cout_w, ksize * ksize, mt_of(cin_w), total, 1, 2, 1);
+  return eavsr::launch_status("pack_conv_weight_bf16x1_dgrad");
+}
+
+extern "C" int eavsr_pack_conv_weight_bf16x1_multi(const float* const* weights, void* const* packed, const int32_t* transposed,
+                                                   int32_t count, int32_t ksize, int32_t c, void* stream) {
+  EAVSR_REQUIRE(count >= 0 && (count == 0 || (weights && packed && transposed)), -1, "pack_conv_weight_bf16x1_multi: NULL pointer");
+  EAVSR_REQUIRE(ksize == 3, -2, "pack_conv_weight_bf16x1_multi: kernel size %d (3 only)", ksize);
+  EAVSR_REQUIRE(c > 0 && c % 8 == 0, -1, "pack_conv_weight_bf16x1_multi: %d channels must be a multiple of 8", c);
+  const long total = (long)(eavsr_conv_weight_bf16x1_bytes(ksize, c, c) / 16);
+  for (int t0 = 0; t0 < count; t0 += PM_MAX) {
+    PackMultiArgs a;
+    a.tr_mask = 0ull;
+    const int m = count - t0 < PM_MAX ? count - t0 : PM_MAX;
+    for (int t = 0; t < PM_MAX; ++t) {
+      const int u = t < m ? t0 + t : t0;
+      EAVSR_REQUIRE(weights[u] && packed[u], -1, "pack_conv_weight_bf16x1_multi: NULL pointer in entry %d", u);
+      a.src[t] = weights[u];
+      a.dst[t] = reinterpret_cast<u32x4*>(packed[u]);
+      if (t < m && transposed[u]) a.tr_mask |= 1ull << t;
+    }
+    hipLaunchKernelGGL(pack7_multi_kernel<1>, dim3((unsigned)((total + 255) / 256), (unsigned)m), dim3(256), 0, eavsr::as_stream(stream), a, c,
+                       c, ksize * ksize, mt_of(c), total);
+  }
+  return eavsr::launch_status("pack_conv_weight_bf16x1_multi");
 }
 
 extern "C" int eavsr_conv_f32x6(const float* x, const void* weight_x6, const float* bias, float* out, int32_t n, int32_t cin,

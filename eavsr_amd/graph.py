@@ -145,6 +145,7 @@ class GraphedTrainStep:
     """
 
     masked = False       # the captured forward holds the PWC-Net mask of epochs >= opt.npost (set by _capture)
+    precision = None     # ... and the training precision it was captured in (networks.set_train_precision; set by _capture)
 
     def __init__(self, model, warmup: int = 2):
         import torch.distributed as dist
@@ -177,6 +178,9 @@ class GraphedTrainStep:
         model, dev, opt = self.model, self.model.device, self.model.optimizer_EAVSRP
         # whether the captured forward holds the PWC-Net mask of epochs >= opt.npost: step() recaptures when the phase changes
         self.masked = model.masked_phase()
+        # ... and the training precision (networks.set_train_precision): the kernels it selects are baked into the graph
+        from . import ops
+        self.precision = ops.TRAIN_PRECISION
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -260,8 +264,10 @@ class GraphedTrainStep:
         if self.graph is None:
             raise RuntimeError("GraphedTrainStep: closed")
         m.data_lr_seq, m.data_hr_seq = self.static_lr, self.static_hr
+        from . import ops
         phase = getattr(m, "masked_phase", None)
-        if phase is not None and phase() != self.masked:
+        # crossing npost, or another training precision (networks.set_train_precision): recapture once
+        if (phase is not None and phase() != self.masked) or (self.precision is not None and ops.TRAIN_PRECISION != self.precision):
             self.graph = None
             self._capture(1, optimizer_steps=False)
         for p, g in self._grads:

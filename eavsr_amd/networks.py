@@ -471,6 +471,40 @@ def backbone_dtype(dtype):
         set_backbone_dtype(prev)
 
 
+TRAIN_PRECISIONS = ops.TRAIN_PRECISIONS
+
+
+def set_train_precision(mode: str) -> None:
+    """The opt-in bf16 TRAINING mode, in the spirit of torch.set_float32_matmul_precision("medium"): "fp32" (the default, from
+    EAVSR_TRAIN_PRECISION: every convolution exact) or "bf16".  Anything else raises ValueError.
+
+    Scope of "bf16": the 3x3 64 -> 64 convolutions that autograd RECORDS (autograd._ConvFn and _RcabFn: RCABlock's convolutions
+    in training), their backward's input-gradient convolutions and their weight gradients -- wherever the crop-sized kernel takes
+    the launch (ops.x6s_takes: at most ops.X6S_MAX_TILES 8 x 32-pixel tiles; the weight gradient also needs w % 4 == 0).  There every
+    operand is rounded once to bf16 (nearest even) and each k-step is one bf16 product with fp32 accumulation; bias, activation
+    and residual stay fp32.  Everything else is exactly as in "fp32": no-grad forwards (inference, evaluation in the middle of
+    training through eavsr_amd.harness), the Winograd launches of large crops, 5x5 / 7x7, DCNv2 and the grouped convolutions.
+    The mode is read at each recorded forward; a GraphedTrainStep recaptures when it changes.  (bench.py's result line keeps
+    reporting `dtype: f32`: that field names the backbone activations, not this mode.)"""
+    ops.TRAIN_PRECISION = ops.check_precision(mode)
+
+
+def get_train_precision() -> str:
+    return ops.TRAIN_PRECISION
+
+
+@_contextlib.contextmanager
+def train_precision(mode: str):
+    """`with networks.train_precision("bf16"): model.optimize_parameters()` -- the previous mode is restored on exit, also when
+    the body raises."""
+    prev = ops.TRAIN_PRECISION
+    set_train_precision(mode)
+    try:
+        yield
+    finally:
+        ops.TRAIN_PRECISION = prev
+
+
 class RCAGroup(nn.Module):
     def __init__(self, in_channels=64, out_channels=64, kernel_size=3, stride=1, padding=1, bias=True,
                  mode="CRC", reduction=16, nb=12):

@@ -384,36 +384,87 @@ def _packed_conv_x6(weights: Sequence[Tensor], dgrad: bool = False) -> Tensor:
     return packed
 
 
-def prepack_conv3_x6(weights: Sequence[Tensor]) -> int:
+# The opt-in bf16 training mode (networks.set_train_precision / EAVSR_TRAIN_PRECISION): "fp32" (the default: every convolution
+# exact) or "bf16" -- the 3x3 64 -> 64 convolutions that autograd records, their input-gradient convolutions and their weight
+# gradients, where the crop-sized kernel runs (x6s_takes), take their operands rounded once to bf16 (csrc/conv3_x6s.hip NP = 1,
+# csrc/conv_wgrad.hip NP = 1).  autograd reads this at each recorded forward; ops itself only follows its `precision` arguments.
+TRAIN_PRECISIONS = ("fp32", "bf16")
+TRAIN_PRECISION = os.environ.get("EAVSR_TRAIN_PRECISION", "fp32")
+if TRAIN_PRECISION not in TRAIN_PRECISIONS:
+    raise ValueError(f"EAVSR_TRAIN_PRECISION={TRAIN_PRECISION!r}: one of {TRAIN_PRECISIONS}")
+
+
+def check_precision(precision: str) -> str:
+    if precision not in TRAIN_PRECISIONS:
+        raise ValueError(f"precision {precision!r}: one of {TRAIN_PRECISIONS}")
+    return precision
+
+
+# bf16 training mode: the one-plane packed forms (eavsr_pack_conv_weight_bf16x1*), a cache of their own -- never confused with the
+# exact forms of _conv7_pack_cache, whatever the mode was when either was packed
+_bf16_pack_cache = register_weight_cache({})
+
+
+def _packed_conv3_bf16(weights: Sequence[Tensor], dgrad: bool = False) -> Tensor:
+    """_packed_conv_x6 for eavsr_conv3x3_bf16x1s: every value rounded once to bf16 (nearest even), one plane"""
+    key = tuple((id(w), w._version) for w in weights) + ((("dgrad", 0),) if dgrad else ())
+    hit = _bf16_pack_cache.get(key)
+    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
+        return hit[1]
+    w = _chk(_cat_weights(weights).detach(), "weight")
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
+    if dgrad:
+        packed = torch.empty(lib().eavsr_conv_weight_bf16x1_bytes(k, cin, cout), device=w.device, dtype=torch.uint8)
+        with _DeviceOf(w):
+            N.check(lib().eavsr_pack_conv_weight_bf16x1_dgrad(_p(w), _p(packed), k, cout, cin, _stream(w)), "pack_conv_weight_bf16x1_dgrad")
+    else:
+        packed = torch.empty(lib().eavsr_conv_weight_bf16x1_bytes(k, cout, cin), device=w.device, dtype=torch.uint8)
+        with _DeviceOf(w):
+            N.check(lib().eavsr_pack_conv_weight_bf16x1(_p(w), _p(packed), k, cout, cin, _stream(w)), "pack_conv_weight_bf16x1")
+    ids = {id(x) for x in weights}
+    for k_ in [k_ for k_ in _bf16_pack_cache if (k_[-1] == ("dgrad", 0)) == dgrad and any(i in ids for i, _ in k_ if isinstance(i, int))]:
+        _bf16_pack_cache.pop(k_, None)
+    refs = tuple(weakref.ref(x, lambda _r, k_=key, c=_bf16_pack_cache: c.pop(k_, None)) for x in weights)
+    _bf16_pack_cache[key] = (refs, packed)
+    return packed
+
+
+def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None) -> int:
     """Both packed forms (forward and input-gradient) of every (64, 64, 3, 3) weight in `weights` that the cache does not hold at
     the weight's current version, in ceil(count / 48) launches (eavsr_pack_conv_weight_x6_multi) instead of one launch per weight and
     form at its first use: what the training step calls once, in front of its forward (540 launches of 4.7 us on its one dependent
-    chain otherwise).  Returns the number of forms packed."""
+    chain otherwise).  precision (default: TRAIN_PRECISION, the mode the training convolutions run in): "bf16" packs the one-plane
+    forms of the bf16 training mode instead (eavsr_pack_conv_weight_bf16x1_multi).  Returns the number of forms packed."""
+    bf16 = check_precision(TRAIN_PRECISION if precision is None else precision) == "bf16"
+    cache = _bf16_pack_cache if bf16 else _conv7_pack_cache
     todo = []
     for w in weights:
         if tuple(w.shape) != (64, 64, 3, 3) or not w.is_cuda or not w.is_contiguous() or w.dtype != torch.float32:
             continue
         for dg in (False, True):
             key = ((id(w), w._version),) + ((("dgrad", 0),) if dg else ())
-            hit = _conv7_pack_cache.get(key)
+            hit = cache.get(key)
             if hit is None or hit[0][0]() is not w:
                 todo.append((w, dg, key))
     if not todo:
         return 0
     dev = todo[0][0].device
-    nbytes = int(lib().eavsr_conv_weight_x6_bytes(3, 64, 64))
+    nbytes = int(lib().eavsr_conv_weight_bf16x1_bytes(3, 64, 64) if bf16 else lib().eavsr_conv_weight_x6_bytes(3, 64, 64))
     store = torch.empty((len(todo), nbytes), device=dev, dtype=torch.uint8)
     cnt = len(todo)
     srcs = (C.c_void_p * cnt)(*[w.detach().data_ptr() for w, _, _ in todo])
     dsts = (C.c_void_p * cnt)(*[store[i].data_ptr() for i in range(cnt)])
     trs = (C.c_int32 * cnt)(*[int(dg) for _, dg, _ in todo])
     with _DeviceOf(todo[0][0]):
-        N.check(lib().eavsr_pack_conv_weight_x6_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_x6_multi")
+        if bf16:
+            N.check(lib().eavsr_pack_conv_weight_bf16x1_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_bf16x1_multi")
+        else:
+            N.check(lib().eavsr_pack_conv_weight_x6_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_x6_multi")
     for i, (w, dg, key) in enumerate(todo):
-        for k_ in [k_ for k_ in _conv7_pack_cache if (k_[-1] == ("dgrad", 0)) == dg and any(i_ == id(w) for i_, _ in k_ if isinstance(i_, int))]:
-            _conv7_pack_cache.pop(k_, None)
-        refs = (weakref.ref(w, lambda _r, k_=key, c=_conv7_pack_cache: c.pop(k_, None)),)
-        _conv7_pack_cache[key] = (refs, store[i])
+        for k_ in [k_ for k_ in cache if (k_[-1] == ("dgrad", 0)) == dg and any(i_ == id(w) for i_, _ in k_ if isinstance(i_, int))]:
+            cache.pop(k_, None)
+        refs = (weakref.ref(w, lambda _r, k_=key, c=cache: c.pop(k_, None)),)
+        cache[key] = (refs, store[i])
     return cnt
 
 
@@ -609,11 +660,12 @@ class BorderPieces:
 
 
 def conv2d(srcs, weight, bias=None, act=None, slope: float = 0.0, residual=None, chan_partial: bool = False, ca=None, ca_out: bool = False,
-           pixel_shuffle2: bool = False, sigmoid_from=None, dgrad: bool = False, res_scale=None, border: bool = False, sum_mul=None):
+           pixel_shuffle2: bool = False, sigmoid_from=None, dgrad: bool = False, res_scale=None, border: bool = False, sum_mul=None,
+           precision: str = "fp32"):
     """see _conv2d (the implementation); this shim only normalises the `border` result: routes that do not produce border pieces
     return None in its place"""
     r = _conv2d(srcs, weight, bias, act, slope, residual, chan_partial, ca, ca_out, pixel_shuffle2, sigmoid_from, dgrad, res_scale, border,
-                sum_mul)
+                sum_mul, precision)
     if border and not (isinstance(r, tuple) and len(r) >= 2 and (r[-1] is None or isinstance(r[-1], BorderPieces))):
         r = (tuple(r) if isinstance(r, tuple) else (r,)) + (None,)
     return r
@@ -624,7 +676,7 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
            slope: float = 0.0, residual: Optional[Tensor] = None, chan_partial: bool = False,
            ca: Optional[Tuple[Tensor, Tensor]] = None, ca_out: bool = False, pixel_shuffle2: bool = False,
            sigmoid_from: Optional[int] = None, dgrad: bool = False, res_scale: Optional[Tensor] = None, border: bool = False,
-           sum_mul: Optional[Tensor] = None):
+           sum_mul: Optional[Tensor] = None, precision: str = "fp32"):
     """conv over the virtual channel-concatenation of `srcs`; `weight` may be a list of weights
     that are concatenated along cout (several heads in one launch).
     border=True (with chan_partial=True): a third result, the sums of the output's four border lines per border tile
@@ -643,8 +695,11 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
     sum_mul=m (n, cout, h, w), with dgrad: also returns (n, rows, cout) partial sums over the plane of out * m -- `sum_hw d r`, what the
     backward of the PREVIOUS RCAB's tail starts with -- from the epilogue of the small-launch bf16x6 kernel (desc.sum_mul), by a
     plane-sum launch behind every other kernel (rows = 1).
+    precision="bf16" (the bf16 training mode; autograd passes it): where the crop-sized kernel takes the launch (x6s_takes), it runs
+    with its operands rounded once to bf16 (eavsr_conv3x3_bf16x1s); every other route ignores it and stays as it is.
     Returns out, then the per-tile channel sums when chan_partial=True, then the effective input when
     ca_out=True."""
+    check_precision(precision)
     if sum_mul is not None:
         if not dgrad or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None or res_scale is not None or act == "relu_mask":
             raise ValueError("sum_mul: input-gradient convolutions only (dgrad=True; no channel sums / prologue / shuffle / sigmoid / mask)")
@@ -751,7 +806,7 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
                and n * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
     if sum_mul is not None and not (use_x6s and w % 4 == 0 and tuple(sum_mul.shape) == (n, cout, h, w) and
                                     all(t_ is None or t_.data_ptr() % 16 == 0 for t_ in (srcs[0], out, residual, sum_mul))):
-        y = conv2d(srcs, weights, None, act, slope, residual, dgrad=True)      # the kernel's epilogue form does not apply: a launch
+        y = conv2d(srcs, weights, None, act, slope, residual, dgrad=True, precision=precision)      # the kernel's epilogue form does not apply: a launch
         return y, plane_sum(y, sum_mul).view(n, 1, -1)
     if dgrad and not use_x6s:      # (e.g. a large launch that the Winograd kernel takes)
         weights, dgrad = [dgrad_weight(weights[0])], False
@@ -810,6 +865,12 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
         raise ValueError("ca_out needs ca")
     st = _stream(out)
     px = float(n) * h * w
+    if use_x6s and precision == "bf16":
+        wq = _packed_conv3_bf16(weights, dgrad=dgrad)
+        _launch(f"conv3x3_{cin}to{cout}_bf16s", 2.0 * cin * cout * 9 * px,
+                4.0 * px * (cin + cout + (cout if residual is not None else 0)), out,
+                lambda: lib().eavsr_conv3x3_bf16x1s(C.byref(d), _p(wq), st), "conv3x3_bf16x1s")
+        return out if not (chan_partial or sum_mul is not None) else (out, part)
     if use_x6s:
         wq = _packed_conv_x6(weights, dgrad=dgrad)
         _launch(f"conv3x3_{cin}to{cout}_x6s", 2.0 * cin * cout * 9 * px,
@@ -1693,9 +1754,15 @@ def affine_offsets_bwd(doff: Tensor, dmask: Optional[Tensor], mask: Optional[Ten
 
 
 def conv_wgrad(dy: Tensor, srcs: Sequence[Tensor], ksize: int, out: Optional[Tensor] = None,
-               accumulate: bool = False) -> Tensor:
+               accumulate: bool = False, precision: str = "fp32") -> Tensor:
     """Weight gradient (cout, cin_total, k, k) of a conv over the virtual concatenation of `srcs`; written to (or, with
-    `accumulate`, added to) `out` when given."""
+    `accumulate`, added to) `out` when given.  precision="bf16": see conv_wgrad_multi."""
+    if check_precision(precision) == "bf16" and wgrad_bf16_takes([dy], [srcs], ksize):
+        dy_ = _chk(dy, "dy")
+        cin_ = sum(int(s.shape[1]) for s in srcs)
+        if out is None:
+            out, accumulate = torch.empty((int(dy_.shape[1]), cin_, ksize, ksize), device=dy_.device, dtype=torch.float32), False
+        return conv_wgrad_multi([dy_], [srcs], ksize, out=out, accumulate=accumulate, precision="bf16")
     dy = _chk(dy, "dy")
     srcs = [_chk(s, f"src{i}") for i, s in enumerate(srcs)]
     n, cout, h, w = dy.shape
@@ -1748,14 +1815,25 @@ def _ptr_array(tensors):
     return (_C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def wgrad_bf16_takes(dys: Sequence[Tensor], srcs_list: Sequence[Sequence[Tensor]], ksize: int) -> bool:
+    """the bf16 training mode's weight gradient (eavsr_conv_wgrad_bias_multi_bf16) takes these uses: 3x3 at a size where the
+    crop-sized convolution kernel runs (x6s_takes), w % 4 == 0 and 16-byte aligned tensors; anything else stays on the exact kernels"""
+    n, _, h, w = dys[0].shape
+    return (ksize == 3 and w % 4 == 0 and x6s_takes(int(n), int(h), int(w))
+            and all(t.data_ptr() % 16 == 0 and t.is_contiguous() for t in list(dys) + [s_ for ss in srcs_list for s_ in ss]))
+
+
 def conv_wgrad_multi(dys: Sequence[Tensor], srcs_list: Sequence[Sequence[Tensor]], ksize: int, out: Tensor,
-                     accumulate: bool = False, bias_out: Optional[Tensor] = None) -> Tensor:
+                     accumulate: bool = False, bias_out: Optional[Tensor] = None, precision: str = "fp32") -> Tensor:
     """`conv_wgrad` over several USES of one weight in one launch per (source, 64-channel block): dys[s] / srcs_list[s] are
     the (dY, sources) pairs of use s, all of the same shapes (the frames of the recurrence: eavsrp_model.py:271-324).  The K
     dimension of the weight-gradient GEMM becomes pixels x uses -- a 2 x 96 x 96 training crop has 72 tiles per use for 256
     CUs -- and the per-use accumulation into `out` becomes one slab reduction.  At most WGRAD_MAX_SEGMENTS uses per call.
     bias_out (cout,): the bias gradient sum(dY) is written (or, accumulate=True, added) there as well -- by the bf16x6 3x3 kernel
-    itself, which stages dY anyway, by a channel-sum launch otherwise (eavsr_conv_wgrad_bias_multi_f32)."""
+    itself, which stages dY anyway, by a channel-sum launch otherwise (eavsr_conv_wgrad_bias_multi_f32).
+    precision="bf16" (the bf16 training mode): where wgrad_bf16_takes holds, dY and X are rounded once to bf16
+    (eavsr_conv_wgrad_bias_multi_bf16: the same slabs and fixed-order reduction); elsewhere the exact kernels as before."""
+    bf16 = check_precision(precision) == "bf16" and wgrad_bf16_takes(dys, srcs_list, ksize)
     nseg = len(dys)
     if not 1 <= nseg <= WGRAD_MAX_SEGMENTS or len(srcs_list) != nseg:
         raise ValueError(f"conv_wgrad_multi: 1..{WGRAD_MAX_SEGMENTS} segments")
@@ -1790,9 +1868,10 @@ def conv_wgrad_multi(dys: Sequence[Tensor], srcs_list: Sequence[Sequence[Tensor]
                 db = bias_out if (si == 0 and ci0 == 0) else None      # once per 64-channel block of outputs
                 _launch(f"conv_wgrad{ksize}x{ksize}", 2.0 * min(64, cout - co0) * min(64, cs - ci0) * ksize * ksize * n * nseg * h * w,
                         4.0 * n * nseg * h * w * 128, dw,
-                        lambda xl=xl, cs=cs, ci0=ci0, co0=co0, base=base, db=db: lib().eavsr_conv_wgrad_bias_multi_f32(
+                        lambda xl=xl, cs=cs, ci0=ci0, co0=co0, base=base, db=db: (
+                            lib().eavsr_conv_wgrad_bias_multi_bf16 if bf16 else lib().eavsr_conv_wgrad_bias_multi_f32)(
                             dyl, xl, nseg, _p(dw), _p(db), _p(ws), n, h, w, cout, co0, cs, ci0, cin, base + ci0, ksize, acc, st),
-                        "conv_wgrad")
+                        "conv_wgrad_bf16" if bf16 else "conv_wgrad")
         base += cs
     return dw
 

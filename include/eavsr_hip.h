@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define EAVSR_ABI_VERSION 31
+#define EAVSR_ABI_VERSION 32
 
 /* activation codes for eavsr_conv2d_f32 */
 #define EAVSR_ACT_NONE 0
@@ -652,6 +652,31 @@ int eavsr_pwc_correlation_f32(const float* a, int64_t a_batch_stride, const floa
 int eavsr_pwc_backwarp_f32(const float* x, int64_t x_batch_stride, const float* flow, int64_t flow_batch_stride, float* out,
                            int64_t out_batch_stride, float* mask, int32_t n, int32_t c, int32_t h, int32_t w, int32_t flow_h,
                            int32_t flow_w, float flow_mul, void* stream);
+
+/* ---- The opt-in bf16 training mode (ABI 32; networks.set_train_precision("bf16")) -------------------------------------------
+ * The forward, input-gradient and weight-gradient convolutions of RCABlock's 3x3 64 -> 64 convolutions (models/networks.py:456-464)
+ * at a training crop, as loss.backward() runs them (models/eavsrp_model.py:109-119), with every operand ROUNDED ONCE to bf16,
+ * nearest even (what torch.Tensor.to(torch.bfloat16) computes), one bf16 product per k-step and fp32 accumulation -- in the
+ * spirit of torch.set_float32_matmul_precision("medium").  Bias, activation and residual stay fp32 in the epilogue.  Not exact:
+ * the kernels above (eavsr_conv3x3_f32x6s, eavsr_conv_wgrad_bias_multi_f32) remain the default.
+ * Packed weight of eavsr_conv3x3_bf16x1s: one plane instead of three, eavsr_conv_weight_bf16x1_bytes(3, cout, cin) bytes (0 for
+ * any other ksize); _dgrad: the input-gradient form of the forward weight (cout_w, cin_w, 3, 3), as eavsr_pack_conv_weight_x6_dgrad;
+ * _multi: `count` (c, c, 3, 3) weights in ceil(count / 48) launches, as eavsr_pack_conv_weight_x6_multi. */
+size_t eavsr_conv_weight_bf16x1_bytes(int32_t ksize, int32_t cout, int32_t cin);
+int eavsr_pack_conv_weight_bf16x1(const float* weight, void* packed, int32_t ksize, int32_t cout, int32_t cin, void* stream);
+int eavsr_pack_conv_weight_bf16x1_dgrad(const float* weight, void* packed, int32_t ksize, int32_t cout_w, int32_t cin_w, void* stream);
+int eavsr_pack_conv_weight_bf16x1_multi(const float* const* weights, void* const* packed, const int32_t* transposed, int32_t count,
+                                        int32_t ksize, int32_t c, void* stream);
+/* eavsr_conv3x3_f32x6s with the rounded operands (nn.Conv2d forward of RCABlock, models/networks.py:456-458, and its input
+ * gradient in loss.backward()): the same descriptor fields, cases, tiles and per-tile sums (eavsr_conv3x3_x6s_tiles(h, w) rows). */
+int eavsr_conv3x3_bf16x1s(const eavsr_conv2d_desc* desc, const void* weight_bf16x1, void* stream);
+/* eavsr_conv_wgrad_bias_multi_f32 with dY and X rounded once (the weight gradients of RCABlock's convolutions in loss.backward(),
+ * models/eavsrp_model.py:109-113): the same arguments, workspace, slabs and fixed-order reduction (deterministic, no atomics).
+ * ksize 3, w % 4 == 0 and 16-byte aligned segments only (else -2); n == 0 writes zeros (or leaves an accumulated result). */
+int eavsr_conv_wgrad_bias_multi_bf16(const void* const* dy_list, const void* const* x_list, int32_t nseg, float* dweight,
+                                     float* dbias, float* workspace, int32_t n, int32_t h, int32_t w, int32_t cout_total,
+                                     int32_t co0, int32_t cin_src, int32_t ci0, int32_t cin_total, int32_t ci_dst0, int32_t ksize,
+                                     int32_t accumulate, void* stream);
 
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
