@@ -180,6 +180,12 @@ SIGNATURES = {
     "eavsr_pack_conv_weight_bf16x1_multi": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "eavsr_conv3x3_bf16x1s": (C.c_int, [vp, vp, vp]),
     "eavsr_conv_wgrad_bias_multi_bf16": (C.c_int, [vp, vp, i32, vp, vp, vp] + [i32] * 11 + [vp]),
+    # the opt-in deterministic training mode (csrc/det_scatter.hip; additions to ABI 32)
+    "eavsr_resize_bilinear_ac_bwd_det_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "eavsr_flow_warp_bwd_dx_det_workspace_floats": (C.c_int64, [i32, i32, i32]),
+    "eavsr_flow_warp_bwd_dx_det_f32": (C.c_int, [vp] * 5 + [i32] * 4 + [vp]),
+    "eavsr_dcnv2_col2im_dx_det_workspace_floats": (C.c_int64, [i32, i32, i32]),
+    "eavsr_dcnv2_col2im_dx_det_f32": (C.c_int, [vp] * 5 + [i32] * 5 + [vp]),
 }
 
 # Entry points of the LAB build only (`python -m eavsr_amd.build --lab`; the header's EXPERIMENTAL section): bound when the

@@ -50,6 +50,8 @@ class grad_sink:
 
     def __init__(self):
         self.entries = {}
+        # deterministic mode (networks.set_deterministic): how uses are grouped into launches must depend on this backward only
+        self.det = ops.deterministic_active()
 
     def __enter__(self):
         if grad_sink._active is not None:
@@ -99,8 +101,13 @@ class grad_sink:
         e["prec"] = precision
         e["pending"].append((g, list(srcs)))
         e["uses"] += 1
-        if len(e["pending"]) >= self.BATCH or e["uses"] == grad_sink._last_uses.get(key, -1):
-            self._launch(e)       # a full batch, or the last use this call site had in the previous backward
+        # a full batch, or the last use this call site had in the previous backward.  Not in the deterministic mode: that count
+        # is history (a backward of another shape or phase, or of another model whose freed weights had the same id()), and a launch
+        # it triggers early splits the uses into other groups -- another rounding of the same sum.  There every group is BATCH
+        # uses in backward order and the rest waits for flush(): a pure function of this backward (at the cost of holding the
+        # last group's dY and sources until backward ends).
+        if len(e["pending"]) >= self.BATCH or (not self.det and e["uses"] == grad_sink._last_uses.get(key, -1)):
+            self._launch(e)
 
     @staticmethod
     def _launch(e):
@@ -267,6 +274,7 @@ class _FlowWarpFn(Function):
     @staticmethod
     def forward(ctx, x, flow, flow2):
         ctx.save_for_backward(x, flow, *( [flow2] if flow2 is not None else []))
+        ctx.det = ops.deterministic_active()      # networks.set_deterministic: dx without atomics
         return ops.flow_warp(x, flow, "zeros", flow2=flow2)
 
     @staticmethod
@@ -276,7 +284,12 @@ class _FlowWarpFn(Function):
         flow2 = saved[2] if len(saved) > 2 else None
         need_dx = ctx.needs_input_grad[0]
         need_df = ctx.needs_input_grad[1] or (flow2 is not None and ctx.needs_input_grad[2])
-        dx, dflow = ops.flow_warp_bwd(x, flow, flow2, dout.contiguous(), need_dx, need_df)
+        if ctx.det:      # dflow is fixed-order already; dx through the inverted index (csrc/det_scatter.hip)
+            dout = dout.contiguous()
+            dflow = ops.flow_warp_bwd(x, flow, flow2, dout, False, True)[1] if need_df else None
+            dx = ops.flow_warp_bwd_dx_det(flow, flow2, dout) if need_dx else None
+        else:
+            dx, dflow = ops.flow_warp_bwd(x, flow, flow2, dout.contiguous(), need_dx, need_df)
         return dx, (dflow if ctx.needs_input_grad[1] else None), (dflow if flow2 is not None and ctx.needs_input_grad[2] else None)
 
 
@@ -318,6 +331,7 @@ class _DcnFn(Function):
         ctx.dg = dg
         ctx.has_bias = bias is not None
         ctx.params = [weight] + ([bias] if bias is not None else [])      # the caller's tensor objects (grad_sink keys on them)
+        ctx.det = ops.deterministic_active()
         ctx.save_for_backward(x, offset, mask, weight)
         return ops.modulated_deform_conv2d(x, offset, mask, weight, bias, 1, 1, 1, 1, dg)
 
@@ -328,6 +342,28 @@ class _DcnFn(Function):
         dout = dout.contiguous()
         cout, cin = weight.shape[0], weight.shape[1]
         need_w, need_b = ctx.needs_input_grad[3], ctx.has_bias and ctx.needs_input_grad[4]
+        if ctx.det and not ops.dcnv2_bwd_supported(x, weight, dg):
+            raise RuntimeError(
+                f"deterministic training mode: no atomic-free DCNv2 backward for this configuration ({int(x.shape[1])} -> "
+                f"{int(weight.shape[0])} channels, {dg} deformable groups, EAVSR_DCN_BWD={ops.DCN_BWD}); it needs 64 -> 64 "
+                "channels, 8 groups and the sampler backward (EAVSR_DCN_BWD=sampler).  The column backward's col2im adds with "
+                "float atomics")
+        if ctx.det:
+            # deterministic mode: doffset / dmask / dW from the sampler backward without its dx (whose out-of-window corners use
+            # float atomics); dx = the gather-form col2im of dcol = W^T . dOut (csrc/det_scatter.hip)
+            need_dx = ctx.needs_input_grad[0]
+            if need_w and (need_b or not ctx.has_bias) and grad_sink.eligible(ctx.params):
+                bufs, acc = grad_sink._active.raw(ctx.params)
+                _, doff, dmask, _ = ops.dcnv2_bwd(x, offset, mask, weight, dout, dg, need_dx=False, dweight=bufs[0], accumulate=acc)
+                if ctx.has_bias:
+                    ops.channel_sum(dout, out=bufs[1], accumulate=acc)
+                dW = db = None
+            else:
+                _, doff, dmask, dW = ops.dcnv2_bwd(x, offset, mask, weight, dout, dg, need_dx=False)
+                dW = dW if need_w else None
+                db = ops.channel_sum(dout) if need_b else None
+            dx = ops.dcnv2_col2im_dx_det(offset, mask, ops.conv2d(dout, _dcn_wt(weight), None), dg) if need_dx else None
+            return dx, doff, dmask, dW, db, None
         if ops.dcnv2_bwd_supported(x, weight, dg):
             # round 6: the whole backward on the sampler's side (csrc/dcn_bwd.hip): no column tensor, no GEMM launches, no col2im
             if need_w and (need_b or not ctx.has_bias) and grad_sink.eligible(ctx.params):
@@ -426,13 +462,15 @@ class _ResizeFn(Function):
     @staticmethod
     def forward(ctx, x, pre_add, post_add, size, scale):
         ctx.meta = (tuple(x.shape), scale)
+        ctx.det = ops.deterministic_active()
         return ops.resize_bilinear_ac(x, size, scale, pre_add=pre_add, post_add=post_add)
 
     @staticmethod
     def backward(ctx, dout):
         shape, scale = ctx.meta
         dout = dout.contiguous()
-        din = ops.resize_bilinear_ac_bwd(dout, shape, scale) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None
+        bwd = ops.resize_bilinear_ac_bwd_det if ctx.det else ops.resize_bilinear_ac_bwd
+        din = bwd(dout, shape, scale) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None
         return (din if ctx.needs_input_grad[0] else None, din if ctx.needs_input_grad[1] else None,
                 dout if ctx.needs_input_grad[2] else None, None, None)
 

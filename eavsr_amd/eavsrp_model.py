@@ -405,6 +405,9 @@ class EAVSRPModel:
         # opt.train_precision (not among the reference's options): the opt-in bf16 training mode (networks.set_train_precision)
         if getattr(opt, "train_precision", None) is not None:
             N.set_train_precision(opt.train_precision)
+        # opt.deterministic (not among the reference's options): the opt-in deterministic training mode (networks.set_deterministic)
+        if getattr(opt, "deterministic", None) is not None:
+            N.set_deterministic(opt.deterministic)
         gpu_ids = list(getattr(opt, "gpu_ids", [0]))
         if len(gpu_ids) == 0:
             raise RuntimeError("eavsr_amd has no CPU path (--gpu_ids -1 is the reference's CPU mode)")

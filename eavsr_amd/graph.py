@@ -146,6 +146,7 @@ class GraphedTrainStep:
 
     masked = False       # the captured forward holds the PWC-Net mask of epochs >= opt.npost (set by _capture)
     precision = None     # ... and the training precision it was captured in (networks.set_train_precision; set by _capture)
+    deterministic = None  # ... and whether in the deterministic mode (networks.set_deterministic; set by _capture)
 
     def __init__(self, model, warmup: int = 2):
         import torch.distributed as dist
@@ -181,6 +182,7 @@ class GraphedTrainStep:
         # ... and the training precision (networks.set_train_precision): the kernels it selects are baked into the graph
         from . import ops
         self.precision = ops.TRAIN_PRECISION
+        self.deterministic = ops.deterministic_active()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -266,8 +268,10 @@ class GraphedTrainStep:
         m.data_lr_seq, m.data_hr_seq = self.static_lr, self.static_hr
         from . import ops
         phase = getattr(m, "masked_phase", None)
-        # crossing npost, or another training precision (networks.set_train_precision): recapture once
-        if (phase is not None and phase() != self.masked) or (self.precision is not None and ops.TRAIN_PRECISION != self.precision):
+        # crossing npost, another training precision (networks.set_train_precision) or a change of the deterministic mode
+        # (networks.set_deterministic): recapture once
+        if ((phase is not None and phase() != self.masked) or (self.precision is not None and ops.TRAIN_PRECISION != self.precision)
+                or (self.deterministic is not None and ops.deterministic_active() != self.deterministic)):
             self.graph = None
             self._capture(1, optimizer_steps=False)
         for p, g in self._grads:

@@ -505,6 +505,38 @@ def train_precision(mode: str):
         ops.TRAIN_PRECISION = prev
 
 
+def set_deterministic(flag: bool) -> None:
+    """The opt-in DETERMINISTIC training mode, in the spirit of torch.use_deterministic_algorithms(True): when on, a training step is a
+    pure function of (parameters, optimizer state, inputs, modes, shapes) on one GPU with one build -- loss, gradients and updated
+    parameters are bitwise identical from run to run, eager or graphed.  The backward of flow_warp, of resize_bilinear_ac and of
+    DCNv2 then compute their input gradients without float atomics (csrc/det_scatter.hip; every other backward reduction is
+    fixed-order in both modes), and autograd.grad_sink groups a weight's uses into weight-gradient launches without looking at
+    earlier backwards.  A DCNv2 backward without an atomic-free form (not 64 -> 64 channels in 8 groups, or
+    EAVSR_DCN_BWD=columns) raises RuntimeError.  Off by default (EAVSR_DETERMINISTIC=0|1); also on whenever torch.are_deterministic_algorithms_enabled().
+    Composes with set_train_precision("bf16").  Read at each recorded forward; a GraphedTrainStep recaptures when it changes.
+    flag must be a bool (ValueError otherwise)."""
+    if not isinstance(flag, bool):
+        raise ValueError(f"set_deterministic: expected True or False, got {flag!r}")
+    ops.DETERMINISTIC = flag
+
+
+def get_deterministic() -> bool:
+    """whether training runs in the deterministic mode: set_deterministic(True) / EAVSR_DETERMINISTIC=1, or torch's own switch"""
+    return ops.deterministic_active()
+
+
+@_contextlib.contextmanager
+def deterministic(flag: bool = True):
+    """`with networks.deterministic(): model.optimize_parameters()` -- the previous setting is restored on exit, also when the body
+    raises."""
+    prev = ops.DETERMINISTIC
+    set_deterministic(flag)
+    try:
+        yield
+    finally:
+        ops.DETERMINISTIC = prev
+
+
 class RCAGroup(nn.Module):
     def __init__(self, in_channels=64, out_channels=64, kernel_size=3, stride=1, padding=1, bias=True,
                  mode="CRC", reduction=16, nb=12):

@@ -400,6 +400,20 @@ def check_precision(precision: str) -> str:
     return precision
 
 
+# The opt-in deterministic training mode (networks.set_deterministic / EAVSR_DETERMINISTIC=0|1): the backward of flow_warp, of
+# resize_bilinear_ac and of DCNv2 compute their input gradients without float atomics (csrc/det_scatter.hip), so that a training step
+# is bitwise reproducible.  Also on whenever torch.are_deterministic_algorithms_enabled().  autograd reads deterministic_active() at
+# each recorded forward; ops itself only follows what it is asked to launch.
+_det_env = os.environ.get("EAVSR_DETERMINISTIC", "0")
+if _det_env not in ("0", "1"):
+    raise ValueError(f"EAVSR_DETERMINISTIC={_det_env!r}: 0 or 1")
+DETERMINISTIC = _det_env == "1"
+
+
+def deterministic_active() -> bool:
+    return DETERMINISTIC or torch.are_deterministic_algorithms_enabled()
+
+
 # bf16 training mode: the one-plane packed forms (eavsr_pack_conv_weight_bf16x1*), a cache of their own -- never confused with the
 # exact forms of _conv7_pack_cache, whatever the mode was when either was packed
 _bf16_pack_cache = register_weight_cache({})
@@ -1725,6 +1739,50 @@ def resize_bilinear_ac_bwd(dout: Tensor, in_shape, scale: float) -> Tensor:
             lambda: lib().eavsr_resize_bilinear_ac_bwd_f32(_p(dout), _p(din), n, c, hin, win, hout, wout, float(scale), st),
             "resize_bilinear_ac_bwd")
     return din
+
+
+def resize_bilinear_ac_bwd_det(dout: Tensor, in_shape, scale: float) -> Tensor:
+    """resize_bilinear_ac_bwd without atomics (deterministic mode): every input pixel gathers its output pixels in a fixed order"""
+    dout = _chk(dout, "dout")
+    n, c, hin, win = in_shape
+    hout, wout = dout.shape[2:]
+    din = torch.empty((n, c, hin, win), device=dout.device, dtype=torch.float32)
+    st = _stream(dout)
+    _launch("resize_bilinear_ac_bwd_det", 0.0, 4.0 * (dout.numel() + din.numel()), dout,
+            lambda: lib().eavsr_resize_bilinear_ac_bwd_det_f32(_p(dout), _p(din), n, c, hin, win, hout, wout, float(scale), st),
+            "resize_bilinear_ac_bwd_det")
+    return din
+
+
+def flow_warp_bwd_dx_det(flow: Tensor, flow2: Optional[Tensor], dout: Tensor) -> Tensor:
+    """dx of flow_warp_bwd without atomics (deterministic mode): an inverted index per sample, one fixed-order sum per cell and channel"""
+    flow, dout = _chk(flow, "flow"), _chk(dout, "dout")
+    if flow2 is not None:
+        flow2 = _chk(flow2, "flow2")
+    n, c, h, w = dout.shape
+    dx = torch.empty_like(dout)
+    ws = torch.empty(int(lib().eavsr_flow_warp_bwd_dx_det_workspace_floats(n, h, w)), device=dout.device, dtype=torch.int32)
+    st = _stream(dout)
+    _launch("flow_warp_bwd_dx_det", 8.0 * dout.numel(), 4.0 * dout.numel() * 3, dout,
+            lambda: lib().eavsr_flow_warp_bwd_dx_det_f32(_p(flow), _p(flow2), _p(dout), _p(dx), _p(ws), n, c, h, w, st),
+            "flow_warp_bwd_dx_det")
+    return dx
+
+
+def dcnv2_col2im_dx_det(offset: Tensor, mask: Tensor, dcol: Tensor, dg: int) -> Tensor:
+    """DCNv2's dx from the column gradient dcol = W^T . dY (n, 576, h, w) without atomics (deterministic mode): a gather-form col2im
+    through an inverted index per (sample, deformable group); 64 channels, 8 groups"""
+    offset, mask, dcol = _chk(offset, "offset"), _chk(mask, "mask"), _chk(dcol, "dcol")
+    n, c9, h, w = dcol.shape
+    if c9 != 576 or dg != 8 or tuple(offset.shape) != (n, 144, h, w) or tuple(mask.shape) != (n, 72, h, w):
+        raise NotImplementedError("dcnv2_col2im_dx_det: 64 channels, 8 deformable groups, 3x3")
+    dx = torch.empty((n, 64, h, w), device=dcol.device, dtype=torch.float32)
+    ws = torch.empty(int(lib().eavsr_dcnv2_col2im_dx_det_workspace_floats(n, h, w)), device=dcol.device, dtype=torch.int32)
+    st = _stream(dcol)
+    _launch("dcnv2_col2im_dx_det", 2.0 * dcol.numel() * 4, 4.0 * (dcol.numel() + dx.numel()), dcol,
+            lambda: lib().eavsr_dcnv2_col2im_dx_det_f32(_p(offset), _p(mask), _p(dcol), _p(dx), _p(ws), n, 64, h, w, dg, st),
+            "dcnv2_col2im_dx_det")
+    return dx
 
 
 def pyramid_bwd(dd2: Tensor, dd4: Tensor) -> Tensor:

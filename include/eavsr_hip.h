@@ -678,6 +678,28 @@ int eavsr_conv_wgrad_bias_multi_bf16(const void* const* dy_list, const void* con
                                      int32_t co0, int32_t cin_src, int32_t ci0, int32_t cin_total, int32_t ci_dst0, int32_t ksize,
                                      int32_t accumulate, void* stream);
 
+/* ---- The opt-in deterministic training mode (networks.set_deterministic; added to ABI 32, nothing above changes) -----------------
+ * Atomic-free input gradients of the three scatter-shaped backward ops of loss.backward() (models/eavsrp_model.py:109-119): every
+ * output element is summed in an order that depends only on the inputs, so they are bitwise reproducible from run to run (the atomic
+ * entry points above stay the default).  They WRITE their output (no pre-zeroing).
+ * resize: a gather; every input pixel adds its output pixels' terms (the same corners and products as
+ * eavsr_resize_bilinear_ac_bwd_f32) in increasing (oy, ox) order. */
+int eavsr_resize_bilinear_ac_bwd_det_f32(const float* dout, float* din, int32_t n, int32_t c, int32_t hin, int32_t win,
+                                         int32_t hout, int32_t wout, float scale, void* stream);
+/* flow_warp dx (dflow: eavsr_flow_warp_bwd_f32 with dx = NULL, already fixed-order): per sample an inverted index -- for every dx cell
+ * the (source pixel, corner) pairs that sample it, in ascending order, positions computed as the atomic kernel computes them -- then
+ * one sum per (cell, channel) over its list.  workspace: eavsr_flow_warp_bwd_dx_det_workspace_floats 4-byte words. */
+int64_t eavsr_flow_warp_bwd_dx_det_workspace_floats(int32_t n, int32_t h, int32_t w);
+int eavsr_flow_warp_bwd_dx_det_f32(const float* flow, const float* flow2, const float* dout, float* dx, void* workspace, int32_t n,
+                                   int32_t c, int32_t h, int32_t w, void* stream);
+/* DCNv2 dx as a gather-form col2im (doffset / dmask / dweight: eavsr_dcnv2_bwd_f32 with dx_il8 = NULL): dcolumns = W^T . dY
+ * (n, 576, h, w), row (channel * 9 + tap); one inverted index per (sample, deformable group) over 9 taps x pixels with the sampling
+ * rule of eavsr_dcnv2_bwd_f32; dx (n, 64, h, w) NCHW.  64 channels, 8 deformable groups (-2 otherwise).  workspace:
+ * eavsr_dcnv2_col2im_dx_det_workspace_floats 4-byte words. */
+int64_t eavsr_dcnv2_col2im_dx_det_workspace_floats(int32_t n, int32_t h, int32_t w);
+int eavsr_dcnv2_col2im_dx_det_f32(const float* offset, const float* mask, const float* dcolumns, float* dx, void* workspace, int32_t n,
+                                  int32_t c, int32_t h, int32_t w, int32_t deform_groups, void* stream);
+
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
  * Schedules that were built, measured against the stable ones above and retired; kept because DESIGN.md / docs/history quote
