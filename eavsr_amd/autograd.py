@@ -12,12 +12,12 @@ from __future__ import annotations
 from typing import List, Optional, Sequence, Tuple, Union
 
 import os
-import weakref
 
 import torch
 from torch.autograd import Function
 
 from . import ops
+from .weight_cache import WeightCache
 
 Tensor = torch.Tensor
 
@@ -157,22 +157,16 @@ class grad_sink:
 # c0 .. c0+cs.  A weight is used once per frame and branch, so within a step the same operand is asked for 7-28
 # times: it is built once per weight version (and, being the same tensor object, its packed form is then also a
 # hit in ops.pack_cache).
-_dgrad_cache = ops.register_weight_cache({})
+_dgrad_cache = WeightCache()
 
 
 def _dgrad_weight(ws, c0: int, cs: int) -> Tensor:
-    key = tuple((id(w), w._version) for w in ws) + (c0, cs)
-    hit = _dgrad_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], ws)):
-        return hit[1]
+    hit = _dgrad_cache.lookup(ws, (c0, cs))
+    if hit is not None:
+        return hit
     W = ws[0] if len(ws) == 1 else torch.cat(ws, 0)
     wt = W.detach()[:, c0:c0 + cs].flip(2, 3).transpose(0, 1).contiguous()   # (cs, cout, k, k)
-    ids = {id(w) for w in ws}
-    for k_ in [k_ for k_ in _dgrad_cache if k_[-2:] == (c0, cs) and any(i in ids for i, _ in k_[:-2])]:
-        _dgrad_cache.pop(k_, None)
-    refs = tuple(weakref.ref(w, lambda _r, k_=key, c=_dgrad_cache: c.pop(k_, None)) for w in ws)
-    _dgrad_cache[key] = (refs, wt)
-    return wt
+    return _dgrad_cache.store(ws, (c0, cs), wt)
 
 
 def _train_precision(ws, srcs) -> str:
@@ -308,21 +302,16 @@ def flow_warp(x, flow, padding_mode="zeros", flow2=None, flow_layout="nchw", int
 
 
 # ------------------------------------------------------------------------------------------ DCNv2
-_dcn_wt_cache = ops.register_weight_cache({})
+_dcn_wt_cache = WeightCache()
 
 
 def _dcn_wt(weight: Tensor) -> Tensor:
     """(cin * 9, cout, 1, 1): the DCNv2 weight as the 1x1 convolution that maps dOut to the column gradients; once per weight version"""
-    key = (id(weight), weight._version)
-    hit = _dcn_wt_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        return hit[1]
+    hit = _dcn_wt_cache.lookup((weight,))
+    if hit is not None:
+        return hit
     cout, cin = int(weight.shape[0]), int(weight.shape[1])
-    wt = weight.detach().reshape(cout, cin * 9).t().contiguous().view(cin * 9, cout, 1, 1)
-    for k_ in [k_ for k_ in _dcn_wt_cache if k_[0] == id(weight)]:
-        _dcn_wt_cache.pop(k_, None)
-    _dcn_wt_cache[key] = (weakref.ref(weight, lambda _r, k_=key, c=_dcn_wt_cache: c.pop(k_, None)), wt)
-    return wt
+    return _dcn_wt_cache.store((weight,), None, weight.detach().reshape(cout, cin * 9).t().contiguous().view(cin * 9, cout, 1, 1))
 
 
 class _DcnFn(Function):

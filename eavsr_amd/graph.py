@@ -49,8 +49,8 @@ class GraphedForward:
             self.static_out = self.module(self.static_in)
         # the captured launches read the derived weight forms (packed / Winograd-transformed) that the warm-up left in the
         # per-parameter caches: hold them, so that clearing or refreshing a cache cannot free memory the graph still uses
-        from . import ops
-        self._weights_alive = [dict(getattr(d, "_d", d)) for d in ops.WEIGHT_CACHES]
+        from .weight_cache import WEIGHT_CACHES
+        self._weights_alive = [c.snapshot() for c in WEIGHT_CACHES]
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if x.shape != self.static_in.shape or x.dtype != self.static_in.dtype or x.device != self.static_in.device:
@@ -126,9 +126,9 @@ def clear_weight_caches():
     A replayed graph updates the parameters on the device without touching their Python-side version counters, so
     a cache filled inside (or before) a capture must not serve eager calls afterwards - and a capture must not hit an
     entry built outside it, or the replays would keep reading that stale copy."""
-    from . import autograd, ops      # (importing autograd registers its caches)
-    for d in ops.WEIGHT_CACHES:      # every derived-weight cache registers itself there (ops.register_weight_cache)
-        d.clear()
+    from . import autograd, ops, weight_cache      # (autograd, ops: so that their caches exist)
+    for c in weight_cache.WEIGHT_CACHES:
+        c.clear()
 
 
 class GraphedTrainStep:

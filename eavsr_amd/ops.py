@@ -10,12 +10,12 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-import weakref
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _native as N
+from .weight_cache import WEIGHT_CACHES, WeightCache      # (WEIGHT_CACHES: the registry, also read as ops.WEIGHT_CACHES)
 
 Tensor = torch.Tensor
 
@@ -226,58 +226,29 @@ def flow_warp_pair(xa: Tensor, xb: Tensor, flow: Tensor, flow2: Optional[Tensor]
 # ------------------------------------------------------------------------------------------
 # packed conv weights (cached per parameter version)
 # ------------------------------------------------------------------------------------------
-class _PackCache:
-    """Packed weights, cached per weight *object* and version.  Entries hold weak references to the
-    source tensors and are verified by identity, so a freed tensor whose id / address is reused
-    can never produce a stale hit; nn.Parameters live as long as their module, so the hot path
-    always hits."""
-
-    def __init__(self):
-        self._d = {}
-
-    def get(self, weights: Sequence[Tensor]) -> Tensor:
-        key = tuple((id(w), w._version) for w in weights)
-        hit = self._d.get(key)
-        if hit is not None:
-            refs, packed = hit
-            if all(r() is w for r, w in zip(refs, weights)):
-                return packed
-        w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
-        w = _chk(w.detach(), "weight")
-        cout, cin, kh, kw = w.shape
-        if kh != kw:
-            raise NotImplementedError("square kernels only")
-        elems = lib().eavsr_packed_weight_elems(cout, cin, kh)
-        if elems <= 0:
-            raise NotImplementedError(f"conv weight shape {tuple(w.shape)} unsupported")
-        packed = torch.empty(elems, device=w.device, dtype=torch.float32)
-        with _DeviceOf(w):
-            N.check(lib().eavsr_pack_conv_weight_f32(_p(w), _p(packed), cout, cin, kh, _stream(w)), "pack_conv_weight")
-        d = self._d
-        # drop stale versions of the same objects and dead entries
-        ids = {id(x) for x in weights}
-        for k in [k for k in d if any(i in ids for i, _ in k)]:
-            d.pop(k, None)
-        refs = tuple(weakref.ref(x, lambda _r, k=key, d=d: d.pop(k, None)) for x in weights)
-        d[key] = (refs, packed)
-        return packed
-
-    def clear(self):
-        self._d.clear()
+pack_cache = WeightCache()
 
 
-pack_cache = _PackCache()
+def _packed_f32(weights: Sequence[Tensor]) -> Tensor:
+    """the packed form of a conv weight (or of several stacked along cout) for eavsr_conv2d_f32; cached per weight objects and versions"""
+    hit = pack_cache.lookup(weights)
+    if hit is not None:
+        return hit
+    w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
+    w = _chk(w.detach(), "weight")
+    cout, cin, kh, kw = w.shape
+    if kh != kw:
+        raise NotImplementedError("square kernels only")
+    elems = lib().eavsr_packed_weight_elems(cout, cin, kh)
+    if elems <= 0:
+        raise NotImplementedError(f"conv weight shape {tuple(w.shape)} unsupported")
+    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
+    with _DeviceOf(w):
+        N.check(lib().eavsr_pack_conv_weight_f32(_p(w), _p(packed), cout, cin, kh, _stream(w)), "pack_conv_weight")
+    return pack_cache.store(weights, None, packed)
 
-# Every cache of a form DERIVED from a parameter (packed / transformed / split / transposed weights, concatenated biases), keyed
-# by (id, _version): graph.clear_weight_caches() empties all of them around a capture (a replayed graph updates the parameters
-# without bumping `_version`).  A new cache registers itself here -- ADVICE r5: two caches added in round 5 were missing from
-# the hand-kept list there.
-WEIGHT_CACHES = [pack_cache]
 
-
-def register_weight_cache(d):
-    WEIGHT_CACHES.append(d)
-    return d
+pack_cache.get = _packed_f32      # tools/ call it by this name: ops.pack_cache.get(weights)
 
 
 def _cat_bias(biases: Sequence[Optional[Tensor]]) -> Optional[Tensor]:
@@ -286,40 +257,29 @@ def _cat_bias(biases: Sequence[Optional[Tensor]]) -> Optional[Tensor]:
     return biases[0] if len(biases) == 1 else torch.cat([b.detach() for b in biases], 0)
 
 
-_bias_cache = register_weight_cache({})
+_bias_cache = WeightCache()
 
 
 def _bias_of(biases: Sequence[Optional[Tensor]]) -> Optional[Tensor]:
     if len(biases) == 1:
         return None if biases[0] is None else _chk(biases[0].detach(), "bias")
-    key = tuple((id(b), b._version) for b in biases)
-    hit = _bias_cache.get(key)
-    if hit is not None and all(r() is b for r, b in zip(hit[0], biases)):
-        return hit[1]
-    cat = _chk(_cat_bias(biases), "bias")
-    refs = tuple(weakref.ref(b, lambda _r, k=key, c=_bias_cache: c.pop(k, None)) for b in biases)
-    _bias_cache[key] = (refs, cat)
-    return cat
+    hit = _bias_cache.lookup(biases)
+    if hit is not None:
+        return hit
+    return _bias_cache.store(biases, None, _chk(_cat_bias(biases), "bias"))
 
 
-_wcat_cache = register_weight_cache({})
+_wcat_cache = WeightCache()
 
 
 def _cat_weights(weights: Sequence[Tensor]) -> Tensor:
     """cat(weights, 0) in the original layout, cached per (object, version) like the packed weights"""
     if len(weights) == 1:
         return _chk(weights[0].detach(), "weight")
-    key = tuple((id(w), w._version) for w in weights)
-    hit = _wcat_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
-    cat = _chk(torch.cat([w.detach() for w in weights], 0), "weight")
-    ids = {id(w) for w in weights}
-    for k_ in [k_ for k_ in _wcat_cache if any(i in ids for i, _ in k_)]:
-        _wcat_cache.pop(k_, None)
-    refs = tuple(weakref.ref(w, lambda _r, k_=key, c=_wcat_cache: c.pop(k_, None)) for w in weights)
-    _wcat_cache[key] = (refs, cat)
-    return cat
+    hit = _wcat_cache.lookup(weights)
+    if hit is not None:
+        return hit
+    return _wcat_cache.store(weights, None, _chk(torch.cat([w.detach() for w in weights], 0), "weight"))
 
 
 # Small-cout 3x3 convolutions (64 -> 6 / 18 -> 2 heads of the pyramid levels, conv_last): eavsr_conv3x3_smallco_lite_f32 wherever the
@@ -328,26 +288,20 @@ def _cat_weights(weights: Sequence[Tensor]) -> Tensor:
 # the step 240.0 -> 236.8 ms (DESIGN.md 4k).  EAVSR_SMALLCO=classic: round 2's 112-184-register kernels (the A/B reference).
 SMALLCO_LITE = os.environ.get("EAVSR_SMALLCO", "lite") != "classic"
 SMALLCO_LITE_MIN_TILES = 0
-_smallco_pack_cache = register_weight_cache({})
+_smallco_pack_cache = WeightCache()
 
 
 def _packed_smallco(weights: Sequence[Tensor]) -> Tensor:
     """[ci][kx][block] form of a small-cout 3x3 weight (eavsr_pack_smallco_weight); cached per weight objects and versions"""
-    key = tuple((id(w), w._version) for w in weights)
-    hit = _smallco_pack_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
+    hit = _smallco_pack_cache.lookup(weights)
+    if hit is not None:
+        return hit
     w = _chk(_cat_weights(weights).detach(), "weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
     packed = torch.empty(lib().eavsr_smallco_packed_elems(cout, cin), device=w.device, dtype=torch.float32)
     with _DeviceOf(w):
         N.check(lib().eavsr_pack_smallco_weight(_p(w), _p(packed), cout, cin, _stream(w)), "pack_smallco_weight")
-    ids = {id(x) for x in weights}
-    for k in [k for k in _smallco_pack_cache if any(i in ids for i, _ in k)]:
-        _smallco_pack_cache.pop(k, None)
-    refs = tuple(weakref.ref(x, lambda _r, k=key, c=_smallco_pack_cache: c.pop(k, None)) for x in weights)
-    _smallco_pack_cache[key] = (refs, packed)
-    return packed
+    return _smallco_pack_cache.store(weights, None, packed)
 
 
 # 7x7 convolutions (SPyNet's basic module) and the 5x5 heads of the predictor: "bf16x6" = eavsr_conv_f32x6 (fp32 operands split
@@ -355,33 +309,29 @@ def _packed_smallco(weights: Sequence[Tensor]) -> Tensor:
 # eavsr_conv2d_f32; 5x5: F(2x2,5x5)).  A/B switches.
 CONV7_MODE = os.environ.get("EAVSR_CONV7", "bf16x6")
 CONV5_MODE = os.environ.get("EAVSR_CONV5", "bf16x6")
-_conv7_pack_cache = register_weight_cache({})
+_conv7_pack_cache = WeightCache()
+
+
+def _packed_conv(cache, nbytes_fn: str, pack_fn: str, weights: Sequence[Tensor], dgrad: bool) -> Tensor:
+    """what _packed_conv_x6 and _packed_conv3_bf16 share: the library's byte count / pack / dgrad pack entry points by name"""
+    tag = "dgrad" if dgrad else None
+    hit = cache.lookup(weights, tag)
+    if hit is not None:
+        return hit
+    w = _chk(_cat_weights(weights).detach(), "weight")
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
+    name = pack_fn + ("_dgrad" if dgrad else "")
+    packed = torch.empty(getattr(lib(), nbytes_fn)(k, *((cin, cout) if dgrad else (cout, cin))), device=w.device, dtype=torch.uint8)
+    with _DeviceOf(w):
+        N.check(getattr(lib(), "eavsr_" + name)(_p(w), _p(packed), k, cout, cin, _stream(w)), name)
+    return cache.store(weights, tag, packed)
 
 
 def _packed_conv_x6(weights: Sequence[Tensor], dgrad: bool = False) -> Tensor:
     """A-operand form of a 7x7 / 5x5 / 3x3 weight (eavsr_pack_conv_weight_x6); cached per weight objects and versions.
     dgrad=True: the form of the INPUT-GRADIENT convolution of the (single) forward weight -- transposed and flipped by the pack
     kernel itself (eavsr_pack_conv_weight_x6_dgrad), no materialised copy."""
-    key = tuple((id(w), w._version) for w in weights) + ((("dgrad", 0),) if dgrad else ())
-    hit = _conv7_pack_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
-    w = _chk(_cat_weights(weights).detach(), "weight")
-    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
-    if dgrad:
-        packed = torch.empty(lib().eavsr_conv_weight_x6_bytes(k, cin, cout), device=w.device, dtype=torch.uint8)
-        with _DeviceOf(w):
-            N.check(lib().eavsr_pack_conv_weight_x6_dgrad(_p(w), _p(packed), k, cout, cin, _stream(w)), "pack_conv_weight_x6_dgrad")
-    else:
-        packed = torch.empty(lib().eavsr_conv_weight_x6_bytes(k, cout, cin), device=w.device, dtype=torch.uint8)
-        with _DeviceOf(w):
-            N.check(lib().eavsr_pack_conv_weight_x6(_p(w), _p(packed), k, cout, cin, _stream(w)), "pack_conv_weight_x6")
-    ids = {id(x) for x in weights}
-    for k_ in [k_ for k_ in _conv7_pack_cache if (k_[-1] == ("dgrad", 0)) == dgrad and any(i in ids for i, _ in k_ if isinstance(i, int))]:
-        _conv7_pack_cache.pop(k_, None)
-    refs = tuple(weakref.ref(x, lambda _r, k_=key, c=_conv7_pack_cache: c.pop(k_, None)) for x in weights)
-    _conv7_pack_cache[key] = (refs, packed)
-    return packed
+    return _packed_conv(_conv7_pack_cache, "eavsr_conv_weight_x6_bytes", "pack_conv_weight_x6", weights, dgrad)
 
 
 # The opt-in bf16 training mode (networks.set_train_precision / EAVSR_TRAIN_PRECISION): "fp32" (the default: every convolution
@@ -416,31 +366,12 @@ def deterministic_active() -> bool:
 
 # bf16 training mode: the one-plane packed forms (eavsr_pack_conv_weight_bf16x1*), a cache of their own -- never confused with the
 # exact forms of _conv7_pack_cache, whatever the mode was when either was packed
-_bf16_pack_cache = register_weight_cache({})
+_bf16_pack_cache = WeightCache()
 
 
 def _packed_conv3_bf16(weights: Sequence[Tensor], dgrad: bool = False) -> Tensor:
     """_packed_conv_x6 for eavsr_conv3x3_bf16x1s: every value rounded once to bf16 (nearest even), one plane"""
-    key = tuple((id(w), w._version) for w in weights) + ((("dgrad", 0),) if dgrad else ())
-    hit = _bf16_pack_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
-    w = _chk(_cat_weights(weights).detach(), "weight")
-    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
-    if dgrad:
-        packed = torch.empty(lib().eavsr_conv_weight_bf16x1_bytes(k, cin, cout), device=w.device, dtype=torch.uint8)
-        with _DeviceOf(w):
-            N.check(lib().eavsr_pack_conv_weight_bf16x1_dgrad(_p(w), _p(packed), k, cout, cin, _stream(w)), "pack_conv_weight_bf16x1_dgrad")
-    else:
-        packed = torch.empty(lib().eavsr_conv_weight_bf16x1_bytes(k, cout, cin), device=w.device, dtype=torch.uint8)
-        with _DeviceOf(w):
-            N.check(lib().eavsr_pack_conv_weight_bf16x1(_p(w), _p(packed), k, cout, cin, _stream(w)), "pack_conv_weight_bf16x1")
-    ids = {id(x) for x in weights}
-    for k_ in [k_ for k_ in _bf16_pack_cache if (k_[-1] == ("dgrad", 0)) == dgrad and any(i in ids for i, _ in k_ if isinstance(i, int))]:
-        _bf16_pack_cache.pop(k_, None)
-    refs = tuple(weakref.ref(x, lambda _r, k_=key, c=_bf16_pack_cache: c.pop(k_, None)) for x in weights)
-    _bf16_pack_cache[key] = (refs, packed)
-    return packed
+    return _packed_conv(_bf16_pack_cache, "eavsr_conv_weight_bf16x1_bytes", "pack_conv_weight_bf16x1", weights, dgrad)
 
 
 def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None) -> int:
@@ -456,29 +387,24 @@ def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None)
         if tuple(w.shape) != (64, 64, 3, 3) or not w.is_cuda or not w.is_contiguous() or w.dtype != torch.float32:
             continue
         for dg in (False, True):
-            key = ((id(w), w._version),) + ((("dgrad", 0),) if dg else ())
-            hit = cache.get(key)
-            if hit is None or hit[0][0]() is not w:
-                todo.append((w, dg, key))
+            if cache.lookup((w,), "dgrad" if dg else None) is None:
+                todo.append((w, dg))
     if not todo:
         return 0
     dev = todo[0][0].device
     nbytes = int(lib().eavsr_conv_weight_bf16x1_bytes(3, 64, 64) if bf16 else lib().eavsr_conv_weight_x6_bytes(3, 64, 64))
     store = torch.empty((len(todo), nbytes), device=dev, dtype=torch.uint8)
     cnt = len(todo)
-    srcs = (C.c_void_p * cnt)(*[w.detach().data_ptr() for w, _, _ in todo])
+    srcs = (C.c_void_p * cnt)(*[w.detach().data_ptr() for w, _ in todo])
     dsts = (C.c_void_p * cnt)(*[store[i].data_ptr() for i in range(cnt)])
-    trs = (C.c_int32 * cnt)(*[int(dg) for _, dg, _ in todo])
+    trs = (C.c_int32 * cnt)(*[int(dg) for _, dg in todo])
     with _DeviceOf(todo[0][0]):
         if bf16:
             N.check(lib().eavsr_pack_conv_weight_bf16x1_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_bf16x1_multi")
         else:
             N.check(lib().eavsr_pack_conv_weight_x6_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_x6_multi")
-    for i, (w, dg, key) in enumerate(todo):
-        for k_ in [k_ for k_ in cache if (k_[-1] == ("dgrad", 0)) == dg and any(i_ == id(w) for i_, _ in k_ if isinstance(i_, int))]:
-            cache.pop(k_, None)
-        refs = (weakref.ref(w, lambda _r, k_=key, c=cache: c.pop(k_, None)),)
-        cache[key] = (refs, store[i])
+    for i, (w, dg) in enumerate(todo):
+        cache.store((w,), "dgrad" if dg else None, store[i])
     return cnt
 
 
@@ -509,7 +435,7 @@ def _conv_x6(x: Tensor, weights, biases, act, slope, sigmoid_from: int = -1):
 # type (fp32 NCHW in and out).  Set by networks.set_backbone_dtype (EAVSR_CONV3_16BIT=0 keeps these convolutions fp32: A/B switch).
 CONV3_H16 = None
 CONV3_H16_ENABLED = os.environ.get("EAVSR_CONV3_16BIT", "1") == "1"
-_h16g_pack_cache = register_weight_cache({})
+_h16g_pack_cache = WeightCache()
 
 
 def set_conv3_h16(dtype) -> None:
@@ -520,27 +446,21 @@ def set_conv3_h16(dtype) -> None:
 
 
 def _packed_h16g(weights: Sequence[Tensor], code: int) -> Tensor:
-    key = tuple((id(w), w._version) for w in weights) + (code,)
-    hit = _h16g_pack_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
+    hit = _h16g_pack_cache.lookup(weights, code)
+    if hit is not None:
+        return hit
     w = _chk(_cat_weights(weights).detach(), "weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
     packed = torch.empty(int(lib().eavsr_conv3x3_h16g_weight_bytes(cout, cin)), device=w.device, dtype=torch.uint8)
     with _DeviceOf(w):
         N.check(lib().eavsr_pack_conv3x3_h16g(_p(w), _p(packed), cout, cin, code, _stream(w)), "pack_conv3x3_h16g")
-    ids = {id(x) for x in weights}
-    for k_ in [k_ for k_ in _h16g_pack_cache if any(isinstance(e, tuple) and e[0] in ids for e in k_)]:
-        _h16g_pack_cache.pop(k_, None)
-    refs = tuple(weakref.ref(x, lambda _r, k_=key, c=_h16g_pack_cache: c.pop(k_, None)) for x in weights)
-    _h16g_pack_cache[key] = (refs, packed)
-    return packed
+    return _h16g_pack_cache.store(weights, code, packed)
 
 
 # SPyNet's 7x7 layers with >= 16 output channels in the 16-bit modes (one operand plane of csrc/conv_x6.hip); EAVSR_CONV7_16BIT=0
 # keeps them on the exact bf16x6 form (A/B switch)
 CONV7_H16_ENABLED = os.environ.get("EAVSR_CONV7_16BIT", "1") == "1"
-_h16x1_pack_cache = register_weight_cache({})
+_h16x1_pack_cache = WeightCache()
 
 
 def _conv_h16x1(x: Tensor, weights, biases, act, slope, dtype):
@@ -548,20 +468,13 @@ def _conv_h16x1(x: Tensor, weights, biases, act, slope, dtype):
     cout = sum(int(w_.shape[0]) for w_ in weights)
     k = int(weights[0].shape[-1])
     code = h16_code(dtype)
-    key = tuple((id(w_), w_._version) for w_ in weights) + (code,)
-    hit = _h16x1_pack_cache.get(key)
-    if hit is not None and all(r() is w_ for r, w_ in zip(hit[0], weights)):
-        wp = hit[1]
-    else:
+    wp = _h16x1_pack_cache.lookup(weights, code)
+    if wp is None:
         wc = _chk(_cat_weights(weights).detach(), "weight")
         wp = torch.empty(lib().eavsr_conv_weight_h16x1_bytes(k, cout, cin), device=wc.device, dtype=torch.uint8)
         with _DeviceOf(wc):
             N.check(lib().eavsr_pack_conv_weight_h16x1(_p(wc), _p(wp), k, cout, cin, code, _stream(wc)), "pack_conv_weight_h16x1")
-        ids = {id(x_) for x_ in weights}
-        for k_ in [k_ for k_ in _h16x1_pack_cache if any(isinstance(e, tuple) and e[0] in ids for e in k_)]:
-            _h16x1_pack_cache.pop(k_, None)
-        refs = tuple(weakref.ref(x_, lambda _r, k_=key, c=_h16x1_pack_cache: c.pop(k_, None)) for x_ in weights)
-        _h16x1_pack_cache[key] = (refs, wp)
+        _h16x1_pack_cache.store(weights, code, wp)
     b = _bias_of(biases)
     out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
     st = _stream(x)
@@ -647,21 +560,16 @@ def ca_fusable(x: Tensor, cout: int = 64) -> bool:
 FUSE_PIXEL_SHUFFLE = os.environ.get("EAVSR_FUSE_SHUFFLE", "1") == "1"
 
 
-_dgrad_w_cache = register_weight_cache({})
+_dgrad_w_cache = WeightCache()
 
 
 def dgrad_weight(w: Tensor) -> Tensor:
     """(cin, cout, k, k) transposed and flipped copy of a forward weight: the weight of its input-gradient convolution; cached
     per weight object and version"""
-    key = (id(w), w._version)
-    hit = _dgrad_w_cache.get(key)
-    if hit is not None and hit[0]() is w:
-        return hit[1]
-    wt = w.detach().flip(2, 3).transpose(0, 1).contiguous()
-    for k_ in [k_ for k_ in _dgrad_w_cache if k_[0] == id(w)]:
-        _dgrad_w_cache.pop(k_, None)
-    _dgrad_w_cache[key] = (weakref.ref(w, lambda _r, k_=key, c=_dgrad_w_cache: c.pop(k_, None)), wt)
-    return wt
+    hit = _dgrad_w_cache.lookup((w,))
+    if hit is not None:
+        return hit
+    return _dgrad_w_cache.store((w,), None, w.detach().flip(2, 3).transpose(0, 1).contiguous())
 
 
 class BorderPieces:
@@ -824,7 +732,7 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
         return y, plane_sum(y, sum_mul).view(n, 1, -1)
     if dgrad and not use_x6s:      # (e.g. a large launch that the Winograd kernel takes)
         weights, dgrad = [dgrad_weight(weights[0])], False
-    wp = None if use_x6s else pack_cache.get(weights)      # (the x6s kernel has its own packed form)
+    wp = None if use_x6s else _packed_f32(weights)      # (the x6s kernel has its own packed form)
     part = None
     if sum_mul is not None:      # (use_x6s holds)
         part = torch.empty((n, lib().eavsr_conv3x3_x6s_tiles(h, w), cout), device=out.device, dtype=torch.float32)
@@ -993,7 +901,7 @@ def modulated_deform_conv2d(input: Tensor, offset: Tensor, mask: Tensor, weight:
                 lambda: lib().eavsr_dcnv2_f32x9(_p(x), _p(offset), _p(mask), _p(wx), _p(b), _p(out), n, cin, h, w, cout,
                                                 deform_groups, st), "dcnv2_f32x9")
         return out
-    wp = pack_cache.get([weight])
+    wp = _packed_f32([weight])
     _launch("dcnv2", flops, nbytes, x,
             lambda: lib().eavsr_dcnv2_f32(_p(x), _p(offset), _p(mask), _p(wp), _p(b), _p(out), n, cin, h, w, cout,
                                           deform_groups, st), "dcnv2")
@@ -1131,16 +1039,15 @@ def set_dcn_il_impl(impl: str) -> None:
     DCN_IL_IMPL = impl
 
 
-_il2_pack_cache = register_weight_cache({})
+_il2_pack_cache = WeightCache()
 
 
 def _packed_dcn_il2(weight: Tensor) -> Tensor:
     """Pre-split (3 x bf16) weight slab of a 3x3 DCNv2 weight in the pair-step order of eavsr_dcnv2_il2_f32; cached per weight
     object and version, verified by identity."""
-    key = (id(weight), weight._version)
-    hit = _il2_pack_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        return hit[1]
+    hit = _il2_pack_cache.lookup((weight,))
+    if hit is not None:
+        return hit
     w = _chk(weight.detach(), "weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
     nbytes = lib().eavsr_dcn_weight_il2_bytes(cout, cin)
@@ -1149,20 +1056,16 @@ def _packed_dcn_il2(weight: Tensor) -> Tensor:
     packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.int32)
     with _DeviceOf(w):
         N.check(lib().eavsr_pack_dcn_weight_il2(_p(w), _p(packed), cout, cin, _stream(w)), "pack_dcn_weight_il2")
-    for k in [k for k in _il2_pack_cache if k[0] == id(weight)]:
-        _il2_pack_cache.pop(k, None)
-    _il2_pack_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_il2_pack_cache: c.pop(k, None)), packed)
-    return packed
+    return _il2_pack_cache.store((weight,), None, packed)
 
 
-_il16_pack_cache = register_weight_cache({})
+_il16_pack_cache = WeightCache()
 
 
 def _packed_il16(weight: Tensor, code: int) -> Tensor:
-    key = (id(weight), weight._version, code)
-    hit = _il16_pack_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        return hit[1]
+    hit = _il16_pack_cache.lookup((weight,), code)
+    if hit is not None:
+        return hit
     w = _chk(weight.detach(), "weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
     if tuple(w.shape[2:]) != (3, 3):
@@ -1173,10 +1076,7 @@ def _packed_il16(weight: Tensor, code: int) -> Tensor:
     packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.int32)
     with _DeviceOf(w):
         N.check(lib().eavsr_pack_dcn_il16_weight(_p(w), _p(packed), cout, cin, code, _stream(w)), "pack_dcn_il16_weight")
-    for k in [k for k in _il16_pack_cache if k[0] == id(weight)]:
-        _il16_pack_cache.pop(k, None)
-    _il16_pack_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_il16_pack_cache: c.pop(k, None)), packed)
-    return packed
+    return _il16_pack_cache.store((weight,), code, packed)
 
 
 def to_il8_h16(x: Tensor, dtype) -> Tensor:
@@ -1247,16 +1147,15 @@ def set_dcn_mode(mode: str) -> None:
     DCN_MODE = mode
 
 
-_x9_pack_cache = register_weight_cache({})
+_x9_pack_cache = WeightCache()
 
 
 def _packed_x9(weights: Sequence[Tensor]) -> Tensor:
     """Pre-split (3 x bf16) weight slab of a 3x3 weight -- or of several stacked along cout -- for the bf16x9 kernels;
     cached per weight objects and versions, verified by identity (as pack_cache)."""
-    key = tuple((id(w), w._version) for w in weights)
-    hit = _x9_pack_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
+    hit = _x9_pack_cache.lookup(weights)
+    if hit is not None:
+        return hit
     w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
     w = _chk(w.detach(), "weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
@@ -1268,12 +1167,7 @@ def _packed_x9(weights: Sequence[Tensor]) -> Tensor:
     packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.int32)
     with _DeviceOf(w):
         N.check(lib().eavsr_pack_dcn_weight_x9(_p(w), _p(packed), cout, cin, _stream(w)), "pack_dcn_weight_x9")
-    ids = {id(x) for x in weights}
-    for k in [k for k in _x9_pack_cache if any(i in ids for i, _ in k)]:
-        _x9_pack_cache.pop(k, None)
-    refs = tuple(weakref.ref(x, lambda _r, k=key, c=_x9_pack_cache: c.pop(k, None)) for x in weights)
-    _x9_pack_cache[key] = (refs, packed)
-    return packed
+    return _x9_pack_cache.store(weights, None, packed)
 
 
 def _packed_dcn_x9(weight: Tensor) -> Tensor:
@@ -1335,7 +1229,7 @@ def modes(conv: Optional[str] = None, dcn: Optional[str] = None, dcn_il_impl: Op
         set_dcn_il_impl(prev[2])
 
 
-_wino_pack_cache = register_weight_cache({})
+_wino_pack_cache = WeightCache()
 
 
 def _packed_wino(weights: Sequence[Tensor], four: bool = False, kind: Optional[str] = None) -> Tensor:
@@ -1344,10 +1238,9 @@ def _packed_wino(weights: Sequence[Tensor], four: bool = False, kind: Optional[s
     kind = kind or ("f4" if four else "f2")
     if kind == "f2":
         require_lab("Winograd F(2x2,3x3)")
-    key = tuple((id(w), w._version) for w in weights) + ((kind, 0),)
-    hit = _wino_pack_cache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], weights)):
-        return hit[1]
+    hit = _wino_pack_cache.lookup(weights, kind)
+    if hit is not None:
+        return hit
     w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
     w = _chk(w.detach(), "weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
@@ -1359,12 +1252,7 @@ def _packed_wino(weights: Sequence[Tensor], four: bool = False, kind: Optional[s
         fn = getattr(lib(), {"f2": "eavsr_pack_conv_weight_wino", "f4": "eavsr_pack_conv_weight_wino4",
                              "f5": "eavsr_pack_conv_weight_wino5x5"}[kind])
         N.check(fn(_p(w), _p(packed), cout, cin, _stream(w)), "pack_conv_weight_wino")
-    ids = {id(x) for x in weights}
-    for k in [k for k in _wino_pack_cache if k[-1] == (kind, 0) and any(i in ids for i, _ in k[:-1])]:
-        _wino_pack_cache.pop(k, None)
-    refs = tuple(weakref.ref(x, lambda _r, k=key, c=_wino_pack_cache: c.pop(k, None)) for x in weights)
-    _wino_pack_cache[key] = (refs, packed)
-    return packed
+    return _wino_pack_cache.store(weights, kind, packed)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2105,14 +1993,13 @@ def from_nhwc_h16(x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
     return out
 
 
-_h16_pack_cache = register_weight_cache({})
+_h16_pack_cache = WeightCache()
 
 
 def _packed_h16(weight: Tensor, code: int) -> Tensor:
-    key = (id(weight), weight._version, code)
-    hit = _h16_pack_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        return hit[1]
+    hit = _h16_pack_cache.lookup((weight,), code)
+    if hit is not None:
+        return hit
     w = _chk(weight.detach(), "weight")
     if tuple(w.shape) != (64, 64, 3, 3):
         raise NotImplementedError("the 16-bit backbone kernel is the 3x3 64->64 convolution")
@@ -2120,10 +2007,7 @@ def _packed_h16(weight: Tensor, code: int) -> Tensor:
     st = _stream(w)
     with _DeviceOf(w):
         N.check(lib().eavsr_pack_conv3x3_c64_h16(_p(w), _p(packed), code, st), "pack_conv3x3_c64_h16")
-    for k in [k for k in _h16_pack_cache if k[0] == id(weight)]:
-        _h16_pack_cache.pop(k, None)
-    _h16_pack_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_h16_pack_cache: c.pop(k, None)), packed)
-    return packed
+    return _h16_pack_cache.store((weight,), code, packed)
 
 
 def conv3x3_c64_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], relu: bool = False, chan_partial: bool = False,
@@ -2279,17 +2163,17 @@ def rcab_convs_h16(x: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: 
     return (out, part) if chan_partial else out
 
 
-_h16_ps_cache = register_weight_cache({})
-_h16_last_cache = register_weight_cache({})
+_h16_ps_cache = WeightCache()
+_h16_last_cache = WeightCache()
 
 
 def _packed_h16_ps2(weight: Tensor, bias: Optional[Tensor], code: int):
     """(256, 64, 3, 3) weight of a conv + PixelShuffle(2) stage -> four packed 64 -> 64 matrices (slice k = 2 dy + dx: the output
     channels 4 c + k as channel c) and the bias in the same order (4 x 64)"""
-    key = (id(weight), weight._version, None if bias is None else (id(bias), bias._version), code)
-    hit = _h16_ps_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        return hit[1], hit[2]
+    sources = (weight,) if bias is None else (weight, bias)
+    hit = _h16_ps_cache.lookup(sources, code)
+    if hit is not None:
+        return hit
     w = _chk(weight.detach(), "weight")
     if tuple(w.shape) != (256, 64, 3, 3):
         raise NotImplementedError("the 16-bit pixel-shuffle stage is the 3x3 64 -> 256 convolution")
@@ -2300,10 +2184,7 @@ def _packed_h16_ps2(weight: Tensor, bias: Optional[Tensor], code: int):
         for k in range(4):
             N.check(lib().eavsr_pack_conv3x3_c64_h16(_p(sl[k]), _p(packed[k]), code, st), "pack_conv3x3_c64_h16")
     b4 = None if bias is None else _chk(bias.detach(), "bias").view(64, 4).t().contiguous()
-    for k in [k for k in _h16_ps_cache if k[0] == id(weight)]:
-        _h16_ps_cache.pop(k, None)
-    _h16_ps_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_h16_ps_cache: c.pop(k, None)), packed, b4)
-    return packed, b4
+    return _h16_ps_cache.store(sources, code, (packed, b4))
 
 
 def conv3x3_c64_h16_act(x: Tensor, weight: Tensor, bias: Optional[Tensor], act: Optional[str] = None, slope: float = 0.0,
@@ -2338,15 +2219,10 @@ def conv3x3_c64to3_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], residu
     n, h, w, c = x.shape
     if c != 64 or tuple(weight.shape) != (3, 64, 3, 3):
         raise NotImplementedError("the 16-bit conv_last kernel is the 3x3 64 -> 3 convolution")
-    key = (id(weight), weight._version, x.dtype)
-    hit = _h16_last_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        wt = hit[1]
-    else:      # [ky][kx][8-channel block][co][8 channels], rounded to the activation type (scalar loads in the kernel)
-        wt = _chk(weight.detach(), "weight").view(3, 8, 8, 3, 3).permute(3, 4, 1, 0, 2).contiguous().to(x.dtype)
-        for k in [k for k in _h16_last_cache if k[0] == id(weight)]:
-            _h16_last_cache.pop(k, None)
-        _h16_last_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_h16_last_cache: c.pop(k, None)), wt)
+    wt = _h16_last_cache.lookup((weight,), x.dtype)
+    if wt is None:      # [ky][kx][8-channel block][co][8 channels], rounded to the activation type (scalar loads in the kernel)
+        wt = _h16_last_cache.store((weight,), x.dtype,
+                                   _chk(weight.detach(), "weight").view(3, 8, 8, 3, 3).permute(3, 4, 1, 0, 2).contiguous().to(x.dtype))
     b = None if bias is None else _chk(bias.detach(), "bias")
     r = None if residual is None else _chk(residual, "residual")
     if r is not None and tuple(r.shape) != (n, 3, h, w):
@@ -2360,25 +2236,21 @@ def conv3x3_c64to3_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], residu
     return out
 
 
-_h16_pack5_cache = register_weight_cache({})
+_h16_pack5_cache = WeightCache()
 
 
 def _packed5_h16(wcat: Tensor, code: int) -> Tensor:
     """(cout, 64, 5, 5) fp32 (a parameter or the cached concatenation of several) -> the 16-bit MFMA-fragment order"""
-    key = (id(wcat), wcat._version, code)
-    hit = _h16_pack5_cache.get(key)
-    if hit is not None and hit[0]() is wcat:
-        return hit[1]
+    hit = _h16_pack5_cache.lookup((wcat,), code)
+    if hit is not None:
+        return hit
     if wcat.dim() != 4 or tuple(wcat.shape[1:]) != (64, 5, 5) or wcat.shape[0] > 128:
         raise NotImplementedError("the 16-bit heads kernel is the 5x5 convolution 64 -> (<= 128) channels")
     packed = torch.empty(int(lib().eavsr_conv5x5_c64_h16_weight_bytes()) // 2, device=wcat.device, dtype=_H16_TORCH[code])
     st = _stream(wcat)
     with _DeviceOf(wcat):
         N.check(lib().eavsr_pack_conv5x5_c64_h16(_p(wcat), _p(packed), int(wcat.shape[0]), code, st), "pack_conv5x5_c64_h16")
-    for k in [k for k in _h16_pack5_cache if k[0] == id(wcat)]:
-        _h16_pack5_cache.pop(k, None)
-    _h16_pack5_cache[key] = (weakref.ref(wcat, lambda _r, k=key, c=_h16_pack5_cache: c.pop(k, None)), packed)
-    return packed
+    return _h16_pack5_cache.store((wcat,), code, packed)
 
 
 def conv5x5_c64_h16(x: Tensor, weights, biases) -> Tensor:
@@ -2455,16 +2327,15 @@ def _out_or_new(out: Optional[Tensor], shape, like: Tensor, name: str) -> Tuple[
     return out, _batch_stride(out, name)
 
 
-_pwc_pack_cache = register_weight_cache({})
+_pwc_pack_cache = WeightCache()
 
 
 def _packed_pwc_conv3x3(weight: Tensor) -> Tensor:
     """[9][cin even][cout padded] form of a (cout, cin, 3, 3) weight for eavsr_pwc_conv3x3_f32; cached per weight object and
     version, verified by identity."""
-    key = (id(weight), weight._version)
-    hit = _pwc_pack_cache.get(key)
-    if hit is not None and hit[0]() is weight:
-        return hit[1]
+    hit = _pwc_pack_cache.lookup((weight,))
+    if hit is not None:
+        return hit
     w = _chk(weight.detach(), "weight")
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
         raise NotImplementedError(f"pwc_conv3x3: weight shape {tuple(w.shape)} (3x3 only)")
@@ -2475,10 +2346,7 @@ def _packed_pwc_conv3x3(weight: Tensor) -> Tensor:
     packed = torch.empty(elems, device=w.device, dtype=torch.float32)
     with _DeviceOf(w):
         N.check(lib().eavsr_pwc_pack_conv3x3_f32(_p(w), _p(packed), cout, cin, _stream(w)), "pwc_pack_conv3x3")
-    for k in [k for k in _pwc_pack_cache if k[0] == id(weight)]:
-        _pwc_pack_cache.pop(k, None)
-    _pwc_pack_cache[key] = (weakref.ref(weight, lambda _r, k=key, c=_pwc_pack_cache: c.pop(k, None)), packed)
-    return packed
+    return _pwc_pack_cache.store((weight,), None, packed)
 
 
 def pwc_conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, stride: int = 1, dilation: int = 1,

@@ -375,21 +375,27 @@ def test_learning_rate_schedulers_follow_the_reference_policies():
 
 
 def test_every_derived_weight_cache_is_registered_for_clearing():
-    """graph.clear_weight_caches() must drop EVERY cache keyed by (parameter, version); caches register themselves in
-    ops.WEIGHT_CACHES -- no module-level `*_cache` dict of ops / autograd may stay outside it."""
-    from eavsr_amd import autograd, graph, ops
-    regs = {id(d) for d in ops.WEIGHT_CACHES}
+    """graph.clear_weight_caches() must drop EVERY cache keyed by (parameter, version).  A WeightCache registers itself
+    in WEIGHT_CACHES when it is constructed, so: no module-level `*_cache` of ops / autograd may be a bare dict (that would be an
+    unregistered cache again), every WeightCache of the two modules is in the registry, and all 20 of them are there (18 in ops,
+    pack_cache among them, 2 in autograd)."""
+    from eavsr_amd import autograd, graph, ops, weight_cache
+    assert ops.WEIGHT_CACHES is weight_cache.WEIGHT_CACHES
+    regs = {id(c) for c in weight_cache.WEIGHT_CACHES}
     found = 0
     for mod in (ops, autograd):
         for name, val in vars(mod).items():
-            if name.endswith("_cache") and isinstance(val, dict):
-                assert id(val) in regs, f"{mod.__name__}.{name} is not registered (ops.register_weight_cache)"
+            assert not (name.endswith("_cache") and isinstance(val, dict)), f"{mod.__name__}.{name} is a bare dict, not a WeightCache"
+            if isinstance(val, weight_cache.WeightCache):
+                assert id(val) in regs, f"{mod.__name__}.{name} is not in WEIGHT_CACHES"
                 found += 1
-    assert found >= 17 and id(ops.pack_cache) in regs
-    ops._dgrad_w_cache["x"] = 1
-    autograd._dcn_wt_cache["y"] = 2
+    assert found >= 20 and id(ops.pack_cache) in regs
+    w = torch.nn.Parameter(torch.zeros(2, 2, 3, 3))
+    ops._dgrad_w_cache.store((w,), None, 1)
+    autograd._dcn_wt_cache.store((w,), None, 2)
+    assert len(ops._dgrad_w_cache) == 1 and len(autograd._dcn_wt_cache) == 1
     graph.clear_weight_caches()
-    assert not ops._dgrad_w_cache and not autograd._dcn_wt_cache
+    assert len(ops._dgrad_w_cache) == 0 and len(autograd._dcn_wt_cache) == 0
 
 
 def test_scoped_mode_switches_restore_the_previous_modes():
