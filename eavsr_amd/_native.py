@@ -186,6 +186,10 @@ SIGNATURES = {
     "eavsr_flow_warp_bwd_dx_det_f32": (C.c_int, [vp] * 5 + [i32] * 4 + [vp]),
     "eavsr_dcnv2_col2im_dx_det_workspace_floats": (C.c_int64, [i32, i32, i32]),
     "eavsr_dcnv2_col2im_dx_det_f32": (C.c_int, [vp] * 5 + [i32] * 5 + [vp]),
+    # per-frame PSNR / SSIM and the 8-bit frame (csrc/metrics.hip; additions to ABI 32)
+    "eavsr_frame_metrics_partials": (i32, [i32, i32, i32, i32]),
+    "eavsr_frame_metrics_f32": (C.c_int, [vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "eavsr_rgb8_f32": (C.c_int, [vp, f32, i32, i32, i32, i32, vp, vp]),
 }
 
 # Entry points of the LAB build only (`python -m eavsr_amd.build --lab`; the header's EXPERIMENTAL section): bound when the

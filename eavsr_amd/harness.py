@@ -6,7 +6,9 @@ index maps of the datasets (data/mvsr4x_dataset.py:105-147), of the frame writin
 files under `<root>/sr_{full,patch}_<iter>/<scene>/<frame>`; a dependency-free encoder: zlib + struct) and of the SSIM of
 psnr_total.py:39-44 (skimage's `structural_similarity(win_size=11, data_range=255, multichannel=True,
 gaussian_weights=True)`, restated in torch).  LPIPS (psnr_total.py:27-35) needs the pretrained AlexNet blob of the `lpips`
-package, which does not exist here: not provided.  No dataset files: the benchmarks feed synthetic clips, a user's loader
+package, which does not exist here: not provided.  `evaluate(..., per_frame=True)` gives psnr_total.py's report -- every frame on its
+own, the mean per scene, the mean of the scenes (psnr_total.py:88-143) -- from one fused HIP pass (`ops.frame_metrics`,
+csrc/metrics.hip); `calc_psnr` / `calc_ssim` stay as the host restatements its tests compare with.  No dataset files: the benchmarks feed synthetic clips, a user's loader
 feeds `{'lr_seq', 'hr_seq', 'fname'}` dicts exactly as the reference's does.
 """
 from __future__ import annotations
@@ -65,17 +67,28 @@ def _png_chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
-def write_png(image: Tensor, path: str, level: int = 6) -> str:
+def write_png(image: Tensor, path: str, level: int = 6, hwc: Optional[bool] = None) -> str:
     """One 8-bit image, (3, H, W) RGB or (1, H, W) / (H, W) grey, values 0..255 (a `get_current_visuals()` frame: already
     clamped and rounded), as a PNG file -- what `dataset_test.imio.write(np.array(frame).astype(np.uint8), path)` leaves
-    (test_basic.py:85-92; data/imlib.py:164-166 creates the directory).  Colour type 2 / 0, bit depth 8, filter 0, one IDAT."""
+    (test_basic.py:85-92; data/imlib.py:164-166 creates the directory).  Colour type 2 / 0, bit depth 8, filter 0, one IDAT.
+    A uint8 (H, W, 3) / (H, W, 1) tensor -- one frame of `ops.frame_metrics(..., rgb8=True)` / `ops.rgb8` -- is taken as the
+    scanlines themselves: no float pass and no permute.  `hwc` says which layout a uint8 tensor has; by default a uint8 tensor
+    whose last dimension is 1 or 3 and whose first is not is interleaved (an H of 1 or 3 reads as planes, as it always did)."""
     t = image.detach()
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.dim() != 3 or t.shape[0] not in (1, 3):
-        raise ValueError(f"write_png: (3, H, W), (1, H, W) or (H, W), got {tuple(image.shape)}")
-    c, h, w = (int(v) for v in t.shape)
-    u8 = t.to(torch.float32).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous().cpu()      # astype(np.uint8): truncation
+    if hwc is None:
+        hwc = t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] in (1, 3) and t.shape[0] not in (1, 3)
+    if hwc:
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] not in (1, 3):
+            raise ValueError(f"write_png: an interleaved image is uint8 (H, W, 3) or (H, W, 1), got {t.dtype} {tuple(image.shape)}")
+        h, w, c = (int(v) for v in t.shape)
+        u8 = t.contiguous().cpu()
+    else:
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or t.shape[0] not in (1, 3):
+            raise ValueError(f"write_png: (3, H, W), (1, H, W) or (H, W), got {tuple(image.shape)}")
+        c, h, w = (int(v) for v in t.shape)
+        u8 = t.to(torch.float32).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous().cpu()      # astype(np.uint8): truncation
     rows = torch.cat([torch.zeros(h, 1, dtype=torch.uint8), u8.view(h, w * c)], 1)                  # filter byte 0 per scanline
     raw = rows.numpy().tobytes()
     d = os.path.dirname(path)
@@ -158,6 +171,89 @@ def save_visuals(res: Dict[str, Tensor], fnames: Sequence, root: str, load_iter=
     return paths
 
 
+def _frame_name(fnames, i: int, b: int = 0) -> str:
+    """name of frame i of batch entry b in an item's `fname` (a list of per-frame names, each a string or the one-element list /
+    tuple the DataLoader collates it into)"""
+    if isinstance(fnames, str) or fnames is None or len(fnames) <= i:
+        raise ValueError(f"fname: one name per frame is needed, got {fnames!r} for frame {i}")
+    name = fnames[i]
+    return name[b] if isinstance(name, (list, tuple)) else name
+
+
+def save_frames_rgb8(rgb8: Tensor, fnames: Sequence, root: str, load_iter="0", full_res: bool = False) -> List[str]:
+    """`save_visuals` for frames that already are 8-bit interleaved: rgb8 (t, H, W, C) uint8, the quantised frames of one item as
+    `ops.frame_metrics(..., rgb8=True)` / `ops.rgb8` leave them; the same paths (test_basic.py:85-92)."""
+    if rgb8.dim() != 4 or rgb8.dtype != torch.uint8:
+        raise ValueError(f"save_frames_rgb8: uint8 (t, H, W, C), got {rgb8.dtype} {tuple(rgb8.shape)}")
+    frames = rgb8.cpu()      # one copy for the item
+    paths = []
+    for i in range(frames.shape[0]):
+        name = _frame_name(fnames, i)
+        folder = os.path.join(root, "sr_%s_%s" % ("full" if full_res else "patch", load_iter), name[:3])
+        paths.append(write_png(frames[i], os.path.join(folder, name[-9:]), hwc=True))
+    return paths
+
+
+def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0) -> Dict[str, List[float]]:
+    """PSNR and SSIM of every frame on its own, as psnr_total.py:39-44 scores the stored PNG files: sr_seq / hr_seq (n, t, C, H, W)
+    device tensors (scale 255: the model's [0, 1] output and target; scale 1: `get_current_visuals()` tensors), quantised to the
+    8-bit image inside the kernel (`ops.frame_metrics`).  PSNR = -10 log10(sse / (C H W) / 255^2) in float64 on the host from the
+    kernel's exact integer sse (`inf` for identical frames); SSIM is skimage's gaussian-window definition in fp64 (`calc_ssim`).
+    Returns {'psnr': [...], 'ssim': [...]} in (n, t) order."""
+    from . import ops
+    if sr_seq.dim() != 5 or sr_seq.shape != hr_seq.shape:
+        raise ValueError(f"frame_metrics: (n, t, C, H, W) tensors of one shape, got {tuple(sr_seq.shape)} / {tuple(hr_seq.shape)}")
+    c, h, w = (int(v) for v in sr_seq.shape[2:])
+    sse, ssim, _ = ops.frame_metrics(sr_seq.detach().reshape(-1, c, h, w), hr_seq.detach().reshape(-1, c, h, w), scale)
+    return {"psnr": [psnr_from_sse(v, c * h * w) for v in sse.tolist()], "ssim": ssim.tolist()}
+
+
+def psnr_from_sse(sse: int, count: int, range: float = 255.0) -> float:
+    """-10 log10(sse / count / range^2) in float64 (psnr_total.py:13-20 on the 8-bit image); `inf` when sse == 0"""
+    return math.inf if sse == 0 else -10.0 * math.log10(sse / count / (range * range))
+
+
+def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[float]) -> Dict:
+    """The averaging of psnr_total.py:89-133 (host only): frames are grouped by the scene in the first three characters of their
+    name, every scene's frames are averaged, then the scene means are averaged -- NOT the frames, so a short scene weighs as much
+    as a long one.  Returns {'frames': [{'name', 'scene', 'psnr', 'ssim'}, ...] in the given order, 'scenes': {scene: {'psnr',
+    'ssim', 'frames': count}} sorted by scene, 'final': {'psnr', 'ssim', 'scenes': count}}.
+    LPIPS, the third column of the reference's log, is absent: it needs the pretrained AlexNet weights of the `lpips` package,
+    which this project neither has nor may fetch."""
+    if not (len(names) == len(psnr) == len(ssim)):
+        raise ValueError(f"scene_report: {len(names)} names, {len(psnr)} PSNR and {len(ssim)} SSIM values")
+    frames = [{"name": str(nm), "scene": str(nm)[:3], "psnr": float(p), "ssim": float(s)} for nm, p, s in zip(names, psnr, ssim)]
+    mean = lambda v: sum(v) / len(v) if v else math.nan
+    scenes = {}
+    for scene in sorted({fr["scene"] for fr in frames}):
+        rows = [fr for fr in frames if fr["scene"] == scene]
+        scenes[scene] = {"psnr": mean([r["psnr"] for r in rows]), "ssim": mean([r["ssim"] for r in rows]), "frames": len(rows)}
+    final = {"psnr": mean([v["psnr"] for v in scenes.values()]), "ssim": mean([v["ssim"] for v in scenes.values()]),
+             "scenes": len(scenes)}
+    return {"frames": frames, "scenes": scenes, "final": final}
+
+
+def write_metrics_log(report: Dict, path: str) -> str:
+    """A `scene_report` as a text file: per scene its frames and its mean, then the final line; PSNR to 2 decimals and SSIM to 4,
+    the precision of the reference's log (psnr_total.py:116-138), in this project's own layout.  No LPIPS column (see
+    `scene_report`)."""
+    lines = []
+    for scene, mean in report["scenes"].items():
+        lines.append(f"scene {scene}")
+        for fr in report["frames"]:
+            if fr["scene"] == scene:
+                lines.append("  %s  psnr %.2f  ssim %.4f" % (fr["name"], fr["psnr"], fr["ssim"]))
+        lines.append("  mean of %d frames  psnr %.2f  ssim %.4f" % (mean["frames"], mean["psnr"], mean["ssim"]))
+    final = report["final"]
+    lines.append("final, mean of %d scenes  psnr %.2f  ssim %.4f" % (final["scenes"], final["psnr"], final["ssim"]))
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return path
+
+
 def test_window_starts(n_images: int, n_seq: int, n_frame: int) -> List[int]:
     """First frame of every test item (mvsr4x_dataset.py:130-136): each scene of `n_seq` consecutive frames is cut
     into n_seq / n_frame non-overlapping windows of n_frame frames.  Raises as the reference does when n_seq is not
@@ -201,7 +297,7 @@ def crop_center(img: Tensor, p: int) -> Tensor:
 
 
 def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssim_flag: bool = False,
-             save_root: Optional[str] = None, load_iter="0", full_res: bool = False) -> Dict:
+             save_root: Optional[str] = None, load_iter="0", full_res: bool = False, per_frame: bool = False) -> Dict:
     """The timed loop of test_basic.py:56-83 for a model wrapper (EAVSRPModel / EAVSRPx2Model); with `save_root` the frames are
     written as the reference's `--save_imgs` does (test_basic.py:85-92, `save_visuals`); `calc_ssim_flag` adds psnr_total.py's SSIM
     per item (mean over the item's frames).
@@ -209,11 +305,20 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     Every item is a `{'lr_seq': (n,t,3,h,w), 'hr_seq': (n,t,3,sh,sw), 'fname': ...}` dict in [0,1].  Returns the
     per-item PSNR list, their mean, the wall time of the `model.test()` calls (device-synchronised on both sides,
     as the reference's) and frames/s over all items (the reference discards its first iteration inside
-    `EAVSRPModel.forward`, eavsrp_model.py:104-107; `model.time` / `model.num` keep that convention)."""
+    `EAVSRPModel.forward`, eavsrp_model.py:104-107; `model.time` / `model.num` keep that convention).
+
+    `per_frame=True` scores with the fused kernel instead (`ops.frame_metrics` on `model.data_sr_seq` / `data_hr_seq`, no
+    `get_current_visuals` pass): the per-item 'psnr' / 'ssim' keep their meaning (the item's PSNR from the summed squared error, the
+    mean of its frames' SSIM), and the result gains 'frame_psnr' / 'frame_ssim' (every frame on its own, in item, n, t order),
+    'frame_names' and 'report' -- psnr_total.py's per-scene and final means (`scene_report`) over the items' `fname`s, which must
+    then name every frame.  With `save_root` the PNG files are written from the kernel's 8-bit frames."""
     model.eval()
     psnr: List[float] = []
     ssim: List[float] = []
     written: List[str] = []
+    frame_psnr: List[float] = []
+    frame_ssim: List[float] = []
+    frame_names: List[str] = []
     seconds = 0.0
     frames = 0
     for data in items:
@@ -224,6 +329,28 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
         torch.cuda.synchronize()
         seconds += time.time() - t0
         frames += int(model.data_sr_seq.shape[0] * model.data_sr_seq.shape[1])
+        if per_frame:
+            from . import ops
+            sr = model.data_sr_seq.detach()
+            n, t, c, h, w = (int(v) for v in sr.shape)
+            rgb8 = None
+            if model.data_hr_seq is not None:
+                hr = model.data_hr_seq.detach()
+                sse, fs, rgb8 = ops.frame_metrics(sr.reshape(n * t, c, h, w), hr.reshape(n * t, c, h, w), 255.0,
+                                                  rgb8=save_root is not None)
+                sse, fs = sse.tolist(), fs.tolist()
+                frame_psnr += [psnr_from_sse(v, c * h * w) for v in sse]
+                frame_ssim += fs
+                frame_names += [_frame_name(data.get("fname"), i, b) for b in range(n) for i in range(t)]
+                if calc_psnr_flag:
+                    psnr.append(psnr_from_sse(sum(sse), n * t * c * h * w))
+                if calc_ssim_flag:
+                    ssim.append(sum(fs) / len(fs))
+            elif save_root is not None:
+                rgb8 = ops.rgb8(sr.reshape(n * t, c, h, w), 255.0)
+            if save_root is not None:
+                written += save_frames_rgb8(rgb8[:t], data["fname"], save_root, load_iter, full_res)      # batch entry 0, as save_visuals
+            continue
         res = None
         if (calc_psnr_flag or calc_ssim_flag) and model.data_hr_seq is not None:
             res = model.get_current_visuals()
@@ -234,7 +361,7 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
         if save_root is not None:
             res = res if res is not None else model.get_current_visuals()
             written += save_visuals(res, data["fname"], save_root, load_iter, full_res)
-    return {
+    out = {
         "psnr": psnr,
         "psnr_mean": (sum(psnr) / len(psnr)) if psnr else math.nan,
         "ssim": ssim,
@@ -244,3 +371,7 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
         "frames": frames,
         "frames_per_s": frames / seconds if seconds > 0 else math.nan,
     }
+    if per_frame:
+        out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
+                   report=scene_report(frame_names, frame_psnr, frame_ssim))
+    return out

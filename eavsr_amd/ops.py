@@ -1429,6 +1429,46 @@ def concat3(a: Tensor, b: Tensor, c: Tensor) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------------
+# per-frame PSNR / SSIM and the 8-bit frame  (psnr_total.py:39-44, test_basic.py:85-92)
+# ------------------------------------------------------------------------------------------
+def frame_metrics(sr: Tensor, hr: Tensor, scale: float = 255.0, rgb8: bool = False):
+    """sr, hr (F, C, H, W), C 1 or 3, H, W >= 11 -> (sse int64 (F,), ssim float64 (F,), rgb8 uint8 (F, H, W, C) or None), all on
+    the device, of the frames quantised as `get_current_visuals` quantises them (rint(clamp(v * scale, 0, 255)); scale = 1 for
+    tensors that already are visuals): sse the exact sum of squared differences per frame, ssim the mean SSIM of psnr_total.py:41
+    (11-tap gaussian window, fp64), rgb8 the quantised `sr` as interleaved bytes.  One fused launch and a fixed-order sum: two
+    calls on the same input agree bit for bit."""
+    sr, hr = _chk(sr, "sr"), _chk(hr, "hr")
+    if sr.dim() != 4 or sr.shape != hr.shape:
+        raise ValueError(f"frame_metrics: (F, C, H, W) tensors of one shape, got {tuple(sr.shape)} / {tuple(hr.shape)}")
+    f, c, h, w = (int(v) for v in sr.shape)
+    parts = lib().eavsr_frame_metrics_partials(f, c, h, w)
+    if parts < 0:
+        N.check(parts, "frame_metrics")
+    ws = torch.empty((max(f * parts, 1), 2), device=sr.device, dtype=torch.int64)      # 16 bytes per workgroup partial
+    sse = torch.empty(f, device=sr.device, dtype=torch.int64)
+    ssim_sum = torch.empty(f, device=sr.device, dtype=torch.float64)
+    img = torch.empty((f, h, w, c), device=sr.device, dtype=torch.uint8) if rgb8 else None
+    st = _stream(sr)
+    _launch("frame_metrics", 2.0 * 110.0 * sr.numel(), 8.0 * sr.numel() + (sr.numel() if rgb8 else 0), sr,
+            lambda: lib().eavsr_frame_metrics_f32(_p(sr), _p(hr), float(scale), f, c, h, w, _p(ws), _p(sse), _p(ssim_sum), _p(img),
+                                                  st), "frame_metrics")
+    return sse, ssim_sum / float(c * (h - 10) * (w - 10)), img
+
+
+def rgb8(sr: Tensor, scale: float = 255.0) -> Tensor:
+    """sr (F, C, H, W), C 1 or 3 -> uint8 (F, H, W, C): rint(clamp(v * scale, 0, 255)) interleaved, the bytes of the frame's PNG
+    scanlines (test_basic.py:85-92), without the metrics"""
+    sr = _chk(sr, "sr")
+    if sr.dim() != 4:
+        raise ValueError(f"rgb8: an (F, C, H, W) tensor, got {tuple(sr.shape)}")
+    f, c, h, w = (int(v) for v in sr.shape)
+    img = torch.empty((f, h, w, c), device=sr.device, dtype=torch.uint8)
+    st = _stream(sr)
+    _launch("rgb8", 0.0, 5.0 * sr.numel(), sr, lambda: lib().eavsr_rgb8_f32(_p(sr), float(scale), f, c, h, w, _p(img), st), "rgb8")
+    return img
+
+
+# ------------------------------------------------------------------------------------------
 # channel attention
 # ------------------------------------------------------------------------------------------
 def ca_scale(partial: Tensor, hw: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, with_mean: bool = False):

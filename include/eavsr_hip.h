@@ -700,6 +700,26 @@ int64_t eavsr_dcnv2_col2im_dx_det_workspace_floats(int32_t n, int32_t h, int32_t
 int eavsr_dcnv2_col2im_dx_det_f32(const float* offset, const float* mask, const float* dcolumns, float* dx, void* workspace, int32_t n,
                                   int32_t c, int32_t h, int32_t w, int32_t deform_groups, void* stream);
 
+/* ---- f4: per-frame PSNR / SSIM of the evaluation report (added to ABI 32, nothing above changes) ---------------------------------
+ * replaces calc_metrics of psnr_total.py:39-44 (calc_psnr_np, psnr_total.py:13-20, and skimage's structural_similarity(win_size=11,
+ * data_range=255, multichannel=True, gaussian_weights=True)) as the per-frame loop of psnr_total.py:88-143 calls it, and the
+ * float -> uint8 -> HWC conversion of the frame writing (test_basic.py:85-92), in one pass over F frames of C planes (1 or 3) of
+ * H x W fp32 samples, NCHW.  Every sample of both images is quantised first, q = rint(clamp(v * scale, 0, 255)), round half to even
+ * (models/eavsrp_model.py get_current_visuals: scale = 255 for tensors in [0, 1], 1 for tensors that already are visuals).
+ *   sse_out[f]      = sum over the frame of (q_sr - q_hr)^2, exact.
+ *   ssim_sum_out[f] = sum of the SSIM map over the C (H - 10)(W - 10) valid positions (11-tap gaussian window, sigma 1.5, sample
+ *                     covariance, K1 = 0.01, K2 = 0.03, data range 255); moments and map in fp64.  Mean SSIM = sum / count.
+ *   rgb8 (nullable) = q_sr as bytes, HWC interleaved: (F, H, W, C), the scanlines of the frame's PNG.
+ * workspace: F * eavsr_frame_metrics_partials(F, C, H, W) * 16 bytes, 16-byte aligned (one (fp64, int64) pair per workgroup; summed
+ * per frame in a fixed order by a second launch: no atomics, two calls on the same input agree bit for bit).
+ * NULL pointer: -1; H or W < 11, C not 1 or 3, F > 65535: -2 (eavsr_frame_metrics_partials returns -2 as well). */
+int32_t eavsr_frame_metrics_partials(int32_t F, int32_t C, int32_t H, int32_t W);
+int eavsr_frame_metrics_f32(const float* sr, const float* hr, float scale, int32_t F, int32_t C, int32_t H, int32_t W, void* workspace,
+                            int64_t* sse_out, double* ssim_sum_out, uint8_t* rgb8, void* stream);
+/* the quantisation and interleave alone (test_basic.py:85-92 `--save_imgs` without psnr_total.py's metrics): rgb8 (F, H, W, C);
+ * H, W >= 1 */
+int eavsr_rgb8_f32(const float* sr, float scale, int32_t F, int32_t C, int32_t H, int32_t W, uint8_t* rgb8, void* stream);
+
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
  * Schedules that were built, measured against the stable ones above and retired; kept because DESIGN.md / docs/history quote
