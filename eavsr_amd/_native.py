@@ -190,6 +190,14 @@ SIGNATURES = {
     "eavsr_frame_metrics_partials": (i32, [i32, i32, i32, i32]),
     "eavsr_frame_metrics_f32": (C.c_int, [vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "eavsr_rgb8_f32": (C.c_int, [vp, f32, i32, i32, i32, i32, vp, vp]),
+    # LPIPS (AlexNet), the report's third column (csrc/lpips.hip; additions to ABI 32)
+    "eavsr_lpips_conv_weight_elems": (C.c_int64, [i32, i32, i32]),
+    "eavsr_lpips_pack_conv_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "eavsr_lpips_conv1_f32": (C.c_int, [vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "eavsr_lpips_conv_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "eavsr_lpips_maxpool3s2_f32": (C.c_int, [vp, vp, i64, i32, i32, vp]),
+    "eavsr_lpips_tap_partials": (i32, [i32, i32]),
+    "eavsr_lpips_tap_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
 }
 
 # Entry points of the LAB build only (`python -m eavsr_amd.build --lab`; the header's EXPERIMENTAL section): bound when the

@@ -5,10 +5,10 @@ synchronize, PSNR on the clamp*255*round visuals), of `calc_psnr` (util/util.py:
 index maps of the datasets (data/mvsr4x_dataset.py:105-147), of the frame writing of test_basic.py:85-92 (8-bit RGB PNG
 files under `<root>/sr_{full,patch}_<iter>/<scene>/<frame>`; a dependency-free encoder: zlib + struct) and of the SSIM of
 psnr_total.py:39-44 (skimage's `structural_similarity(win_size=11, data_range=255, multichannel=True,
-gaussian_weights=True)`, restated in torch).  LPIPS (psnr_total.py:27-35) needs the pretrained AlexNet blob of the `lpips`
-package, which does not exist here: not provided.  `evaluate(..., per_frame=True)` gives psnr_total.py's report -- every frame on its
+gaussian_weights=True)`, restated in torch).  `evaluate(..., per_frame=True)` gives psnr_total.py's report -- every frame on its
 own, the mean per scene, the mean of the scenes (psnr_total.py:88-143) -- from one fused HIP pass (`ops.frame_metrics`,
-csrc/metrics.hip); `calc_psnr` / `calc_ssim` stay as the host restatements its tests compare with.  No dataset files: the benchmarks feed synthetic clips, a user's loader
+csrc/metrics.hip), and with an LPIPS network (`eavsr_amd.lpips.LPIPSAlex`, csrc/lpips.hip; its pretrained weights come from a path
+the user names, `opt.lpips_path`: none ship here) the report's third column, LPIPS (psnr_total.py:27-35), as well; `calc_psnr` / `calc_ssim` stay as the host restatements its tests compare with.  No dataset files: the benchmarks feed synthetic clips, a user's loader
 feeds `{'lr_seq', 'hr_seq', 'fname'}` dicts exactly as the reference's does.
 """
 from __future__ import annotations
@@ -194,18 +194,22 @@ def save_frames_rgb8(rgb8: Tensor, fnames: Sequence, root: str, load_iter="0", f
     return paths
 
 
-def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0) -> Dict[str, List[float]]:
+def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0, lpips=None) -> Dict[str, List[float]]:
     """PSNR and SSIM of every frame on its own, as psnr_total.py:39-44 scores the stored PNG files: sr_seq / hr_seq (n, t, C, H, W)
     device tensors (scale 255: the model's [0, 1] output and target; scale 1: `get_current_visuals()` tensors), quantised to the
     8-bit image inside the kernel (`ops.frame_metrics`).  PSNR = -10 log10(sse / (C H W) / 255^2) in float64 on the host from the
     kernel's exact integer sse (`inf` for identical frames); SSIM is skimage's gaussian-window definition in fp64 (`calc_ssim`).
-    Returns {'psnr': [...], 'ssim': [...]} in (n, t) order."""
+    Returns {'psnr': [...], 'ssim': [...]} in (n, t) order; with `lpips` (an `eavsr_amd.lpips.LPIPSAlex` on the tensors' device)
+    also 'lpips': the AlexNet LPIPS of every frame pair on the same 8-bit images (psnr_total.py:27-35)."""
     from . import ops
     if sr_seq.dim() != 5 or sr_seq.shape != hr_seq.shape:
         raise ValueError(f"frame_metrics: (n, t, C, H, W) tensors of one shape, got {tuple(sr_seq.shape)} / {tuple(hr_seq.shape)}")
     c, h, w = (int(v) for v in sr_seq.shape[2:])
     sse, ssim, _ = ops.frame_metrics(sr_seq.detach().reshape(-1, c, h, w), hr_seq.detach().reshape(-1, c, h, w), scale)
-    return {"psnr": [psnr_from_sse(v, c * h * w) for v in sse.tolist()], "ssim": ssim.tolist()}
+    out = {"psnr": [psnr_from_sse(v, c * h * w) for v in sse.tolist()], "ssim": ssim.tolist()}
+    if lpips is not None:
+        out["lpips"] = lpips(sr_seq.detach().reshape(-1, c, h, w), hr_seq.detach().reshape(-1, c, h, w), scale).tolist()
+    return out
 
 
 def psnr_from_sse(sse: int, count: int, range: float = 255.0) -> float:
@@ -213,39 +217,47 @@ def psnr_from_sse(sse: int, count: int, range: float = 255.0) -> float:
     return math.inf if sse == 0 else -10.0 * math.log10(sse / count / (range * range))
 
 
-def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[float]) -> Dict:
+def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[float], lpips: Optional[Sequence[float]] = None) -> Dict:
     """The averaging of psnr_total.py:89-133 (host only): frames are grouped by the scene in the first three characters of their
     name, every scene's frames are averaged, then the scene means are averaged -- NOT the frames, so a short scene weighs as much
     as a long one.  Returns {'frames': [{'name', 'scene', 'psnr', 'ssim'}, ...] in the given order, 'scenes': {scene: {'psnr',
     'ssim', 'frames': count}} sorted by scene, 'final': {'psnr', 'ssim', 'scenes': count}}.
-    LPIPS, the third column of the reference's log, is absent: it needs the pretrained AlexNet weights of the `lpips` package,
-    which this project neither has nor may fetch."""
+    With `lpips` (one value per frame: the third column of the reference's log, psnr_total.py:116-138) every frame, every scene and
+    'final' carry an 'lpips' field as well, averaged exactly as the other two; without it the report has no such field."""
     if not (len(names) == len(psnr) == len(ssim)):
         raise ValueError(f"scene_report: {len(names)} names, {len(psnr)} PSNR and {len(ssim)} SSIM values")
+    if lpips is not None and len(lpips) != len(names):
+        raise ValueError(f"scene_report: {len(names)} names and {len(lpips)} LPIPS values")
     frames = [{"name": str(nm), "scene": str(nm)[:3], "psnr": float(p), "ssim": float(s)} for nm, p, s in zip(names, psnr, ssim)]
+    cols = ["psnr", "ssim"]
+    if lpips is not None:
+        cols.append("lpips")
+        for fr, v in zip(frames, lpips):
+            fr["lpips"] = float(v)
     mean = lambda v: sum(v) / len(v) if v else math.nan
     scenes = {}
     for scene in sorted({fr["scene"] for fr in frames}):
         rows = [fr for fr in frames if fr["scene"] == scene]
-        scenes[scene] = {"psnr": mean([r["psnr"] for r in rows]), "ssim": mean([r["ssim"] for r in rows]), "frames": len(rows)}
-    final = {"psnr": mean([v["psnr"] for v in scenes.values()]), "ssim": mean([v["ssim"] for v in scenes.values()]),
-             "scenes": len(scenes)}
+        scenes[scene] = {**{k: mean([r[k] for r in rows]) for k in cols}, "frames": len(rows)}
+    final = {**{k: mean([v[k] for v in scenes.values()]) for k in cols}, "scenes": len(scenes)}
     return {"frames": frames, "scenes": scenes, "final": final}
 
 
 def write_metrics_log(report: Dict, path: str) -> str:
     """A `scene_report` as a text file: per scene its frames and its mean, then the final line; PSNR to 2 decimals and SSIM to 4,
-    the precision of the reference's log (psnr_total.py:116-138), in this project's own layout.  No LPIPS column (see
-    `scene_report`)."""
+    the precision of the reference's log (psnr_total.py:116-138), in this project's own layout.  A report with LPIPS (see
+    `scene_report`) gets `  lpips %.3f` at the end of every line, the reference's three decimals; one without it produces the
+    file it always produced."""
     lines = []
+    third = lambda row: "  lpips %.3f" % row["lpips"] if "lpips" in report["final"] else ""
     for scene, mean in report["scenes"].items():
         lines.append(f"scene {scene}")
         for fr in report["frames"]:
             if fr["scene"] == scene:
-                lines.append("  %s  psnr %.2f  ssim %.4f" % (fr["name"], fr["psnr"], fr["ssim"]))
-        lines.append("  mean of %d frames  psnr %.2f  ssim %.4f" % (mean["frames"], mean["psnr"], mean["ssim"]))
+                lines.append("  %s  psnr %.2f  ssim %.4f" % (fr["name"], fr["psnr"], fr["ssim"]) + third(fr))
+        lines.append("  mean of %d frames  psnr %.2f  ssim %.4f" % (mean["frames"], mean["psnr"], mean["ssim"]) + third(mean))
     final = report["final"]
-    lines.append("final, mean of %d scenes  psnr %.2f  ssim %.4f" % (final["scenes"], final["psnr"], final["ssim"]))
+    lines.append("final, mean of %d scenes  psnr %.2f  ssim %.4f" % (final["scenes"], final["psnr"], final["ssim"]) + third(final))
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -297,7 +309,7 @@ def crop_center(img: Tensor, p: int) -> Tensor:
 
 
 def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssim_flag: bool = False,
-             save_root: Optional[str] = None, load_iter="0", full_res: bool = False, per_frame: bool = False) -> Dict:
+             save_root: Optional[str] = None, load_iter="0", full_res: bool = False, per_frame: bool = False, lpips=None) -> Dict:
     """The timed loop of test_basic.py:56-83 for a model wrapper (EAVSRPModel / EAVSRPx2Model); with `save_root` the frames are
     written as the reference's `--save_imgs` does (test_basic.py:85-92, `save_visuals`); `calc_ssim_flag` adds psnr_total.py's SSIM
     per item (mean over the item's frames).
@@ -311,7 +323,20 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     `get_current_visuals` pass): the per-item 'psnr' / 'ssim' keep their meaning (the item's PSNR from the summed squared error, the
     mean of its frames' SSIM), and the result gains 'frame_psnr' / 'frame_ssim' (every frame on its own, in item, n, t order),
     'frame_names' and 'report' -- psnr_total.py's per-scene and final means (`scene_report`) over the items' `fname`s, which must
-    then name every frame.  With `save_root` the PNG files are written from the kernel's 8-bit frames."""
+    then name every frame.  With `save_root` the PNG files are written from the kernel's 8-bit frames.
+
+    `lpips` (with `per_frame=True` only; it raises otherwise): an `eavsr_amd.lpips.LPIPSAlex`, or the path of its weights (one file
+    in the lpips package's state-dict layout, see `lpips.load_lpips_weights`), read once; the default is `model.opt.lpips_path`
+    where the options have one.  The result then gains 'frame_lpips' and the report its 'lpips' column (psnr_total.py:27-35, every
+    frame pair on the same 8-bit images).  Items without HR frames are skipped, as they are for PSNR and SSIM."""
+    if lpips is not None and not per_frame:
+        raise ValueError("evaluate: lpips needs per_frame=True (LPIPS is part of the per-frame report)")
+    if lpips is None and per_frame:
+        lpips = getattr(getattr(model, "opt", None), "lpips_path", None)
+    if isinstance(lpips, (str, os.PathLike)):
+        from .lpips import build_lpips
+        lpips = build_lpips(os.fspath(lpips), device=model.device)
+    frame_lpips: List[float] = []
     model.eval()
     psnr: List[float] = []
     ssim: List[float] = []
@@ -341,6 +366,8 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
                 sse, fs = sse.tolist(), fs.tolist()
                 frame_psnr += [psnr_from_sse(v, c * h * w) for v in sse]
                 frame_ssim += fs
+                if lpips is not None:
+                    frame_lpips += lpips(sr.reshape(n * t, c, h, w), hr.reshape(n * t, c, h, w), 255.0).tolist()
                 frame_names += [_frame_name(data.get("fname"), i, b) for b in range(n) for i in range(t)]
                 if calc_psnr_flag:
                     psnr.append(psnr_from_sse(sum(sse), n * t * c * h * w))
@@ -373,5 +400,7 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     }
     if per_frame:
         out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
-                   report=scene_report(frame_names, frame_psnr, frame_ssim))
+                   report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips if lpips is not None else None))
+        if lpips is not None:
+            out["frame_lpips"] = frame_lpips
     return out

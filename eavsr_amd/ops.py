@@ -1469,6 +1469,126 @@ def rgb8(sr: Tensor, scale: float = 255.0) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------------
+# LPIPS (AlexNet), the report's third column  (psnr_total.py:27-35; csrc/lpips.hip)
+# ------------------------------------------------------------------------------------------
+_lpips_pack_cache = WeightCache()
+
+
+def _lp(t: Tensor, name: str, dim: Optional[int] = 4) -> Tensor:
+    """an fp32 contiguous GPU tensor, taken as it is: the LPIPS entry points copy nothing"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: dtype {t.dtype} unsupported (fp32 only)")
+    if dim is not None and t.dim() != dim:
+        raise ValueError(f"{name}: expected {dim} dimensions, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous, strides {t.stride()} for shape {tuple(t.shape)}")
+    return t
+
+
+def _packed_lpips_conv(weight: Tensor) -> Tensor:
+    """[k^2][cin padded to 4][cout] form of a (cout, cin, k, k) weight for eavsr_lpips_conv1_f32 / eavsr_lpips_conv_f32; cached per
+    weight object and version, verified by identity."""
+    hit = _lpips_pack_cache.lookup((weight,))
+    if hit is not None:
+        return hit
+    w = _lp(weight.detach(), "weight")
+    cout, cin, k, k2 = (int(v) for v in w.shape)
+    elems = lib().eavsr_lpips_conv_weight_elems(cout, cin, k) if k == k2 else -1
+    if elems <= 0:
+        raise NotImplementedError(f"lpips_conv: weight shape {tuple(w.shape)} unsupported")
+    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
+    with _DeviceOf(w):
+        N.check(lib().eavsr_lpips_pack_conv_f32(_p(w), _p(packed), cout, cin, k, _stream(w)), "lpips_pack_conv")
+    return _lpips_pack_cache.store((weight,), None, packed)
+
+
+def lpips_conv1(sr: Tensor, hr: Tensor, weight: Tensor, bias: Tensor, shift: Tensor, scl: Tensor, scale: float = 255.0) -> Tensor:
+    """sr, hr (F, 3, H, W) -> (2F, cout, (H - 7) // 4 + 1, (W - 7) // 4 + 1): relu(conv2d(front(cat(sr, hr)), weight (cout, 3, 11,
+    11), bias, stride 4, padding 2)) with front(v) = ((rint(clamp(v * scale, 0, 255)) / 127.5 - 1) - shift[c]) / scl[c] applied in
+    registers (the 8-bit image of `frame_metrics`, lpips' im2tensor and ScalingLayer)."""
+    sr, hr = _lp(sr, "sr"), _lp(hr, "hr")
+    if sr.shape != hr.shape or sr.shape[1] != 3:
+        raise ValueError(f"lpips_conv1: (F, 3, H, W) tensors of one shape, got {tuple(sr.shape)} / {tuple(hr.shape)}")
+    if tuple(weight.shape[1:]) != (3, 11, 11):
+        raise ValueError(f"lpips_conv1: weight {tuple(weight.shape)}, expected (cout, 3, 11, 11)")
+    f, _, h, w = (int(v) for v in sr.shape)
+    cout = int(weight.shape[0])
+    wp = _packed_lpips_conv(weight)
+    b, shift, scl = _lp(bias.detach(), "bias", 1), _lp(shift.detach(), "shift", None), _lp(scl.detach(), "scale", None)
+    if b.numel() != cout or shift.numel() != 3 or scl.numel() != 3:
+        raise ValueError("lpips_conv1: bias (cout), shift and scale of three values each")
+    ho, wo = (h - 7) // 4 + 1, (w - 7) // 4 + 1
+    out = torch.empty((2 * f, cout, max(ho, 0), max(wo, 0)), device=sr.device, dtype=torch.float32)
+    st = _stream(sr)
+    px = 2.0 * f * max(ho, 0) * max(wo, 0)
+    _launch("lpips_conv1", 2.0 * 363 * cout * px, 4.0 * (2 * sr.numel() + out.numel()), sr,
+            lambda: lib().eavsr_lpips_conv1_f32(_p(sr), _p(hr), float(scale), _p(shift), _p(scl), _p(wp), _p(b), _p(out), f, h, w, cout,
+                                                 st), "lpips_conv1")
+    return out
+
+
+def lpips_conv(x: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
+    """relu(F.conv2d(x, weight (cout, cin, k, k), bias, padding=k // 2)) in fp32 on the matrix pipe: AlexNet features.3 / 6 / 8 / 10"""
+    x = _lp(x, "x")
+    n, cin, h, w = (int(v) for v in x.shape)
+    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    if int(weight.shape[1]) != cin:
+        raise ValueError(f"lpips_conv: weight takes {int(weight.shape[1])} channels, input has {cin}")
+    wp = _packed_lpips_conv(weight)
+    b = _lp(bias.detach(), "bias", 1)
+    if b.numel() != cout:
+        raise ValueError(f"lpips_conv: bias of {b.numel()} values for {cout} channels")
+    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    st = _stream(x)
+    px = float(n) * h * w
+    _launch("lpips_conv", 2.0 * k * k * cin * cout * px, 4.0 * px * (cin + cout), x,
+            lambda: lib().eavsr_lpips_conv_f32(_p(x), _p(wp), _p(b), _p(out), n, cin, h, w, cout, k, st), "lpips_conv")
+    return out
+
+
+def lpips_maxpool(x: Tensor) -> Tensor:
+    """F.max_pool2d(x, 3, 2) of an (n, c, h, w) tensor, h, w >= 3"""
+    x = _lp(x, "x")
+    n, c, h, w = (int(v) for v in x.shape)
+    out = torch.empty((n, c, max((h - 3) // 2 + 1, 0), max((w - 3) // 2 + 1, 0)), device=x.device, dtype=torch.float32)
+    st = _stream(x)
+    _launch("lpips_maxpool", 0.0, 4.0 * (x.numel() + out.numel()), x,
+            lambda: lib().eavsr_lpips_maxpool3s2_f32(_p(x), _p(out), n * c, h, w, st), "lpips_maxpool")
+    return out
+
+
+def lpips_tap(feat: Tensor, lin_weight: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """feat (2F, C, h, w): images [0:F] and [F:2F] are the two sides; lin_weight the tap's (1, C, 1, 1) weight.  Returns the float64
+    (F,) means over the pixels of sum_c lin_c (f^_a - f^_b)^2, f^ = f / (sqrt(sum_c f^2) + 1e-10); with `out` (float64 (F,)) the
+    means are ADDED to it.  Fixed-order sums: two calls agree bit for bit."""
+    feat = _lp(feat, "feat")
+    n2, c, h, w = (int(v) for v in feat.shape)
+    if n2 % 2:
+        raise ValueError(f"lpips_tap: an even number of images (SR then HR), got {n2}")
+    f = n2 // 2
+    lin = _lp(lin_weight.detach(), "lin_weight", None)
+    if lin.numel() != c:
+        raise ValueError(f"lpips_tap: lin weight of {lin.numel()} values for {c} channels")
+    parts = lib().eavsr_lpips_tap_partials(h, w)
+    if parts < 0:
+        N.check(parts, "lpips_tap")
+    ws = torch.empty(max(f * parts, 1), device=feat.device, dtype=torch.float64)
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(f, device=feat.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (f,) or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"lpips_tap: `out` must be a contiguous float64 ({f},) device tensor")
+    st = _stream(feat)
+    _launch("lpips_tap", 8.0 * feat.numel(), 4.0 * feat.numel(), feat,
+            lambda: lib().eavsr_lpips_tap_f32(_p(feat), _p(lin), _p(ws), _p(out), f, c, h, w, int(accumulate), st), "lpips_tap")
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # channel attention
 # ------------------------------------------------------------------------------------------
 def ca_scale(partial: Tensor, hw: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, with_mean: bool = False):

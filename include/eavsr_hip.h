@@ -720,6 +720,41 @@ int eavsr_frame_metrics_f32(const float* sr, const float* hr, float scale, int32
  * H, W >= 1 */
 int eavsr_rgb8_f32(const float* sr, float scale, int32_t F, int32_t C, int32_t H, int32_t W, uint8_t* rgb8, void* stream);
 
+/* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
+ * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
+ * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
+ * All tensors fp32 NCHW; the F SR frames and F HR frames of an item are ONE batch of 2F images (image f: SR frame f, image F + f:
+ * its HR frame).  Nothing is allocated; every launch goes to `stream`.
+ *
+ * Convolution weights are packed once: [ksize^2][cin rounded up to 4][cout], zeros in the padding (torchvision AlexNet
+ * `features.{0,3,6,8,10}.weight`, (cout, cin, k, k)).  cout must be a multiple of 64. */
+int64_t eavsr_lpips_conv_weight_elems(int32_t cout, int32_t cin, int32_t ksize);
+int eavsr_lpips_pack_conv_f32(const float* weight, float* packed, int32_t cout, int32_t cin, int32_t ksize, void* stream);
+/* First stage with the front end fused in: sr, hr (F, 3, H, W) fp32 in RGB order.  Per sample q = rint(clamp(v * scale, 0, 255))
+ * (half to even, as eavsr_frame_metrics_f32), x = q / 127.5 - 1 (lpips `im2tensor`), (x - shift3[c]) / scale3[c] (lpips
+ * `ScalingLayer`; shift3, scale3: device pointers to three floats) in registers, then ReLU(conv 3 -> cout, 11 x 11, stride 4, zero
+ * padding 2 of the scaled image, + bias) on the fp32 matrix pipe: out (2F, cout, (H - 7) / 4 + 1, (W - 7) / 4 + 1).
+ * NULL pointer: -1; H or W < 7, cout not a multiple of 64: -2. */
+int eavsr_lpips_conv1_f32(const float* sr, const float* hr, float scale, const float* shift3, const float* scale3,
+                          const float* weight_packed, const float* bias, float* out, int32_t F, int32_t H, int32_t W, int32_t cout,
+                          void* stream);
+/* ReLU(conv cin -> cout, ksize x ksize, stride 1, padding ksize / 2, + bias) on the fp32 matrix pipe (fp32 operands and
+ * accumulators): AlexNet features.3 (5 x 5), .6, .8, .10 (3 x 3).  x (n, cin, h, w), out (n, cout, h, w).
+ * cin not a multiple of 32, cout not a multiple of 64, ksize not in {1, 3, 5, 7, 11}: -2. */
+int eavsr_lpips_conv_f32(const float* x, const float* weight_packed, const float* bias, float* out, int32_t n, int32_t cin, int32_t h,
+                         int32_t w, int32_t cout, int32_t ksize, void* stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2) (no padding, floor) of `planes` planes of h x w: out (planes, (h - 3) / 2 + 1,
+ * (w - 3) / 2 + 1).  h or w < 3: -2. */
+int eavsr_lpips_maxpool3s2_f32(const float* x, float* out, int64_t planes, int32_t h, int32_t w, void* stream);
+/* One tap of LPIPS (lpips `normalize_tensor`, the squared difference, `NetLinLayer` without dropout, `spatial_average`):
+ * feat (2F, C, h, w), lin_weight (C) the tap's 1 x 1 weight.  Per frame f and pixel: f^ = feat / (sqrt(sum_c feat^2) + 1e-10) for
+ * images f and F + f, d = sum_c lin_weight[c] (f^_sr - f^_hr)^2;  out[f] = (accumulate ? out[f] : 0) + mean over the pixels of d,
+ * fp64.  workspace: F * eavsr_lpips_tap_partials(h, w) doubles (one partial per workgroup, added per frame in a fixed order by a
+ * second launch: no atomics, two calls on the same input agree bit for bit).  C > 448 or F > 65535: -2. */
+int32_t eavsr_lpips_tap_partials(int32_t h, int32_t w);
+int eavsr_lpips_tap_f32(const float* feat, const float* lin_weight, void* workspace, double* out, int32_t F, int32_t C, int32_t h,
+                        int32_t w, int32_t accumulate, void* stream);
+
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
  * Schedules that were built, measured against the stable ones above and retired; kept because DESIGN.md / docs/history quote
