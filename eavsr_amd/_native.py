@@ -90,6 +90,7 @@ SIGNATURES = {
     "eavsr_conv2d_ck": (i32, [i32]),
     "eavsr_conv2d_tile_rows": (i32, [i32, i32, i32, i32]),
     "eavsr_conv2d_tiles": (i32, [i32, i32, i32, i32]),
+    "eavsr_route_batch": (i32, [i32]),
     "eavsr_packed_weight_elems": (i64, [i32, i32, i32]),
     "eavsr_pack_conv_weight_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),
     "eavsr_conv3x3_smallco_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
@@ -190,6 +191,7 @@ SIGNATURES = {
     "eavsr_frame_metrics_partials": (i32, [i32, i32, i32, i32]),
     "eavsr_frame_metrics_f32": (C.c_int, [vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "eavsr_rgb8_f32": (C.c_int, [vp, f32, i32, i32, i32, i32, vp, vp]),
+    "eavsr_u8_to_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
     # LPIPS (AlexNet), the report's third column (csrc/lpips.hip; additions to ABI 32)
     "eavsr_lpips_conv_weight_elems": (C.c_int64, [i32, i32, i32]),
     "eavsr_lpips_pack_conv_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),

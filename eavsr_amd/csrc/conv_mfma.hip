@@ -24,6 +24,7 @@
 // The input is the virtual concatenation of up to 5 sources, so torch.cat never materialises.
 #include "common.h"
 
+#include <atomic>
 #include <mutex>
 
 namespace {
@@ -632,8 +633,14 @@ int launch_ks(const ConvArgs& a, dim3 grid, int CO, bool vec, hipStream_t st) {
 
 // rows per wave for an (n, h, w) problem: minimise rounds over the 256 CUs x (rows per tile + fixed per-tile cost).
 // 7x7 (SPyNet only) keeps the 32-row tile.
+// eavsr_route_batch: a caller that cuts one batch into several launches (EAVSRP.forward_long's frame chunks) names the batch size the
+// choice below is made for, so that every chunk runs the tile height -- and with it the per-tile channel sums -- of the whole batch.
+std::atomic<int> g_route_batch{0};
+
 inline int tile_rows_of(int n, int h, int w, int ksize) {
   if (ksize == 7) return 4;
+  const int routed = g_route_batch.load(std::memory_order_relaxed);
+  if (routed > 0) n = routed;
   int best = 4;
   long best_cost = -1;
   for (int nt = 4; nt >= 1; nt >>= 1) {
@@ -655,6 +662,8 @@ int launch_nt(const ConvArgs& a, dim3 grid, int CO, bool vec, int nt, hipStream_
 }  // namespace
 
 extern "C" int32_t eavsr_conv2d_ck(int32_t ksize) { return chunk_of(ksize); }
+
+extern "C" int32_t eavsr_route_batch(int32_t n) { return g_route_batch.exchange(n > 0 ? n : 0, std::memory_order_relaxed); }
 
 extern "C" int32_t eavsr_conv2d_tile_rows(int32_t n, int32_t h, int32_t w, int32_t ksize) {
   return 8 * tile_rows_of(n > 0 ? n : 1, h, w, ksize);

@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import autograd as AG
+from . import framestore as FS
 from . import networks as N
 from . import ops
 
@@ -312,9 +313,15 @@ class EAVSRP(nn.Module):
         n, t = lqs.shape[:2]
         branches = [k for k in feats if k not in _PYR]
         srcs = [_frame_major(feats["spatial"])] + [_frame_major(feats[k]) for k in branches]
-        hr = self.reconstruction(srcs)
         if lq_tm is None:
             lq_tm = lqs.transpose(0, 1).reshape(t * n, *lqs.shape[2:])
+        out = self._upsample_tm(srcs, lq_tm)
+        return out.view(t, n, *out.shape[1:]).transpose(0, 1).contiguous()
+
+    def _upsample_tm(self, srcs, lq_tm):
+        """the tail on frame-major tensors: srcs = `spatial` and the four branches (rows, 64, h, w), lq_tm (rows, 3, h, w) ->
+        (rows, 3, s h, s w).  `upsample` runs it on all t n rows, `forward_long` on a chunk of frames."""
+        hr = self.reconstruction(srcs)
         tail16 = (N.BACKBONE_DTYPE is not None and TAIL_IN_16BIT and self.n_feats == 64 and
                   not AG.needs_grad(hr, lq_tm, list(self.upsample1.parameters()) + list(self.conv_hr.parameters()) +
                                     list(self.conv_last.parameters()) + (list(self.upsample2.parameters()) if self.scale == 4 else [])))
@@ -330,8 +337,7 @@ class EAVSRP(nn.Module):
                 hr = ops.conv3x3_c64_h16_act(hr, u2.weight, u2.bias, act="lrelu", slope=0.1, pixel_shuffle2=True)
             hr = ops.conv3x3_c64_h16_act(hr, self.conv_hr.weight, self.conv_hr.bias, act="lrelu", slope=0.1)
             skip = ops.resize_bilinear(lq_tm, (self.scale * lq_tm.shape[2], self.scale * lq_tm.shape[3]))
-            out = ops.conv3x3_c64to3_h16(hr, self.conv_last.weight, self.conv_last.bias, residual=skip)
-            return out.view(t, n, *out.shape[1:]).transpose(0, 1).contiguous()
+            return ops.conv3x3_c64to3_h16(hr, self.conv_last.weight, self.conv_last.bias, residual=skip)
         # conv -> PixelShuffle(2) -> LeakyReLU (:343-347): the activation commutes with the shuffle and the shuffle is the conv
         # kernel's own store pattern (the torch copy was 0.8 / 3.3 GB per 2-clip forward)
         hr = self.upsample1[0](hr, act="lrelu", slope=0.1, pixel_shuffle2=True)
@@ -341,8 +347,159 @@ class EAVSRP(nn.Module):
         # nn.Upsample(scale_factor, 'bilinear', align_corners=False) (:158,359): source coordinate (dst + 0.5) / s - 0.5
         skip = (self.img_upsample(lq_tm) if lq_tm.requires_grad else
                 ops.resize_bilinear(lq_tm, (self.scale * lq_tm.shape[2], self.scale * lq_tm.shape[3])))
-        out = self.conv_last(hr, residual=skip)                                      # :359-360
-        return out.view(t, n, *out.shape[1:]).transpose(0, 1).contiguous()
+        return self.conv_last(hr, residual=skip)                                     # :359-360
+
+    # -- long clips ------------------------------------------------------------------------
+    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None):
+        """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
+
+        The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
+        pyramid, the reconstruction with the upsampling tail -- run over `frame_chunk` frames at a time (all n clips of those
+        frames), so their activations no longer grow with t; `propagate` is a per-time-step recurrence already and keeps its
+        arithmetic.  Each chunk is launched under `ops.route_batch(<the whole batch>)`: every convolution takes the kernel the
+        whole batch would take, and the result is bit-identical to `forward(lrs)` (DESIGN 7b names the one route that is not
+        pinned).  frame_chunk=None or >= t: one chunk, no pinning -- the launches of `forward`.
+
+        cache="device": every per-frame tensor stays in device memory, as in `forward`.  cache="host": the `cpu_cache` of the
+        BasicVSR family -- frames in pinned host memory, a device window of what the current and the next time step read, copies
+        on one side stream (`framestore.HostStore`).  A copy changes no bits: both give the same result.
+
+        lrs: (n, t, 3, h, w) fp32 in [0, 1] on the device, or uint8 -- (n, t, 3, h, w) or interleaved (n, t, h, w, 3), on the
+        device or in (pinned) host memory -- converted chunk by chunk with `ops.u8_to_f32` (v / 255, the reference's
+        `np.float32(img) / 255`), so that a host-resident scene crosses the link as bytes.
+
+        sink: `sink(first_frame, sr_chunk)` is called once per finished chunk with sr_chunk (n, frames, 3, s h, s w); the SR clip is
+        then never allocated as a whole and None is returned.  Without a sink: the (n, t, 3, s h, s w) tensor `forward` returns."""
+        FS.check_cache(cache)
+        if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
+            raise ValueError("forward_long: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_long is inference only: call it under torch.no_grad() (training runs `forward`)")
+        u8 = lrs.dtype == torch.uint8
+        if not u8 and not lrs.is_cuda:
+            raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path); for a CPU reference use "
+                               "the original repository with --gpu_ids -1")
+        device = lrs.device if lrs.is_cuda else next(self.parameters()).device
+        if device.type != "cuda":
+            raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path): a uint8 clip in host memory needs the "
+                               "network on the GPU")
+        hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
+        n, t = int(lrs.shape[0]), int(lrs.shape[1])
+        c, h, w = (3, int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[2:])
+        assert h >= 64 and w >= 64, (
+            'The height and width of inputs should be at least 64, '
+            f'but got {h} and {w}.')
+        if frame_chunk is not None and int(frame_chunk) < 1:
+            raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
+        fc = t if frame_chunk is None else min(int(frame_chunk), t)
+        chunks = [(a, min(a + fc, t)) for a in range(0, t, fc)]
+        single = len(chunks) == 1
+        pin = (lambda rows: None) if single else (lambda rows: rows)      # one chunk IS the whole batch: nothing to pin
+        store = FS.make_store(cache, n, t, device)
+
+        # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
+        last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
+        for a, b in chunks:
+            lr_c = self._ingest(lrs, a, b, device, hwc)
+            store.put_range("lr", a, lr_c)
+            seq = lr_c if last is None else torch.cat([last, lr_c], 0)
+            m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
+            if m > 0:
+                lrs_1, lrs_2 = seq[:m], seq[n:]
+                with ops.route_batch(pin(2 * n * (t - 1))):
+                    both = self.spynet(torch.cat([lrs_1, lrs_2], 0), torch.cat([lrs_2, lrs_1], 0))
+                first = a if last is None else a - 1
+                store.put_range("flow_backward", first, both[:m])
+                store.put_range("flow_forward", first, both[m:])
+            with ops.route_batch(pin(t * n)):
+                f1 = self.encoder(lr_c)
+                f2, f4 = AG.pyramid(f1)
+            for key, val in zip(_PYR, (f1, f2, f4)):
+                store.put_range(key, a, val)
+            last = lr_c[-n:]
+            del lr_c, seq, f1, f2, f4
+
+        # -- stage 2: the four branches, one time step at a time
+        branches = []
+        for iter_ in (1, 2):
+            for direction in ("backward", "forward"):
+                module = f"{direction}_{iter_}"
+                self._propagate_long(store, module, list(branches), n, t)
+                branches.append(module)
+
+        # -- stage 3, per chunk: reconstruction + upsampling tail
+        keys = ["spatial"] + branches + ["lr"]
+        out = None
+        for key in keys:
+            store.prefetch_range(key, *chunks[0])
+        for ci, (a, b) in enumerate(chunks):
+            tensors = [store.get_range(key, a, b) for key in keys]
+            if ci + 1 < len(chunks):      # (host cache: the next chunk's copies overlap this chunk's kernels)
+                for key in keys:
+                    store.prefetch_range(key, *chunks[ci + 1])
+            with ops.route_batch(pin(t * n)):
+                sr = self._upsample_tm(tensors[:-1], tensors[-1])
+            del tensors
+            sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
+            if sink is not None:
+                sink(a, sr.contiguous())
+            elif single:
+                out = sr.contiguous()
+            else:
+                if out is None:
+                    out = sr.new_empty((n, t) + tuple(sr.shape[2:]))
+                out[:, a:b] = sr
+            del sr
+        store.finish()
+        return out
+
+    def _ingest(self, lrs, a, b, device, hwc):
+        """frames a .. b of the clip as frame-major fp32 ((b - a) n, 3, h, w) on the device"""
+        part = lrs[:, a:b]
+        if part.dtype != torch.uint8:
+            return part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
+        if not part.is_cuda:
+            part = part.to(device, non_blocking=True)      # bytes cross the link
+        part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
+        return ops.u8_to_f32(part, hwc=hwc)
+
+    def _propagate_long(self, store, module_name, others, n, t):
+        """`propagate` (eavsrp_model.py:242-329) on a frame store, inference only: the same launches per time step; what a step
+        reads comes from the store, whose schedule (`framestore.propagate_reads` / `prefetch_schedule`) has it on the device by
+        then, and the step's result goes back to it."""
+        backward = "backward" in module_name
+        order = list(range(t))[::-1] if backward else list(range(t))
+        step = 1 if backward else -1
+        fkey = FS.FLOW_KEYS[0] if backward else FS.FLOW_KEYS[1]
+        align, fusion, backbone = self.deform_align[module_name], self.fusion[module_name], self.backbone[module_name]
+        store.begin(FS.prefetch_schedule(FS.propagate_reads(t, backward, others)))
+        feat_prop, zeros, hist = None, None, []
+        for i, idx in enumerate(order):
+            store.step(i)
+            cur = [store.get(k, idx) for k in _PYR]
+            if i == 0:
+                feat_prop = cur[0].new_zeros(cur[0].shape[0], self.n_feats, *cur[0].shape[2:])
+                store.new_branch(module_name, feat_prop)
+            else:
+                nbr = [store.get(k, idx + step) for k in _PYR]
+                flow_n1 = store.get(fkey, idx if backward else idx - 1)
+                cond_n1 = align(nbr, cur, feat_prop, flow_n1)
+                if i > 1:
+                    feat_n2 = hist[-2]
+                    nbr2 = [store.get(k, idx + 2 * step) for k in _PYR]
+                    flow_n2 = store.get(fkey, idx + 1 if backward else idx - 2)
+                    flow_n2 = AG.add(flow_n1, AG.flow_warp(flow_n2, flow_n1))            # :309-310
+                    cond_n2 = align(nbr2, cur, feat_n2, flow_n2)
+                else:
+                    if zeros is None:
+                        zeros = torch.zeros_like(cond_n1)
+                    cond_n2 = zeros
+                feat_prop = fusion([cond_n1, cur[0], cond_n2])                          # :313-314
+            res = backbone([cur[0]] + [store.get(k, idx) for k in others] + [feat_prop])   # :317-323
+            feat_prop = AG.add(feat_prop, res, out=store.out_slot(module_name, idx))
+            store.put(module_name, idx, feat_prop)
+            hist = (hist + [feat_prop])[-2:]
+            store.done(i)
 
 
 class EAVSRPx2(EAVSRP):
@@ -387,6 +544,31 @@ def make_optimizer(net: "EAVSRP", opt) -> torch.optim.Adam:
                             weight_decay=getattr(opt, "weight_decay", 0.0))
 
 
+def long_clip_options(opt=None):
+    """(frame_chunk, cpu_cache) of the opt-in long-clip path: `opt.frame_chunk` (frames per chunk of the batched stages; None / 0 =
+    off) and `opt.cpu_cache` (per-frame tensors in pinned host memory), each falling back to the environment where the options do
+    not carry it -- EAVSR_FRAME_CHUNK=<positive integer>, EAVSR_CPU_CACHE=0|1.  Neither is among the reference's options."""
+    fc = getattr(opt, "frame_chunk", None)
+    if fc is None:
+        env = os.environ.get("EAVSR_FRAME_CHUNK", "")
+        if env != "":
+            if not env.isdigit() or int(env) < 1:
+                raise ValueError(f"EAVSR_FRAME_CHUNK={env!r}: a positive number of frames")
+            fc = int(env)
+    elif isinstance(fc, bool) or not isinstance(fc, int) or fc < 0:
+        raise ValueError(f"opt.frame_chunk={fc!r}: a positive number of frames, or None")
+    fc = fc or None
+    cc = getattr(opt, "cpu_cache", None)
+    if cc is None:
+        env = os.environ.get("EAVSR_CPU_CACHE", "0")
+        if env not in ("0", "1"):
+            raise ValueError(f"EAVSR_CPU_CACHE={env!r}: 0 or 1")
+        cc = env == "1"
+    elif not isinstance(cc, bool):
+        raise ValueError(f"opt.cpu_cache={cc!r}: True or False")
+    return fc, cc
+
+
 class EAVSRPModel:
     """Stand-in of EAVSRPModel / EAVSRPx2Model (models/eavsrp_model.py:18-119): set_input / forward / test /
     optimize_parameters / get_current_visuals / load_networks / save_networks with the reference's
@@ -402,6 +584,8 @@ class EAVSRPModel:
         self.opt = opt
         self.scale = opt.scale
         self.isTrain = getattr(opt, "isTrain", False)
+        # opt.frame_chunk / opt.cpu_cache (not among the reference's options): the opt-in long-clip inference path (EAVSRP.forward_long)
+        self.frame_chunk, self.cpu_cache = long_clip_options(opt)
         # opt.train_precision (not among the reference's options): the opt-in bf16 training mode (networks.set_train_precision)
         if getattr(opt, "train_precision", None) is not None:
             N.set_train_precision(opt.train_precision)
@@ -495,7 +679,12 @@ class EAVSRPModel:
                 self.data_sr_seq = self.data_sr_seq * self.mask
             return
         start = time.time()
-        self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
+        if not self.isTrain and (self.frame_chunk is not None or self.cpu_cache):
+            with torch.no_grad():
+                self.data_sr_seq = self.netEAVSRP.forward_long(self.data_lr_seq, frame_chunk=self.frame_chunk,
+                                                               cache="host" if self.cpu_cache else "device")
+        else:
+            self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
         self.data_sr = self.data_sr_seq[:, self.idx]
         end = time.time()
         if not self.isfirst:

@@ -1,0 +1,257 @@
+"""Per-frame tensors of a long clip (EAVSRP.forward_long): where they live and when they move.
+
+A clip of t frames keeps, per frame, the encoder's pyramid (`spatial`, `spatial_d2`, `spatial_d4`), the four propagation
+branches, the two flows and the fp32 LR frame.  `DeviceStore` keeps them in device memory as `EAVSRP.forward` does (frame-major
+buffers, a frame is a contiguous slice).  `HostStore` is the `cpu_cache` of the BasicVSR family: every frame lives in pinned host
+memory and the device holds a WINDOW -- what the current and the next time step of `propagate` read -- filled by copies on one
+side stream that run ahead of the compute stream, ordered by events only.
+
+The order in which `propagate` reads its inputs is known before it starts (`propagate_reads`), so the copies follow a schedule
+computed on the host (`prefetch_schedule`): both are pure functions of (t, direction, earlier branches) and are tested without a
+GPU.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+Tensor = torch.Tensor
+Item = Tuple[str, int]
+
+PYR = ("spatial", "spatial_d2", "spatial_d4")
+FLOW_KEYS = ("flow_backward", "flow_forward")
+
+
+def propagate_reads(t: int, backward: bool, others: Sequence[str] = ()) -> List[List[Item]]:
+    """What time step i of one propagation branch over t frames reads from the store, as (key, frame) pairs in the order the step
+    uses them (eavsrp_model.py:242-329): the current frame's pyramid; from the second step on the neighbour's pyramid and the flow
+    between the two; from the third step on the second neighbour's pyramid and the flow one step further; the frame's features of
+    every earlier branch (`others`).  A backward branch walks frames t-1 .. 0 and reads `flow_backward`, a forward branch walks
+    0 .. t-1 and reads `flow_forward`; flow j joins frames j and j + 1.  (The branch's own last two outputs are the recurrence's
+    state: they never leave the device and are not listed.)"""
+    if t < 1:
+        raise ValueError(f"propagate_reads: t >= 1, got {t}")
+    order = list(range(t))[::-1] if backward else list(range(t))
+    step = 1 if backward else -1
+    fkey = FLOW_KEYS[0] if backward else FLOW_KEYS[1]
+    reads: List[List[Item]] = []
+    for i, idx in enumerate(order):
+        r: List[Item] = [(k, idx) for k in PYR]
+        if i > 0:
+            r += [(k, idx + step) for k in PYR]
+            r.append((fkey, idx if backward else idx - 1))
+            if i > 1:
+                r += [(k, idx + 2 * step) for k in PYR]
+                r.append((fkey, idx + 1 if backward else idx - 2))
+        r += [(k, idx) for k in others]
+        reads.append(r)
+    return reads
+
+
+class Schedule(NamedTuple):
+    """prologue: copied in before step 0 is enqueued (what step 0 reads).  fetch[i]: copies started when step i is enqueued -- what
+    step i + 1 reads and the window does not hold yet; they overlap step i's kernels.  evict[i]: dropped from the window once step
+    i is enqueued (nothing step i + 1 reads)."""
+    prologue: List[Item]
+    fetch: List[List[Item]]
+    evict: List[List[Item]]
+
+
+def prefetch_schedule(reads: Sequence[Sequence[Item]]) -> Schedule:
+    """One step of lookahead: while step i computes, the window holds reads[i] and reads[i + 1].  Every tensor is read in
+    consecutive steps only (a pyramid frame as current, neighbour, second neighbour; a flow twice; an earlier branch's frame once),
+    so nothing is ever fetched twice and nothing is dropped before its last use."""
+    def unique(items):
+        return list(dict.fromkeys(items))
+    prologue = unique(reads[0]) if reads else []
+    resident = set(prologue)
+    fetch, evict = [], []
+    for i in range(len(reads)):
+        nxt = unique(reads[i + 1]) if i + 1 < len(reads) else []
+        f = [it for it in nxt if it not in resident]
+        resident.update(f)
+        keep = set(nxt)
+        e = sorted(it for it in resident if it not in keep)
+        resident.difference_update(e)
+        fetch.append(f)
+        evict.append(e)
+    return Schedule(prologue, fetch, evict)
+
+
+def window_bound(n_others: int) -> Dict[str, int]:
+    """The most frames of each kind the window of `prefetch_schedule(propagate_reads(..))` ever holds: four pyramid frames (current,
+    two neighbours, the next step's new frame) at each of the three levels, three flows, two frames of every earlier branch."""
+    return {"pyramid_frames": 4, "flows": 3, "frames_per_other_branch": 2, "items": 3 * 4 + 3 + 2 * int(n_others)}
+
+
+def check_cache(cache: str) -> str:
+    if cache not in ("device", "host"):
+        raise ValueError(f"cache {cache!r}: 'device' or 'host'")
+    return cache
+
+
+class DeviceStore:
+    """Today's residency: every frame stays in device memory.  A range of frames put as one frame-major tensor ((k n, c, h, w),
+    frame-major rows) is kept as that tensor; a frame, or an aligned range, is a contiguous slice of it."""
+    cache = "device"
+
+    def __init__(self, n: int, t: int, device):
+        self.n, self.t, self.device = int(n), int(t), device
+        self._blocks: Dict[str, List[Tuple[int, int, Tensor]]] = {}      # key -> [(first frame, frames, tensor)]
+        self._where: Dict[Item, Tuple[Tensor, int]] = {}                 # (key, frame) -> (tensor, frame offset in it)
+
+    def put_range(self, key: str, first: int, frames: Tensor) -> None:
+        k = int(frames.shape[0]) // self.n
+        self._blocks.setdefault(key, []).append((first, k, frames))
+        for j in range(k):
+            self._where[(key, first + j)] = (frames, j)
+
+    def new_branch(self, key: str, like: Tensor) -> None:
+        """one frame-major buffer for a branch's t outputs: `out_slot` hands out its rows, `upsample` reads it without a torch.cat"""
+        self.put_range(key, 0, like.new_empty((self.t * self.n,) + tuple(like.shape[1:])))
+
+    def out_slot(self, key: str, idx: int) -> Optional[Tensor]:
+        return self.get(key, idx)
+
+    def put(self, key: str, idx: int, frame: Tensor) -> None:
+        if (key, idx) not in self._where:      # (a branch writes into its out_slot: nothing to do then)
+            self.put_range(key, idx, frame)
+
+    def get(self, key: str, idx: int) -> Tensor:
+        block, j = self._where[(key, idx)]
+        return block[j * self.n:(j + 1) * self.n]
+
+    def get_range(self, key: str, a: int, b: int) -> Tensor:
+        for first, k, block in self._blocks[key]:
+            if first <= a and b <= first + k:
+                return block[(a - first) * self.n:(b - first) * self.n]
+        return torch.cat([self.get(key, i) for i in range(a, b)], 0)
+
+    # the schedule is the host store's business
+    def begin(self, schedule: Schedule) -> None:
+        pass
+
+    def step(self, i: int) -> None:
+        pass
+
+    def done(self, i: int) -> None:
+        pass
+
+    def prefetch_range(self, key: str, a: int, b: int) -> None:
+        pass
+
+    def finish(self) -> None:
+        pass
+
+
+class HostStore:
+    """`cpu_cache`: frames in pinned host memory, a device window filled ahead of use.
+
+    Every copy, in either direction, runs on ONE side stream.  Device -> host: the side stream waits for an event recorded on the
+    compute stream behind the producer; the source is kept from reuse until the copy has run (`record_stream`).  Host -> device:
+    the target is allocated on the compute stream, the side stream waits for an event recorded there at that moment (whatever
+    used that memory before has finished), copies, and records the event the compute stream waits for at the tensor's first use.
+    The host never synchronises: it enqueues step i + 1's copies when it enqueues step i's kernels.  Host memory is written and
+    read back by the same stream, in order."""
+    cache = "host"
+
+    def __init__(self, n: int, t: int, device):
+        self.n, self.t, self.device = int(n), int(t), device
+        self.side = torch.cuda.Stream(device=device)
+        self._host: Dict[str, Tensor] = {}                                # key -> pinned (frames, n, c, h, w)
+        self._window: Dict[Tuple, List] = {}                              # (key, frame) or (key, (a, b)) -> [device tensor, event or None]
+        self._schedule: Optional[Schedule] = None
+        self.peak_window_items = 0
+
+    def _main(self):
+        return torch.cuda.current_stream(self.device)
+
+    def _host_buffer(self, key: str, like: Tensor) -> Tensor:
+        buf = self._host.get(key)
+        if buf is None:
+            frames = self.t - 1 if key in FLOW_KEYS else self.t
+            buf = torch.empty((max(frames, 1), self.n) + tuple(like.shape[1:]), dtype=like.dtype, pin_memory=True)
+            self._host[key] = buf
+        return buf
+
+    def put_range(self, key: str, first: int, frames: Tensor) -> None:
+        k = int(frames.shape[0]) // self.n
+        dst = self._host_buffer(key, frames)[first:first + k]
+        ready = torch.cuda.Event()
+        ready.record(self._main())
+        self.side.wait_event(ready)
+        with torch.cuda.stream(self.side):
+            dst.view((k * self.n,) + tuple(frames.shape[1:])).copy_(frames, non_blocking=True)
+        frames.record_stream(self.side)
+
+    def new_branch(self, key: str, like: Tensor) -> None:
+        self._host_buffer(key, like)
+
+    def out_slot(self, key: str, idx: int) -> Optional[Tensor]:
+        return None      # a fresh tensor per step; it leaves for the host once written
+
+    def put(self, key: str, idx: int, frame: Tensor) -> None:
+        self.put_range(key, idx, frame)
+
+    def _fetch(self, entries) -> None:
+        """entries: [(window key, host view)] -> device tensors, copied on the side stream"""
+        entries = [(wk, src) for wk, src in entries if wk not in self._window]
+        if not entries:
+            return
+        targets = [torch.empty(src.shape, dtype=src.dtype, device=self.device) for _, src in entries]
+        free = torch.cuda.Event()
+        free.record(self._main())
+        self.side.wait_event(free)
+        with torch.cuda.stream(self.side):
+            for (wk, src), dev in zip(entries, targets):
+                dev.copy_(src, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self.side)
+                self._window[wk] = [dev, ev]
+        self.peak_window_items = max(self.peak_window_items, len(self._window))
+
+    def _take(self, wk) -> Tensor:
+        entry = self._window[wk]
+        if entry[1] is not None:
+            self._main().wait_event(entry[1])
+            entry[1] = None
+        return entry[0]
+
+    def _frame(self, item: Item):
+        return item, self._host[item[0]][item[1]]
+
+    def begin(self, schedule: Schedule) -> None:
+        self._schedule = schedule
+        self._fetch([self._frame(it) for it in schedule.prologue])
+
+    def step(self, i: int) -> None:
+        self._fetch([self._frame(it) for it in self._schedule.fetch[i]])
+
+    def done(self, i: int) -> None:
+        for it in self._schedule.evict[i]:
+            self._window.pop(it, None)
+
+    def get(self, key: str, idx: int) -> Tensor:
+        return self._take((key, idx))
+
+    def prefetch_range(self, key: str, a: int, b: int) -> None:
+        src = self._host[key][a:b]
+        self._fetch([((key, (a, b)), src.view(((b - a) * self.n,) + tuple(src.shape[2:])))])
+
+    def get_range(self, key: str, a: int, b: int) -> Tensor:
+        self.prefetch_range(key, a, b)
+        out = self._take((key, (a, b)))
+        del self._window[(key, (a, b))]
+        return out
+
+    def finish(self) -> None:
+        """the compute stream waits for the side stream's last copy (the pinned buffers are about to be released)"""
+        self._window.clear()
+        last = torch.cuda.Event()
+        last.record(self.side)
+        self._main().wait_event(last)
+
+
+def make_store(cache: str, n: int, t: int, device):
+    return (HostStore if check_cache(cache) == "host" else DeviceStore)(n, t, device)

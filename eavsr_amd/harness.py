@@ -404,3 +404,106 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
         if lpips is not None:
             out["frame_lpips"] = frame_lpips
     return out
+
+
+def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
+                  frame_chunk: Optional[int] = None, cache: str = "device", lpips=None) -> Dict:
+    """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
+
+    `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
+    (`read_png`), or a tensor -- uint8 (t, 3, h, w) / (t, h, w, 3) or fp32 in [0, 1] (t, 3, h, w), with or without a leading clip
+    dimension n, in host or device memory; 8-bit frames stay bytes until the device converts them (`ops.u8_to_f32`).
+    `frame_chunk` / `cache` are `forward_long`'s.  The SR clip is never held as a whole: per finished chunk a sink
+      * writes `<out_dir>/<name>` for every frame (of clip 0) from the kernel's 8-bit frames (`ops.rgb8`) when `out_dir` is given,
+      * scores the chunk against `hr` (same layouts as `frames`, at the output size) with `ops.frame_metrics` -- and `lpips`, an
+        `eavsr_amd.lpips.LPIPSAlex` or the path of its weights -- when `hr` is given.
+    `names`: one name per frame (default: the paths' base names, else `000_00000.png`, ...); a name's first three characters are its
+    scene in the report.  Returns 'frames', 'seconds' (device-synchronised on both sides), 'frames_per_s', 'peak_bytes'
+    (`torch.cuda.max_memory_allocated` over the run), 'written', and with `hr` the 'frame_psnr' / 'frame_ssim' / 'frame_names' /
+    'report' (/ 'frame_lpips') of `evaluate(per_frame=True)`, in (n, t) order."""
+    from . import ops
+    net = getattr(model, "netEAVSRP", model)
+    device = next(net.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError("super_resolve: the network must be on the GPU (eavsr_amd has no CPU path)")
+    paths = None
+    if isinstance(frames, (list, tuple)):
+        paths = [os.fspath(p) for p in frames]
+        frames = torch.stack([read_png(p)[:3] for p in paths], 0)
+        frames = frames.pin_memory()
+
+    def as_clip(x, what):
+        if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+            raise ValueError(f"super_resolve: {what} is a (t, 3, h, w) tensor (uint8: also (t, h, w, 3)), optionally with a leading n")
+        if x.dtype != torch.uint8 and not x.is_floating_point():
+            raise ValueError(f"super_resolve: {what} is uint8 or floating point, got {x.dtype}")
+        return x.unsqueeze(0) if x.dim() == 4 else x
+    lrs = as_clip(frames, "frames")
+    if lrs.dtype != torch.uint8:
+        lrs = lrs.to(device=device, dtype=torch.float32)
+    n, t = int(lrs.shape[0]), int(lrs.shape[1])
+    if hr is not None:
+        hr = as_clip(hr, "hr")
+        if tuple(hr.shape[:2]) != (n, t):
+            raise ValueError(f"super_resolve: hr holds {tuple(hr.shape[:2])} (n, t) frames, the scene {(n, t)}")
+    if names is None:
+        names = [os.path.basename(p) for p in paths] if paths is not None else ["000_%05d.png" % i for i in range(t)]
+    if len(names) != t:
+        raise ValueError(f"super_resolve: {len(names)} names for {t} frames")
+    if isinstance(lpips, (str, os.PathLike)):
+        from .lpips import build_lpips
+        lpips = build_lpips(os.fspath(lpips), device=device)
+    if lpips is not None and hr is None:
+        raise ValueError("super_resolve: lpips needs hr")
+    written: List[str] = []
+    sse_parts, ssim_parts, lpips_parts, counts = [], [], [], []
+
+    def hr_chunk(a, b):
+        part = hr[:, a:b]
+        if not part.is_cuda:
+            part = part.to(device, non_blocking=True)
+        part = part.reshape((n * (b - a),) + tuple(part.shape[2:]))
+        return ops.u8_to_f32(part) if part.dtype == torch.uint8 else part.to(torch.float32)
+
+    def sink(first, sr):
+        k = int(sr.shape[1])
+        c, hh, ww = (int(v) for v in sr.shape[2:])
+        flat = sr.reshape(n * k, c, hh, ww)
+        rgb8 = None
+        if hr is not None:
+            ref = hr_chunk(first, first + k)
+            if ref.shape != flat.shape:
+                raise ValueError(f"super_resolve: hr frames are {tuple(ref.shape[1:])}, the output {tuple(flat.shape[1:])}")
+            sse, fs, rgb8 = ops.frame_metrics(flat, ref, 255.0, rgb8=out_dir is not None)
+            sse_parts.append(sse.view(n, k))
+            ssim_parts.append(fs.view(n, k))
+            counts.append(c * hh * ww)
+            if lpips is not None:
+                lpips_parts.append(lpips(flat, ref, 255.0).view(n, k))
+        elif out_dir is not None:
+            rgb8 = ops.rgb8(flat, 255.0)
+        if out_dir is not None:
+            host = rgb8[:k].cpu()      # clip 0, as save_visuals
+            for j in range(k):
+                written.append(write_png(host[j], os.path.join(out_dir, _frame_name(names, first + j)), hwc=True))
+
+    torch.cuda.synchronize(device)
+    torch.cuda.reset_peak_memory_stats(device)
+    t0 = time.time()
+    with torch.no_grad():
+        net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink)
+    torch.cuda.synchronize(device)
+    seconds = time.time() - t0
+    out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
+           "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written}
+    if hr is not None:
+        sse = torch.cat(sse_parts, 1).reshape(-1).tolist()      # (n, t) order, as evaluate
+        frame_ssim = torch.cat(ssim_parts, 1).reshape(-1).tolist()
+        frame_psnr = [psnr_from_sse(v, counts[0]) for v in sse]
+        frame_names = [_frame_name(names, i, b) for b in range(n) for i in range(t)]
+        frame_lpips = torch.cat(lpips_parts, 1).reshape(-1).tolist() if lpips is not None else None
+        out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
+                   report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips))
+        if lpips is not None:
+            out["frame_lpips"] = frame_lpips
+    return out

@@ -82,6 +82,37 @@ def _wino_tiles(h: int, w: int) -> int:
     return ((h + 7) // 8) * ((w + 31) // 32)
 
 
+# Route pinning.  Which kernel a convolution runs on depends on its launch size (n x tiles against WINO_MIN_TILES, X6S_MAX_TILES, the
+# direct kernel's tile height), and different kernels round differently.  A caller that cuts ONE batch into several launches
+# (EAVSRP.forward_long's frame chunks) wraps them in `with route_batch(n_whole):` -- every routing predicate below then sees the
+# batch size of the whole batch (`_rn`), and the library's own tile-height choice follows (eavsr_route_batch), so each chunk runs the
+# kernels the whole batch would and is bit-identical to its rows of the whole-batch result.  None = off: the launch's own n.
+_ROUTE_BATCH: Optional[int] = None
+
+
+def _rn(n: int) -> int:
+    """the batch size the routing predicates count with"""
+    return int(n) if _ROUTE_BATCH is None else _ROUTE_BATCH
+
+
+@contextlib.contextmanager
+def route_batch(n: Optional[int]):
+    """`with ops.route_batch(t * n):` -- convolutions launched inside choose their kernels as a batch of `n` images would, whatever
+    their own batch size (None: no pinning).  Restores the previous setting on exit, also when the body raises.  Not re-entrant
+    across threads: the pin is process-wide, like the kernel modes."""
+    global _ROUTE_BATCH
+    if n is not None and int(n) < 1:
+        raise ValueError(f"route_batch: a batch size >= 1 or None, got {n!r}")
+    prev = _ROUTE_BATCH
+    _ROUTE_BATCH = None if n is None else int(n)
+    lib().eavsr_route_batch(0 if n is None else int(n))
+    try:
+        yield
+    finally:
+        _ROUTE_BATCH = prev
+        lib().eavsr_route_batch(0 if prev is None else prev)
+
+
 # ------------------------------------------------------------------------------------------
 # optional per-launch timing (HIP events on the launch stream); off unless `with profile():`
 # ------------------------------------------------------------------------------------------
@@ -411,7 +442,7 @@ def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None)
 def x6s_takes(n: int, h: int, w: int) -> bool:
     """a single-source 3x3 64 -> 64 launch of this size runs on eavsr_conv3x3_f32x6s (the crop-sized bf16x6 kernel) in the current mode"""
     return (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4") and CONV3_H16 is None
-            and n * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
+            and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
 
 
 def _conv_x6(x: Tensor, weights, biases, act, slope, sigmoid_from: int = -1):
@@ -525,7 +556,7 @@ def _conv3x3_smallco(x: Tensor, weights, biases, act, slope, residual):
     st = _stream(x)
     px = float(n) * h * w
     if (SMALLCO_LITE and cout in (2, 3, 4, 6) and w % 4 == 0 and x.data_ptr() % 16 == 0 and h * w * cin * 4 < 2 ** 32
-            and n * ((h + 7) // 8) * ((w + 63) // 64) >= SMALLCO_LITE_MIN_TILES):
+            and _rn(n) * ((h + 7) // 8) * ((w + 63) // 64) >= SMALLCO_LITE_MIN_TILES):
         wp = _packed_smallco(list(weights))
         _launch(f"conv3x3_{cin}to{cout}", 2.0 * cin * cout * 9 * px, 4.0 * px * (cin + cout + (cout if residual is not None else 0)), x,
                 lambda: lib().eavsr_conv3x3_smallco_lite_f32(_p(x), _p(wp), _p(b), _p(residual), _p(out), n, cin, h, w, cout,
@@ -543,7 +574,7 @@ def _conv3x3_smallco(x: Tensor, weights, biases, act, slope, residual):
 def _wino_fusable(x: Tensor) -> bool:
     return (lab_available() and CONV_MODE in ("winograd", "winograd4") and x.dim() == 4 and x.shape[3] % 4 == 0 and x.shape[1] % 8 == 0 and x.shape[1] <= 256
             and x.is_contiguous() and x.data_ptr() % 16 == 0
-            and int(x.shape[0]) * _wino_tiles(int(x.shape[2]), int(x.shape[3])) >= WINO_MIN_TILES)
+            and _rn(int(x.shape[0])) * _wino_tiles(int(x.shape[2]), int(x.shape[3])) >= WINO_MIN_TILES)
 
 
 def ca_fusable(x: Tensor, cout: int = 64) -> bool:
@@ -647,7 +678,7 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
         # only the small-launch bf16x6 kernel reads the forward weight in place (necessary conditions; the decision is below)
         if not (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4") and k_ == 3 and len(srcs) == 1 and cin == 64
                 and int(weights[0].shape[1]) not in (2, 3, 4, 6) and CONV3_H16 is None
-                and n * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES):
+                and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES):
             y = conv2d(srcs, dgrad_weight(weights[0]), None, act, slope, residual)
             return y if sum_mul is None else (y, plane_sum(y, sum_mul).view(n, 1, -1))
     cout = sum(int(x.shape[0]) for x in weights) if not dgrad else int(weights[0].shape[1])
@@ -703,12 +734,12 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
         require_lab(f"conv mode {CONV_MODE!r}")
     lab = lab_available()
     use_wino = (CONV_MODE in ("winograd", "winograd4") and base_ok and not masked
-                and n * _wino_tiles(h, w) >= WINO_MIN_TILES
+                and _rn(n) * _wino_tiles(h, w) >= WINO_MIN_TILES
                 and (ca is None or (lab and len(srcs) == 1 and cin <= 256 and ca[1].data_ptr() % 16 == 0)))
     # F(4x4, 3x3): same 512-pixel-per-workgroup granularity (8 x 64), no fused channel-attention prologue
     use_wino4 = (use_wino and CONV_MODE == "winograd4" and out.data_ptr() % 16 == 0
                  and (residual is None or residual.data_ptr() % 16 == 0)
-                 and 2 * n * lib().eavsr_conv3x3_wino4_tiles(h, w) >= WINO_MIN_TILES)
+                 and 2 * _rn(n) * lib().eavsr_conv3x3_wino4_tiles(h, w) >= WINO_MIN_TILES)
     if use_wino and not use_wino4 and not lab:
         use_wino = False      # default build: F(2x2,3x3) is a lab kernel -- what F(4x4,3x3) does not take runs the direct kernel
     if res_scale is not None and not (use_wino4 and cin % 8 == 0 and lib().eavsr_wino4_schedule() >= 1):
@@ -720,12 +751,12 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
     use_wino5 = (CONV_MODE == "winograd4" and k == 5 and ca is None and not masked and w % 4 == 0 and out.data_ptr() % 8 == 0
                  and all(int(s_.shape[1]) % 4 == 0 and s_.data_ptr() % 16 == 0 for s_ in srcs)
                  and (residual is None or residual.data_ptr() % 8 == 0)
-                 and n * lib().eavsr_conv5x5_wino_tiles(h, w) * ((cout + 63) // 64) >= 2 * WINO_MIN_TILES)
+                 and _rn(n) * lib().eavsr_conv5x5_wino_tiles(h, w) * ((cout + 63) // 64) >= 2 * WINO_MIN_TILES)
     # small launches of the 64-channel 3x3 convolution (a training crop, a pyramid level): exact bf16x6 instead of the fp32 MFMA
     # (the explicit modes "direct" / "bf16x9" keep their own kernels: they are the A/B references)
     use_x6s = (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4") and k == 3 and len(srcs) == 1 and cin == 64
                and ca is None and not pixel_shuffle2 and not use_wino
-               and n * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
+               and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
     if sum_mul is not None and not (use_x6s and w % 4 == 0 and tuple(sum_mul.shape) == (n, cout, h, w) and
                                     all(t_ is None or t_.data_ptr() % 16 == 0 for t_ in (srcs[0], out, residual, sum_mul))):
         y = conv2d(srcs, weights, None, act, slope, residual, dgrad=True, precision=precision)      # the kernel's epilogue form does not apply: a launch
@@ -1466,6 +1497,31 @@ def rgb8(sr: Tensor, scale: float = 255.0) -> Tensor:
     st = _stream(sr)
     _launch("rgb8", 0.0, 5.0 * sr.numel(), sr, lambda: lib().eavsr_rgb8_f32(_p(sr), float(scale), f, c, h, w, _p(img), st), "rgb8")
     return img
+
+
+def u8_to_f32(frames: Tensor, hwc: Optional[bool] = None) -> Tensor:
+    """uint8 frames (F, C, h, w) planes or (F, h, w, 3) interleaved -> fp32 (F, C, h, w), every sample float(v) / 255.0f as an IEEE
+    division: the reference's `np.float32(img) / 255` on the device (csrc/ingest.hip).  `hwc` names the layout; by default a tensor
+    whose last dimension is 3 and whose second is not is interleaved.  Any base alignment (a slice of a byte tensor) is taken."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"u8_to_f32: expected a tensor, got {type(frames)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"u8_to_f32: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise ValueError(f"u8_to_f32: a uint8 (F, C, h, w) or (F, h, w, 3) tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if hwc is None:
+        hwc = frames.shape[3] == 3 and frames.shape[1] != 3
+    if hwc and frames.shape[3] != 3:
+        raise ValueError(f"u8_to_f32: an interleaved source is (F, h, w, 3), got {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    if hwc:
+        f, h, w, c = (int(v) for v in x.shape)
+    else:
+        f, c, h, w = (int(v) for v in x.shape)
+    out = torch.empty((f, c, h, w), device=x.device, dtype=torch.float32)
+    st = _stream(x)
+    _launch("u8_to_f32", 0.0, 5.0 * x.numel(), x, lambda: lib().eavsr_u8_to_f32(_p(x), _p(out), f, c, h, w, 1 if hwc else 0, st), "u8_to_f32")
+    return out
 
 
 # ------------------------------------------------------------------------------------------
@@ -2295,7 +2351,7 @@ RCAB_FUSED_MAX_TILES = int(os.environ.get("EAVSR_RCAB_FUSED_MAX_TILES", "1536"))
 
 def rcab_convs_h16_preferred(x: Tensor) -> bool:
     n, h, w, _ = x.shape
-    return n * ((h + 7) // 8) * ((w + 31) // 32) <= RCAB_FUSED_MAX_TILES
+    return _rn(n) * ((h + 7) // 8) * ((w + 31) // 32) <= RCAB_FUSED_MAX_TILES
 
 
 def rcab_convs_h16(x: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: Optional[Tensor], chan_partial: bool = True):

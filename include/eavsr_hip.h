@@ -249,6 +249,11 @@ int32_t eavsr_conv2d_ck(int32_t ksize);
  * chan_partial per sample).  The fused channel-attention prologue exists for 32-row tiles only (-2 otherwise). */
 int32_t eavsr_conv2d_tile_rows(int32_t n, int32_t h, int32_t w, int32_t ksize);
 int32_t eavsr_conv2d_tiles(int32_t n, int32_t h, int32_t w, int32_t ksize);
+/* Route pinning for a batch that is cut into several launches (added to ABI 32, nothing above changes): while n > 0 is set,
+ * eavsr_conv2d_tile_rows / eavsr_conv2d_tiles and eavsr_conv2d_f32 itself choose the tile height as a batch of `n` images would,
+ * whatever desc.n is -- every chunk then runs the kernel instance, and produces the per-tile channel sums, of the whole batch.
+ * n <= 0 clears it.  Process-wide; returns the previous value (0 = none). */
+int32_t eavsr_route_batch(int32_t n);
 /* number of floats of the packed weight buffer for (cout, cin, ksize) */
 int64_t eavsr_packed_weight_elems(int32_t cout, int32_t cin, int32_t ksize);
 /* weight (cout,cin,k,k) -> packed [cout_tile][cin_pad][k*k][co_in_tile], zero padded */
@@ -720,6 +725,11 @@ int eavsr_frame_metrics_f32(const float* sr, const float* hr, float scale, int32
  * H, W >= 1 */
 int eavsr_rgb8_f32(const float* sr, float scale, int32_t F, int32_t C, int32_t H, int32_t W, uint8_t* rgb8, void* stream);
 
+/* ---- 8-bit ingest (added to ABI 32, nothing above changes) --------------------------------------------------------------------------
+ * The reference's `np.float32(img) / 255` on the device: in uint8, (F, C, H, W) planes (hwc = 0) or (F, H, W, 3) interleaved
+ * (hwc = 1, C must be 3) -> out fp32 (F, C, H, W), every sample float(v) / 255.0f as an IEEE division.  `in` may have any
+ * alignment; out must be 16-byte aligned (-2 otherwise).  NULL pointer: -1; F > 65535, bad dims or layout: -2. */
+int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t H, int32_t W, int32_t hwc, void* stream);
 /* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
  * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
  * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
