@@ -1,0 +1,264 @@
+"""Device-resident training data: the reference's dataset (data/realvsr_dataset.py, data/mvsr4x_dataset.py) with the frames held on
+the GPU as bytes and a step's batch built by one gather launch (`ops.gather_pairs`, csrc/batch.hip).
+
+What stays on the host is what decides WHAT to gather -- the permutation of key frames, the mirrored windows (`harness.train_window`),
+the crop origin and the three flips of every item -- as pure functions (`draw_item`, `epoch_plan`, `check_plan`), so it is tested
+without a GPU.  An epoch's plan is two small int32 arrays, uploaded once.
+
+    store = FramePairs(lr_u8, hr_u8, scale=4, n_seq=50)                 # or FramePairs.from_files(lr_paths, hr_paths, ...)
+    batches = TrainBatches(store, batch_size=2, patch_size=96, n_frame=7, seed=0)
+    for epoch in range(epochs):
+        batches.set_epoch(epoch)
+        for batch in batches:                                           # {'lr_seq', 'hr_seq', 'fname'}: fp32, on the device
+            step.step(batch)                                            # graph.GraphedTrainStep, or model.set_input(batch) + optimize_parameters()
+
+Zero-copy variant: `TrainBatches(..., out=(step.static_lr, step.static_hr))` gathers straight into the captured graph's input
+buffers; iterate and call `step.step()` with no batch.
+
+Out of scope here: producing LR frames from HR (the reference's cv2.resize at load time; LR frames are supplied), file lists and
+option parsing, a host-memory store, random numbers on the device.
+"""
+from __future__ import annotations
+
+import random
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import harness
+
+HFLIP, VFLIP, TRANSPOSE = 1, 2, 4
+
+
+def draw_item(rng: random.Random, ih: int, iw: int, patch: int) -> Tuple[int, int, int]:
+    """(top, left, flags) of one training item, consuming `rng` exactly as the reference consumes the `random` module for it:
+    `_crop_patch` (realvsr_dataset.py:166-169) draws the COLUMN first, `randrange(0, iw - patch + 1)`, then the row,
+    `randrange(0, ih - patch + 1)`; `augment_basic` (util.py:242-245) then draws hflip, vflip and the transpose, each
+    `random() < 0.5`.  The same seed gives the reference's crop and flips."""
+    if patch < 1 or patch > ih or patch > iw:
+        raise ValueError(f"draw_item: patch {patch} does not fit a {ih} x {iw} frame")
+    left = rng.randrange(0, iw - patch + 1)
+    top = rng.randrange(0, ih - patch + 1)
+    hflip = rng.random() < 0.5
+    vflip = rng.random() < 0.5
+    rot90 = rng.random() < 0.5
+    return top, left, (HFLIP if hflip else 0) | (VFLIP if vflip else 0) | (TRANSPOSE if rot90 else 0)
+
+
+def default_name(idx: int, n_seq: int) -> str:
+    """'SSS_FFFFF.png': scene and frame within the scene, the datasets' naming (the scene is what `harness.scene_report` groups by)"""
+    return "%03d_%05d.png" % (idx // n_seq, idx % n_seq)
+
+
+def epoch_plan(n_items: int, n_frame: int, n_seq: int, batch_size: int, ih: int, iw: int, patch: int, seed: int, epoch: int,
+               rank: int = 0, world: int = 1, names: Optional[Sequence[str]] = None):
+    """What one rank gathers in one epoch: (frames (B, n, t) int32, desc (B, n, 4) int32 = top, left, flags, 0, names: B lists of
+    the n key frames' names).
+
+    Key frames are one permutation of range(n_items) per (seed, epoch), the same on every rank; rank r takes entries r, r + world,
+    ... of it, and every rank the same number: n_items // world, cut down to whole batches (the graphed step needs fixed
+    shapes, so the incomplete tail is dropped).  An item's window is `harness.train_window` (mirrored at the ends of its scene of
+    n_seq frames); its crop and flips are one `draw_item` from a generator seeded by (seed, epoch, key frame) -- so they depend
+    neither on `world` nor on `batch_size`, only on which frame it is."""
+    if n_items < 1 or n_seq < 1 or n_items % n_seq != 0:
+        raise ValueError(f"epoch_plan: {n_items} frames are not whole scenes of n_seq {n_seq}")
+    if n_frame < 1 or n_frame > n_seq:      # train_window's mirroring assumes this (NOTE: the reference does not check it)
+        raise ValueError(f"epoch_plan: n_frame {n_frame} must be in [1, n_seq {n_seq}]")
+    if batch_size < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"epoch_plan: batch_size {batch_size}, rank {rank} of {world}")
+    if patch < 1 or patch > ih or patch > iw:
+        raise ValueError(f"epoch_plan: patch {patch} does not fit a {ih} x {iw} frame")
+    perm = list(range(n_items))
+    random.Random(f"eavsr-epoch:{int(seed)}:{int(epoch)}").shuffle(perm)
+    n_batches = (n_items // world) // batch_size
+    keys = perm[rank::world][:n_batches * batch_size]
+    frames = np.zeros((n_batches, batch_size, n_frame), np.int32)
+    desc = np.zeros((n_batches, batch_size, 4), np.int32)
+    out_names: List[List[str]] = []
+    for i, key in enumerate(keys):
+        b, j = divmod(i, batch_size)
+        frames[b, j] = harness.train_window(key, key % n_seq, n_frame, n_seq)
+        desc[b, j, :3] = draw_item(random.Random(f"eavsr-item:{int(seed)}:{int(epoch)}:{key}"), ih, iw, patch)
+        if j == 0:
+            out_names.append([])
+        out_names[-1].append(names[key] if names is not None else default_name(key, n_seq))
+    return frames, desc, out_names
+
+
+def check_plan(frames, desc, n_items: int, ih: int, iw: int, patch) -> None:
+    """Host validation of a plan before it is uploaded (the kernel clamps instead of trusting it; a plan that needed the clamp is a
+    bug): every frame index in [0, n_items), every origin inside the frame, no flag above bit 2, and no transpose unless the patch
+    is square.  ValueError otherwise."""
+    ph, pw = (int(patch), int(patch)) if isinstance(patch, int) else (int(patch[0]), int(patch[1]))
+    frames, desc = np.asarray(frames), np.asarray(desc)
+    if frames.dtype != np.int32 or desc.dtype != np.int32 or desc.shape[-1] != 4 or frames.shape[:-1] != desc.shape[:-1]:
+        raise ValueError(f"check_plan: frames int32 (..., t) and desc int32 (..., 4), got {frames.dtype} {frames.shape} / {desc.dtype} {desc.shape}")
+    if ph < 1 or pw < 1 or ph > ih or pw > iw:
+        raise ValueError(f"check_plan: patch {ph} x {pw} does not fit a {ih} x {iw} frame")
+    if frames.size == 0:
+        return
+    if frames.min() < 0 or frames.max() >= n_items:
+        raise ValueError(f"check_plan: frame indices {int(frames.min())}..{int(frames.max())} outside the store's [0, {n_items})")
+    top, left, flags = desc[..., 0], desc[..., 1], desc[..., 2]
+    if top.min() < 0 or top.max() > ih - ph or left.min() < 0 or left.max() > iw - pw:
+        raise ValueError(f"check_plan: a {ph} x {pw} crop at rows {int(top.min())}..{int(top.max())}, columns {int(left.min())}.."
+                         f"{int(left.max())} leaves the {ih} x {iw} frame")
+    if (flags & ~7).any():
+        raise ValueError("check_plan: flags are bit 0 hflip, bit 1 vflip, bit 2 transpose; a higher bit is set")
+    if ph != pw and (flags & TRANSPOSE).any():
+        raise ValueError(f"check_plan: the transpose flag needs a square patch, got {ph} x {pw}")
+
+
+def _as_u8_frames(x, what: str) -> torch.Tensor:
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint8:
+            raise ValueError(f"FramePairs: {what}: uint8 frames, got {x.dtype}")
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"FramePairs: {what}: a tensor or an ndarray, got {type(x)}")
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise ValueError(f"FramePairs: {what}: uint8 (F, C, h, w) or (F, h, w, C), got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def _interleaved(x: torch.Tensor) -> bool:
+    return x.shape[3] in (1, 3) and x.shape[1] not in (1, 3)
+
+
+class FramePairs:
+    """The store: every LR frame and its HR frame as bytes on the device, CHW.
+
+    lr (F, C, h, w) / hr (F, C, scale h, scale w): uint8 tensors or ndarrays, planes or interleaved (F, h, w, C) (a last dimension
+    of 1 or 3 where the second is not; permuted ONCE here, as bytes, never in the gather kernel).  hr may be None (inference-only
+    stores).  The F frames are whole scenes of n_seq consecutive frames.  `names`: one per frame (default 'SSS_FFFFF.png').
+    `device`: where the store lives (default cuda:<current>); the shape checks run before anything is moved there."""
+
+    def __init__(self, lr, hr, scale: int, n_seq: int, names: Optional[Sequence[str]] = None, device=None):
+        lr = _as_u8_frames(lr, "lr")
+        hr = _as_u8_frames(hr, "hr") if hr is not None else None
+        lr_hwc, hr_hwc = _interleaved(lr), hr is not None and _interleaved(hr)
+        chw = lambda x, il: tuple(int(x.shape[i]) for i in ((0, 3, 1, 2) if il else (0, 1, 2, 3)))
+        f, c, h, w = chw(lr, lr_hwc)
+        scale, n_seq = int(scale), int(n_seq)
+        if scale < 1:
+            raise ValueError(f"FramePairs: scale {scale}")
+        if hr is not None and chw(hr, hr_hwc) != (f, c, scale * h, scale * w):
+            raise ValueError(f"FramePairs: hr must be scale {scale} x lr {(f, c, h, w)} = {(f, c, scale * h, scale * w)}, got {chw(hr, hr_hwc)}")
+        if n_seq < 1 or f == 0 or f % n_seq != 0:
+            raise ValueError(f"FramePairs: {f} frames are not whole scenes of n_seq {n_seq}")
+        if names is not None and len(names) != f:
+            raise ValueError(f"FramePairs: {len(names)} names for {f} frames")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        put = lambda x, il: (x.to(dev).permute(0, 3, 1, 2) if il else x.to(dev)).contiguous()
+        self.lr = put(lr, lr_hwc)
+        self.hr = put(hr, hr_hwc) if hr is not None else None
+        self.scale, self.n_seq = scale, n_seq
+        self.names = list(names) if names is not None else [default_name(i, n_seq) for i in range(f)]
+
+    @classmethod
+    def from_files(cls, lr_paths: Sequence[str], hr_paths: Optional[Sequence[str]], scale: int, n_seq: int,
+                   names: Optional[Sequence[str]] = None, device=None, reader=harness.read_png) -> "FramePairs":
+        """Read one file per frame.  `reader(path)` returns a uint8 (C, H, W) tensor or array; the default, `harness.read_png`, is
+        a pure-Python decoder and SLOW (seconds per full-size frame) -- pass your own (an imageio / cv2 / PIL wrapper returning
+        CHW bytes) for a real dataset.  Decoding speed is not this module's business; the store is built once."""
+        if hr_paths is not None and len(hr_paths) != len(lr_paths):
+            raise ValueError(f"FramePairs.from_files: {len(lr_paths)} LR and {len(hr_paths)} HR files")
+        read = lambda paths: torch.stack([torch.as_tensor(np.asarray(reader(p))) for p in paths])
+        return cls(read(lr_paths), read(hr_paths) if hr_paths is not None else None, scale, n_seq, names=names, device=device)
+
+    def __len__(self) -> int:
+        return int(self.lr.shape[0])
+
+    @property
+    def frame_size(self) -> Tuple[int, int]:
+        return int(self.lr.shape[2]), int(self.lr.shape[3])
+
+    @property
+    def device(self) -> torch.device:
+        return self.lr.device
+
+
+class TrainBatches:
+    """The training loader: iterating yields one epoch's `{'lr_seq': (n, t, C, p, p), 'hr_seq': (n, t, C, s p, s p), 'fname': [n
+    names]}`, fp32 on the store's device, each from one `ops.gather_pairs` launch.  `set_epoch(e)` draws epoch e's plan
+    (`epoch_plan`), checks it (`check_plan`) and uploads it once; the same (seed, epoch) gives the same batches on every run.
+
+    rank / world default to torch.distributed's when it is initialised (else 0 / 1).  `out=(lr, hr)`: gather every batch into
+    these buffers (`GraphedTrainStep.static_lr` / `static_hr`: the batch then needs no copy and `step()` is called without one);
+    the yielded tensors are those buffers, overwritten by the next batch.  Without it every batch is newly allocated."""
+
+    def __init__(self, store: FramePairs, batch_size: int, patch_size: int, n_frame: int, seed: int = 0, rank: Optional[int] = None,
+                 world: Optional[int] = None, out=None):
+        if store.hr is None:
+            raise ValueError("TrainBatches: the store has no HR frames")
+        import torch.distributed as dist
+        if rank is None or world is None:
+            live = dist.is_available() and dist.is_initialized()
+            rank = (dist.get_rank() if live else 0) if rank is None else rank
+            world = (dist.get_world_size() if live else 1) if world is None else world
+        self.store, self.batch_size, self.patch_size, self.n_frame = store, int(batch_size), int(patch_size), int(n_frame)
+        self.seed, self.rank, self.world, self.out = int(seed), int(rank), int(world), out
+        self.epoch = None
+        self.set_epoch(0)
+
+    def set_epoch(self, epoch: int) -> None:
+        s = self.store
+        ih, iw = s.frame_size
+        frames, desc, names = epoch_plan(len(s), self.n_frame, s.n_seq, self.batch_size, ih, iw, self.patch_size, self.seed, epoch,
+                                         self.rank, self.world, s.names)
+        check_plan(frames, desc, len(s), ih, iw, self.patch_size)
+        self.epoch, self.names = int(epoch), names
+        self.frames = torch.from_numpy(frames).to(s.device)
+        self.desc = torch.from_numpy(desc).to(s.device)
+
+    def __len__(self) -> int:
+        return int(self.frames.shape[0])
+
+    def __iter__(self) -> Iterator[Dict]:
+        from . import ops
+        s = self.store
+        for b in range(len(self)):
+            lr, hr = ops.gather_pairs(s.lr, s.hr, self.frames[b], self.desc[b], self.patch_size, s.scale, out=self.out)
+            yield {"lr_seq": lr, "hr_seq": hr, "fname": self.names[b]}
+
+
+def _items(store: FramePairs, windows: List[List[int]], top: int, left: int, patch) -> Iterator[Dict]:
+    from . import ops
+    ih, iw = store.frame_size
+    frames = np.asarray(windows, np.int32).reshape(len(windows), 1, -1)
+    desc = np.zeros((len(windows), 1, 4), np.int32)
+    desc[..., 0], desc[..., 1] = top, left
+    check_plan(frames, desc, len(store), ih, iw, patch)
+    frames_dev, desc_dev = torch.from_numpy(frames).to(store.device), torch.from_numpy(desc).to(store.device)
+    for i, win in enumerate(windows):
+        lr, hr = ops.gather_pairs(store.lr, store.hr, frames_dev[i], desc_dev[i], patch, store.scale, may_transpose=False)
+        item = {"lr_seq": lr, "fname": [store.names[k] for k in win]}
+        if hr is not None:
+            item["hr_seq"] = hr
+        yield item
+
+
+def val_items(store: FramePairs, n_frame: int, p: int = 256) -> Iterator[Dict]:
+    """The validation items (`_getitem_val`, realvsr_dataset.py:96-128): for every frame the mirrored window around it
+    (`harness.train_window`), centre-cropped to p x p LR / scale p x scale p HR as `harness.crop_center` does, no flips, batch 1 --
+    what `harness.evaluate` consumes.  'fname' names every frame of the window (the per-frame report needs one each; the reference
+    carries a single name).  The HR crop's origin is scale x the LR crop's, which is the centre crop of the HR frame only when
+    h - p and w - p are even: ValueError otherwise."""
+    ih, iw = store.frame_size
+    if p > ih or p > iw:
+        raise ValueError(f"val_items: a {p} x {p} crop does not fit the {ih} x {iw} frames")
+    if (ih - p) % 2 or (iw - p) % 2:
+        raise ValueError(f"val_items: {ih} x {iw} frames minus a crop of {p} leave an odd margin: the HR centre crop is not scale x the LR one")
+    windows = [harness.train_window(i, i % store.n_seq, n_frame, store.n_seq) for i in range(len(store))]
+    return _items(store, windows, (ih - p) // 2, (iw - p) // 2, p)
+
+
+def test_items(store: FramePairs, n_frame: int) -> Iterator[Dict]:
+    """The test items (`_getitem_test`, realvsr_dataset.py:130-147): every scene cut into n_seq / n_frame non-overlapping windows
+    (`harness.test_window_starts`), full frames, no flips, batch 1, 'fname' the window's frame names."""
+    starts = harness.test_window_starts(len(store), store.n_seq, n_frame)
+    return _items(store, [list(range(s0, s0 + n_frame)) for s0 in starts], 0, 0, store.frame_size)
+
+
+test_items.__test__ = False      # a name pytest would otherwise collect when a test module imports it

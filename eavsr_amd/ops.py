@@ -1524,6 +1524,69 @@ def u8_to_f32(frames: Tensor, hwc: Optional[bool] = None) -> Tensor:
     return out
 
 
+def gather_pairs(lr_store: Tensor, hr_store: Optional[Tensor], frames: Tensor, desc: Tensor, patch, scale: int, out=None,
+                 may_transpose: bool = True):
+    """One launch builds a batch from device-resident 8-bit frames (csrc/batch.hip): the reference's training item -- window, crop,
+    hflip / vflip / transpose, `np.float32(img) / 255` (data/realvsr_dataset.py:62-94, util/util.py:223-248) -- for LR and HR together.
+
+    lr_store (F, C, h, w) and hr_store (F, C, scale h, scale w) uint8 (hr_store None: LR only); frames (n, t) int32 indices into F;
+    desc (n, 4) int32 = top, left, flags, 0 in LR pixels, flags bit 0 hflip, bit 1 vflip, bit 2 transpose; `patch` the LR patch size,
+    an int or (ph, pw).  frames / desc are read on the device (the launch is graph-capturable; overwrite them in place between
+    replays), so their CONTENTS are not checked here: the kernel clamps what is out of range, `dataset.check_plan` validates a plan
+    on the host.  `may_transpose=False` promises that no sample carries the transpose flag and lifts the square-patch requirement
+    (the kernel ignores the flag when ph != pw).  `out=(lr_out, hr_out)`: fp32 contiguous buffers of the result's shapes to write
+    into (GraphedTrainStep.static_lr / static_hr); nothing is allocated then.  Returns (lr (n, t, C, ph, pw), hr (n, t, C, s ph,
+    s pw) or None), every sample float(v) / 255.0f as an IEEE division."""
+    for nm, v in (("lr_store", lr_store), ("frames", frames), ("desc", desc)) + ((("hr_store", hr_store),) if hr_store is not None else ()):
+        if not isinstance(v, torch.Tensor):
+            raise TypeError(f"gather_pairs: {nm}: expected a tensor, got {type(v)}")
+        if not v.is_cuda:
+            raise RuntimeError(f"gather_pairs: {nm} is on {v.device}; eavsr_amd runs on the GPU only (no CPU path)")
+        if v.device != lr_store.device:
+            raise ValueError(f"gather_pairs: {nm} is on {v.device}, lr_store on {lr_store.device}")
+    ph, pw = (int(patch), int(patch)) if isinstance(patch, int) else (int(patch[0]), int(patch[1]))
+    s = int(scale)
+    if lr_store.dtype != torch.uint8 or lr_store.dim() != 4:
+        raise ValueError(f"gather_pairs: lr_store: a uint8 (F, C, h, w) tensor, got {lr_store.dtype} {tuple(lr_store.shape)}")
+    F_, c, h, w = (int(v) for v in lr_store.shape)
+    if hr_store is not None and (hr_store.dtype != torch.uint8 or tuple(hr_store.shape) != (F_, c, s * h, s * w)):
+        raise ValueError(f"gather_pairs: hr_store: uint8 {(F_, c, s * h, s * w)} (scale {s} x the LR store {tuple(lr_store.shape)}), got "
+                         f"{hr_store.dtype} {tuple(hr_store.shape)}")
+    if s < 1 or ph < 1 or pw < 1 or ph > h or pw > w:
+        raise ValueError(f"gather_pairs: patch {ph} x {pw} (scale {s}) does not fit the {h} x {w} frames")
+    if may_transpose and ph != pw:
+        raise ValueError(f"gather_pairs: the transpose flag needs a square patch, got {ph} x {pw} (may_transpose=False: no sample carries it)")
+    if frames.dtype != torch.int32 or frames.dim() != 2 or desc.dtype != torch.int32 or tuple(desc.shape) != (frames.shape[0], 4):
+        raise ValueError(f"gather_pairs: frames int32 (n, t) and desc int32 (n, 4), got {frames.dtype} {tuple(frames.shape)} / "
+                         f"{desc.dtype} {tuple(desc.shape)}")
+    n, t = (int(v) for v in frames.shape)
+    if t < 1 or F_ < 1:
+        raise ValueError(f"gather_pairs: no frames (store of {F_}, windows of {t})")
+    if not (lr_store.is_contiguous() and frames.is_contiguous() and desc.is_contiguous() and (hr_store is None or hr_store.is_contiguous())):
+        raise ValueError("gather_pairs: stores and index tensors must be contiguous (nothing is copied here)")
+    shapes = [(n, t, c, ph, pw), (n, t, c, s * ph, s * pw)]
+    if out is not None:
+        lr_out, hr_out = out
+        for nm, o, shp in (("lr", lr_out, shapes[0]), ("hr", hr_out, shapes[1])):
+            if o is None and nm == "hr" and hr_store is None:
+                continue
+            if (not isinstance(o, torch.Tensor) or o.dtype != torch.float32 or tuple(o.shape) != shp or not o.is_contiguous()
+                    or o.device != lr_store.device):
+                raise ValueError(f"gather_pairs: out[{nm}]: a contiguous fp32 {shp} tensor on {lr_store.device}, got "
+                                 f"{getattr(o, 'dtype', type(o))} {tuple(getattr(o, 'shape', ()))}")
+        if hr_store is None:
+            hr_out = None
+    else:
+        lr_out = torch.empty(shapes[0], device=lr_store.device, dtype=torch.float32)
+        hr_out = torch.empty(shapes[1], device=lr_store.device, dtype=torch.float32) if hr_store is not None else None
+    st = _stream(lr_store)
+    samples = lr_out.numel() + (hr_out.numel() if hr_out is not None else 0)
+    _launch("gather_pairs_u8", 0.0, 5.0 * samples, lr_store,
+            lambda: lib().eavsr_gather_pairs_u8(_p(lr_store), _p(hr_store) if hr_store is not None else None, _p(frames), _p(desc), _p(lr_out),
+                                                _p(hr_out) if hr_out is not None else None, F_, n, t, c, h, w, s, ph, pw, st), "gather_pairs")
+    return lr_out, hr_out
+
+
 # ------------------------------------------------------------------------------------------
 # LPIPS (AlexNet), the report's third column  (psnr_total.py:27-35; csrc/lpips.hip)
 # ------------------------------------------------------------------------------------------

@@ -730,6 +730,22 @@ int eavsr_rgb8_f32(const float* sr, float scale, int32_t F, int32_t C, int32_t H
  * (hwc = 1, C must be 3) -> out fp32 (F, C, H, W), every sample float(v) / 255.0f as an IEEE division.  `in` may have any
  * alignment; out must be 16-byte aligned (-2 otherwise).  NULL pointer: -1; F > 65535, bad dims or layout: -2. */
 int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t H, int32_t W, int32_t hwc, void* stream);
+/* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
+ * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
+ * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
+ *   lr_store (F, C, h, w) uint8; hr_store (F, C, s h, s w) uint8, or NULL together with hr_out: LR only; both 4-byte aligned.
+ *   frames (n, t) int32 indices into F; desc (n, 4) int32 = top, left, flags, 0 in LR pixels (the HR origin is s x the LR one);
+ *   flags bit 0 hflip, bit 1 vflip, bit 2 transpose, applied in that order.  Both are DEVICE memory, read by the kernel: a captured
+ *   launch replays with whatever they hold then.
+ *   lr_out (n, t, C, ph, pw), hr_out (n, t, C, s ph, s pw) fp32, 16-byte aligned.  With (r, q) = (x, y) if transposed, else (y, x):
+ *     out[c, y, x] = float(crop[c, vflip ? P-1-r : r, hflip ? P-1-q : q]) / 255.0f, an IEEE division as eavsr_u8_to_f32.
+ * The kernel clamps every frame index into [0, F) and every origin into [0, h - ph] x [0, w - pw], and ignores the transpose bit
+ * when ph != pw: whatever frames / desc hold, it reads inside the stores and writes inside the outputs.  Callers validate their
+ * plans on the host (eavsr_amd/dataset.py check_plan).
+ * NULL pointer: -1; bad dims, a patch larger than the frame, s h or s w > 32768, n t C > 65535, misaligned pointers: -2. */
+int eavsr_gather_pairs_u8(const uint8_t* lr_store, const uint8_t* hr_store, const int32_t* frames, const int32_t* desc, float* lr_out,
+                          float* hr_out, int32_t F, int32_t n, int32_t t, int32_t C, int32_t h, int32_t w, int32_t s, int32_t ph,
+                          int32_t pw, void* stream);
 /* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
  * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
  * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
