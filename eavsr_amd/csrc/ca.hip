@@ -547,7 +547,7 @@ extern "C" int eavsr_scale_residual_f32(const float* r, const float* scale, cons
                                         int32_t c, int32_t hw, void* stream) {
   EAVSR_REQUIRE(r && scale && x && out, -1, "scale_residual: NULL pointer");
   EAVSR_REQUIRE(n >= 0 && c >= 0 && hw > 0, -1, "scale_residual: bad dims");
-  EAVSR_REQUIRE((long)n * c <= 65535, -1, "scale_residual: n*c too large");
+  EAVSR_REQUIRE((long)n * c <= 65535, -1, "scale_residual: n*c = %ld planes, at most 65535 per launch", (long)n * c);
   if (n * c == 0) return 0;
   const bool vec = (hw % 4) == 0 && (((uintptr_t)r | (uintptr_t)x | (uintptr_t)out) & 15) == 0;
   const int work = vec ? hw / 4 : hw;

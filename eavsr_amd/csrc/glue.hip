@@ -66,7 +66,8 @@ __global__ __launch_bounds__(256) void concat3_kernel(const float* __restrict__ 
 extern "C" int eavsr_normalize_f32(const float* in, const float* mean, const float* stdv, float* out, int32_t n, int32_t c,
                                    int32_t hw, void* stream) {
   EAVSR_REQUIRE(in && mean && stdv && out, -1, "normalize: NULL pointer");
-  EAVSR_REQUIRE(n >= 0 && c > 0 && hw > 0 && (long)n * c <= 65535, -1, "normalize: bad dims");
+  EAVSR_REQUIRE(n >= 0 && c > 0 && hw > 0, -1, "normalize: bad dims");
+  EAVSR_REQUIRE((long)n * c <= 65535, -1, "normalize: n*c = %ld planes, at most 65535 per launch", (long)n * c);
   if (n == 0) return 0;
   int bx = eavsr::cdiv(hw, 256);
   if (bx > 256) bx = 256;
@@ -76,7 +77,8 @@ extern "C" int eavsr_normalize_f32(const float* in, const float* mean, const flo
 
 extern "C" int eavsr_avg_pool2_f32(const float* in, float* out, int32_t nc, int32_t h, int32_t w, void* stream) {
   EAVSR_REQUIRE(in && out, -1, "avg_pool2: NULL pointer");
-  EAVSR_REQUIRE(nc >= 0 && h > 0 && w > 0 && nc <= 65535, -1, "avg_pool2: bad dims");
+  EAVSR_REQUIRE(nc >= 0 && h > 0 && w > 0, -1, "avg_pool2: bad dims");
+  EAVSR_REQUIRE(nc <= 65535, -1, "avg_pool2: n*c = %d planes, at most 65535 per launch", nc);
   EAVSR_REQUIRE(h % 2 == 0 && w % 2 == 0, -2, "avg_pool2: h=%d w=%d must be even", h, w);
   if (nc == 0) return 0;
   dim3 grid(eavsr::cdiv(w / 2, 64), eavsr::cdiv(h / 2, 4), nc), block(64, 4, 1);
@@ -87,7 +89,8 @@ extern "C" int eavsr_avg_pool2_f32(const float* in, float* out, int32_t nc, int3
 extern "C" int eavsr_resize_bilinear_f32(const float* in, float* out, int32_t n, int32_t c, int32_t hin, int32_t win,
                                          int32_t hout, int32_t wout, int32_t cmul, float m0, float m1, void* stream) {
   EAVSR_REQUIRE(in && out, -1, "resize_bilinear: NULL pointer");
-  EAVSR_REQUIRE(n >= 0 && c >= 0 && hin > 0 && win > 0 && hout > 0 && wout > 0 && (long)n * c <= 65535, -1, "resize_bilinear: bad dims");
+  EAVSR_REQUIRE(n >= 0 && c >= 0 && hin > 0 && win > 0 && hout > 0 && wout > 0, -1, "resize_bilinear: bad dims");
+  EAVSR_REQUIRE((long)n * c <= 65535, -1, "resize_bilinear: n*c = %ld planes, at most 65535 per launch", (long)n * c);
   EAVSR_REQUIRE(cmul == 0 || cmul == c, -1, "resize_bilinear: cmul %d must be 0 or the channel count %d", cmul, c);
   if (n * c == 0) return 0;
   const float rh = (float)hin / (float)hout, rw = (float)win / (float)wout;      // ATen: area_pixel_compute_scale without a scale factor
@@ -100,7 +103,8 @@ extern "C" int eavsr_resize_bilinear_f32(const float* in, float* out, int32_t n,
 extern "C" int eavsr_concat3_f32(const float* a, int32_t ca, const float* b, int32_t cb, const float* c, int32_t cc, float* out,
                                  int32_t n, int32_t hw, void* stream) {
   EAVSR_REQUIRE(a && b && c && out, -1, "concat3: NULL pointer");
-  EAVSR_REQUIRE(n >= 0 && ca > 0 && cb > 0 && cc > 0 && hw > 0 && (long)n * (ca + cb + cc) <= 65535, -1, "concat3: bad dims");
+  EAVSR_REQUIRE(n >= 0 && ca > 0 && cb > 0 && cc > 0 && hw > 0, -1, "concat3: bad dims");
+  EAVSR_REQUIRE((long)n * (ca + cb + cc) <= 65535, -1, "concat3: n*c = %ld planes, at most 65535 per launch", (long)n * (ca + cb + cc));
   if (n == 0) return 0;
   int bx = eavsr::cdiv(hw, 256);
   if (bx > 64) bx = 64;

@@ -86,7 +86,7 @@ extern "C" int eavsr_resize_bilinear_ac_f32(const float* in, const float* in2, c
                                             int32_t wout, float scale, void* stream) {
   EAVSR_REQUIRE(in && out, -1, "resize_bilinear_ac: NULL pointer");
   EAVSR_REQUIRE(n >= 0 && c >= 0 && hin > 0 && win > 0 && hout > 0 && wout > 0, -1, "resize_bilinear_ac: bad dims");
-  EAVSR_REQUIRE((long)n * c <= 65535, -1, "resize_bilinear_ac: n*c too large");
+  EAVSR_REQUIRE((long)n * c <= 65535, -1, "resize_bilinear_ac: n*c = %ld planes, at most 65535 per launch", (long)n * c);
   if (n * c == 0) return 0;
   const float rh = hout > 1 ? (float)(hin - 1) / (float)(hout - 1) : 0.f;
   const float rw = wout > 1 ? (float)(win - 1) / (float)(wout - 1) : 0.f;

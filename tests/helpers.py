@@ -123,3 +123,23 @@ def filled(shapes, preset="default", seed=0):
 
 def maxabs(a, b):
     return (a.double() - b.double()).abs().max().item()
+
+
+def restate_pairs(store, frames, desc, ph, pw, s=1):
+    """the training item of the reference restated in numpy (crop -> [:, :, ::-1] -> [:, ::-1, :] -> transpose(0, 2, 1) ->
+    np.float32(.) / 255; data/realvsr_dataset.py:166-175, util/util.py:223-227), what ops.gather_pairs is compared with:
+    store (F, C, H, W) uint8 ndarray at resolution s x LR; frames (n, t), desc (n, 4) in LR pixels -> (n, t, C, s ph, s pw) fp32"""
+    n, t = frames.shape
+    out = np.empty((n, t, store.shape[1], s * ph, s * pw), np.float32)
+    for i in range(n):
+        top, left, flags = (int(v) for v in desc[i, :3])
+        for j in range(t):
+            img = store[frames[i, j]][..., s * top:s * (top + ph), s * left:s * (left + pw)]
+            if flags & 1:
+                img = img[:, :, ::-1]
+            if flags & 2:
+                img = img[:, ::-1, :]
+            if flags & 4:
+                img = img.transpose(0, 2, 1)
+            out[i, j] = np.float32(np.ascontiguousarray(img)) / 255
+    return out

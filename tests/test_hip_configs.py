@@ -264,9 +264,18 @@ def test_config4_mid_size_fp16_backbone_psnr_against_the_cpu_oracle(cuda):
 def test_config4_full_size_long_sequence_fp16(cuda):
     """BASELINE.json configs[4] at full size, 1 x 15 x 3 x 540 x 960 -> 2160 x 3840: too large for the CPU oracle, so
     size-independent properties: finite output of the right shape, the fp16-backbone forward within 60 dB PSNR of the
-    exact fp32 forward of the same kernels, peak HBM logged (it must fit one 288 GB MI355X with room to spare)."""
+    exact fp32 forward of the same kernels, peak HBM logged (it must fit one 288 GB MI355X with room to spare).
+
+    The fp16-versus-fp32 comparison shares the encoder, the glue and the tail between its two sides, so an offset that wraps in
+    them (the tail's 15 x 256 x 540 x 960 tensor is 7.96 GB, past 2^32 bytes) would pass it.  The independent anchor: the encoder
+    and `EAVSRP.upsample` run once more on all 15 full-size frames, and frames 0 and 14 are compared with the CPU oracle, by the
+    method and under the bound of tests/test_hip_model.py::test_encoder_and_upsampling_tail_vs_oracle (seeded branch features,
+    1e-4 max(1, |ref|max)).  Not on a 64 x 96 crop: the reconstruction backbone's channel attention averages over the whole plane,
+    so a crop of the full-size result is not the result of the crop; the oracle instead does the two frames at the full 540 x 960,
+    one frame at a time, which it affords."""
     from eavsr_amd import networks as Nw
-    net, _ = _net(cuda)
+    from eavsr_amd import ops
+    net, sd = _net(cuda)
     clip = _clip(1, 15, 540, 960, seed=4).to(cuda)
     torch.cuda.reset_peak_memory_stats()
     with torch.no_grad():
@@ -290,6 +299,30 @@ def test_config4_full_size_long_sequence_fp16(cuda):
     assert peak32 < 200 * 2 ** 30, peak32
     print(f"configs[4] 1x15x3x540x960: fp16-vs-fp32 PSNR {psnr:.1f} dB, max diff {maxd:.2e}; peak HBM fp32 "
           f"{peak32 / 2 ** 30:.1f} GiB, fp16 backbone {peak16 / 2 ** 30:.1f} GiB")
+    del y16, y32
+    torch.cuda.empty_cache()
+    x = clip[0]                                                  # (15, 3, 540, 960): n = 1, frame-major
+    with torch.no_grad():
+        f = net.encoder(x)
+    for i in (0, 14):
+        ref_f = O.encoder(sd, "encoder.", x[i:i + 1].cpu())
+        err = H.maxabs(f[i:i + 1].cpu(), ref_f)
+        print(f"configs[4] full size, encoder frame {i}: max|hip - oracle| = {err:.3e} (|ref|max {ref_f.abs().max().item():.3f})")
+        assert err <= 1e-4 * max(1.0, ref_f.abs().max().item()), (i, err)
+    del f
+    g = torch.Generator(device=cuda).manual_seed(44)
+    names = ["spatial", "backward_1", "forward_1", "backward_2", "forward_2"]
+    feats = {k: [torch.randn(1, 64, 540, 960, device=cuda, generator=g) * 0.5 for _ in range(15)] for k in names}
+    with torch.no_grad(), ops.profile() as prof:
+        y = net.upsample(clip, feats)
+    ran = set(prof.summary())
+    assert tuple(y.shape) == (1, 15, 3, 2160, 3840)
+    assert "conv3x3_64to256_wino4" in ran and "conv3x3_320to64_wino4" in ran, ran
+    for i in (0, 14):
+        ref = O.upsample(sd, clip[:, i:i + 1].cpu(), {k: [v[i].cpu()] for k, v in feats.items()}, 4)
+        err = H.maxabs(y[:, i:i + 1].cpu(), ref)
+        print(f"configs[4] full size, tail frame {i}: max|hip - oracle| = {err:.3e} (|ref|max {ref.abs().max().item():.3f})")
+        assert err <= 1e-4 * max(1.0, ref.abs().max().item()), (i, err)
 
 
 # ---------------------------------------------------------------------------------------------------------- configs[2]

@@ -1,6 +1,6 @@
 """The device-resident training data on the GPU (`pytest -m gpu`): ops.gather_pairs (csrc/batch.hip) and eavsr_amd/dataset.py.
 
-The expected value everywhere is `_restate`, a numpy restatement of the reference's item written for this file, in the reference's
+The expected value everywhere is `_restate` (tests/helpers.py restate_pairs), a numpy restatement of the reference's item, in the reference's
 order: crop -> [:, :, ::-1] -> [:, ::-1, :] -> transpose(0, 2, 1) -> np.float32(.) / 255 (data/realvsr_dataset.py:166-175,
 util/util.py:223-227).  The comparison is torch.equal, bit for bit: bytes in, one correctly rounded division out -- there is no
 tolerance to choose."""
@@ -11,26 +11,9 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.helpers import restate_pairs as _restate
 
 pytestmark = pytest.mark.gpu
-
-
-def _restate(store, frames, desc, ph, pw, s=1):
-    """store (F, C, H, W) uint8 ndarray at resolution s x LR; frames (n, t), desc (n, 4) in LR pixels -> (n, t, C, s ph, s pw) fp32"""
-    n, t = frames.shape
-    out = np.empty((n, t, store.shape[1], s * ph, s * pw), np.float32)
-    for i in range(n):
-        top, left, flags = (int(v) for v in desc[i, :3])
-        for j in range(t):
-            img = store[frames[i, j]][..., s * top:s * (top + ph), s * left:s * (left + pw)]
-            if flags & 1:
-                img = img[:, :, ::-1]
-            if flags & 2:
-                img = img[:, ::-1, :]
-            if flags & 4:
-                img = img.transpose(0, 2, 1)
-            out[i, j] = np.float32(np.ascontiguousarray(img)) / 255
-    return out
 
 
 def _stores(F, C, h, w, s, seed):
