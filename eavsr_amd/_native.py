@@ -194,6 +194,8 @@ SIGNATURES = {
     "eavsr_u8_to_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
+    # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)
+    "eavsr_resize_cubic_u8": (C.c_int, [vp] * 6 + [i32] * 6 + [vp]),
     # LPIPS (AlexNet), the report's third column (csrc/lpips.hip; additions to ABI 32)
     "eavsr_lpips_conv_weight_elems": (C.c_int64, [i32, i32, i32]),
     "eavsr_lpips_pack_conv_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),

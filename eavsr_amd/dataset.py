@@ -15,13 +15,18 @@ without a GPU.  An epoch's plan is two small int32 arrays, uploaded once.
 Zero-copy variant: `TrainBatches(..., out=(step.static_lr, step.static_hr))` gathers straight into the captured graph's input
 buffers; iterate and call `step.step()` with no batch.
 
-Out of scope here: producing LR frames from HR (the reference's cv2.resize at load time; LR frames are supplied), file lists and
-option parsing, a host-memory store, random numbers on the device.
+LR frames are either supplied, or made on the device from the full-size "wide" frames as the reference's loaders make them
+(`cv2.resize(img, (w // scale, h // scale), interpolation=cv2.INTER_CUBIC)`, data/mvsr4x_dataset.py:192-201,
+data/realvsr_dataset.py:200): `FramePairs.from_wide` / `from_wide_files`, `ops.resize_cubic_u8` (csrc/resize_cubic.hip) with the
+tables of `cubic_tables`, which restates OpenCV's 8-bit fixed-point path; OpenCV itself is not needed.
+
+Out of scope here: file lists and option parsing, a host-memory store, random numbers on the device.
 """
 from __future__ import annotations
 
+import functools
 import random
-from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -110,6 +115,56 @@ def check_plan(frames, desc, n_items: int, ih: int, iw: int, patch) -> None:
         raise ValueError(f"check_plan: the transpose flag needs a square patch, got {ph} x {pw}")
 
 
+CUBIC_MAX_RATIO = 8
+
+
+@functools.lru_cache(maxsize=64)
+def _cubic_tables(src: int, dst: int):
+    scale = 1.0 / (dst / src)                                   # float64; OpenCV inverts the inverse scale
+    d = np.arange(dst, dtype=np.float64)
+    f = ((d + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f)
+    x = (f - s).astype(np.float32)                              # float32 - float32 (s is integral and exact)
+    one, A = np.float32(1), np.float32(-0.75)
+    A2, A3, A4, A5, A8 = A + np.float32(2), A + np.float32(3), np.float32(4) * A, np.float32(5) * A, np.float32(8) * A
+    x1, xm = x + one, one - x
+    c = np.empty((dst, 4), np.float32)
+    c[:, 0] = ((A * x1 - A5) * x1 + A8) * x1 - A4
+    c[:, 1] = (A2 * x - A3) * x * x + one
+    c[:, 2] = (A2 * xm - A3) * xm * xm + one
+    c[:, 3] = one - c[:, 0] - c[:, 1] - c[:, 2]
+    coef = np.clip(np.rint(c * np.float32(2048)), -32768, 32767).astype(np.int16)
+    ofs = s.astype(np.int32)
+    ofs.setflags(write=False)
+    coef.setflags(write=False)
+    return ofs, coef
+
+
+def cubic_tables(src: int, dst: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One axis of OpenCV's `resize` for CV_8U, INTER_CUBIC, from `src` samples to `dst`: (ofs int32[dst], coef int16[dst, 4]), both
+    read-only (cached per (src, dst)).  Output d reads the source samples ofs[d] - 1 .. ofs[d] + 2, each index clamped into
+    [0, src - 1] (replicate border), with the weights coef[d] / 2048:
+
+        scale = 1.0 / (dst / src) in float64;  f = float32((d + 0.5) * scale - 0.5);  ofs = floor(f);  x = float32(f - ofs)
+        with A = -0.75f, in float32, left to right, every operation rounded (no FMA):
+          c0 = ((A*(x+1) - 5*A)*(x+1) + 8*A)*(x+1) - 4*A;   c1 = ((A+2)*x - (A+3))*x*x + 1
+          c2 = ((A+2)*(1-x) - (A+3))*(1-x)*(1-x) + 1;       c3 = 1 - c0 - c1 - c2
+        coef[d][j] = saturate_int16(round_half_even(c_j * 2048))
+
+    The four weights are NOT corrected to sum to 2048 (2047 or 2049 at some positions, e.g. 70 -> 17); OpenCV does not either.  The
+    image: hor = sum_j coefx * src (int32, exact), v = sum_j coefy * hor (int32), out = clamp((v + 2^21) >> 22, 0, 255): the
+    scalar C++ path of OpenCV, which rounds exact ties up; a SIMD build's vertical pass rounds them to even instead.
+    Built on the host: inside a kernel the compiler would contract a*b+c into an FMA and could move a weight by one.
+
+    ValueError for dst < 1 and for a ratio src / dst outside [1, 8] (no upscaling; the bound limits the kernel's footprint)."""
+    src, dst = int(src), int(dst)
+    if dst < 1:
+        raise ValueError(f"cubic_tables: {src} -> {dst}: at least one output sample")
+    if src < dst or src > CUBIC_MAX_RATIO * dst:
+        raise ValueError(f"cubic_tables: {src} -> {dst}: the ratio src / dst must be in [1, {CUBIC_MAX_RATIO}] (no upscaling)")
+    return _cubic_tables(src, dst)
+
+
 def _as_u8_frames(x, what: str) -> torch.Tensor:
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint8:
@@ -166,6 +221,68 @@ class FramePairs:
             raise ValueError(f"FramePairs.from_files: {len(lr_paths)} LR and {len(hr_paths)} HR files")
         read = lambda paths: torch.stack([torch.as_tensor(np.asarray(reader(p))) for p in paths])
         return cls(read(lr_paths), read(hr_paths) if hr_paths is not None else None, scale, n_seq, names=names, device=device)
+
+    @classmethod
+    def _from_wide_chunks(cls, what: str, n: int, get: Callable[[int, int], torch.Tensor], hr, scale: int, n_seq: int, names,
+                          device, chunk: int) -> "FramePairs":
+        """`get(lo, hi)`: wide frames [lo, hi) as uint8 (hi - lo, C, H, W) or (hi - lo, H, W, C), anywhere.  Every check runs on
+        the first chunk's shape, before anything is moved to the device."""
+        scale, n_seq, chunk = int(scale), int(n_seq), int(chunk)
+        if scale < 1 or scale > CUBIC_MAX_RATIO:
+            raise ValueError(f"{what}: scale {scale} must be in [1, {CUBIC_MAX_RATIO}]")
+        if chunk < 1:
+            raise ValueError(f"{what}: chunk {chunk}")
+        if n_seq < 1 or n == 0 or n % n_seq != 0:
+            raise ValueError(f"{what}: {n} frames are not whole scenes of n_seq {n_seq}")
+        if names is not None and len(names) != n:
+            raise ValueError(f"{what}: {len(names)} names for {n} frames")
+        chw = lambda x: tuple(int(x.shape[i]) for i in ((0, 3, 1, 2) if _interleaved(x) else (0, 1, 2, 3)))
+        first = _as_u8_frames(get(0, min(chunk, n)), "wide")
+        _, c, H, W = chw(first)
+        if hr is not None and chw(hr) != (n, c, H, W):
+            raise ValueError(f"{what}: wide and hr frames must have the same size: wide {(n, c, H, W)}, hr {chw(hr)}")
+        if H % scale or W % scale:
+            raise ValueError(f"{what}: H % scale == 0 and W % scale == 0 is required (the store holds hr = scale x lr exactly; nothing "
+                             f"is cropped here): {H} x {W} frames, scale {scale}")
+        from . import ops
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        lr = torch.empty((n, c, H // scale, W // scale), device=dev, dtype=torch.uint8)
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            part = first if lo == 0 else _as_u8_frames(get(lo, hi), "wide")
+            if chw(part) != (hi - lo, c, H, W):
+                raise ValueError(f"{what}: wide frames {lo}..{hi - 1} are {chw(part)[1:]}, the first ones {(c, H, W)}")
+            part = part.to(dev, non_blocking=True)
+            part = (part.permute(0, 3, 1, 2) if _interleaved(part) else part).contiguous()
+            ops.resize_cubic_u8(part, (H // scale, W // scale), out=lr[lo:hi])
+        return cls(lr, hr, scale, n_seq, names=names, device=dev)
+
+    @classmethod
+    def from_wide(cls, wide, hr, scale: int, n_seq: int, names: Optional[Sequence[str]] = None, device=None,
+                  chunk: int = 16) -> "FramePairs":
+        """The store of a data set kept as the reference keeps it: `wide` frames of the SAME size as the `hr` ("tele") frames, the LR
+        frame being `cv2.resize(wide, (W // scale, H // scale), interpolation=cv2.INTER_CUBIC)` (data/mvsr4x_dataset.py:192-201,
+        data/realvsr_dataset.py:200) -- computed here on the device by `ops.resize_cubic_u8`, bit for bit as `cubic_tables` defines it.
+
+        wide, hr: uint8 (F, C, H, W) or (F, H, W, C), ndarrays or tensors, on the host or the device; hr None: an inference-only
+        store.  H % scale == 0 and W % scale == 0 (ValueError otherwise: nothing is cropped silently).  `wide` is uploaded and
+        resized `chunk` frames at a time into the preallocated LR store, so the full-size wide frames are never all on the device;
+        the result does not depend on `chunk`."""
+        wide = _as_u8_frames(wide, "wide")
+        hr = _as_u8_frames(hr, "hr") if hr is not None else None
+        return cls._from_wide_chunks("FramePairs.from_wide", int(wide.shape[0]), lambda lo, hi: wide[lo:hi], hr, scale, n_seq, names,
+                                     device, chunk)
+
+    @classmethod
+    def from_wide_files(cls, wide_paths: Sequence[str], hr_paths: Optional[Sequence[str]], scale: int, n_seq: int,
+                        names: Optional[Sequence[str]] = None, device=None, reader=harness.read_png, chunk: int = 16) -> "FramePairs":
+        """`from_wide` from one file per frame, read `chunk` wide files at a time (`reader`: see `from_files`)."""
+        if hr_paths is not None and len(hr_paths) != len(wide_paths):
+            raise ValueError(f"FramePairs.from_wide_files: {len(wide_paths)} wide and {len(hr_paths)} HR files")
+        read = lambda paths: torch.stack([torch.as_tensor(np.asarray(reader(p))) for p in paths])
+        hr = _as_u8_frames(read(hr_paths), "hr") if hr_paths is not None else None
+        return cls._from_wide_chunks("FramePairs.from_wide_files", len(wide_paths), lambda lo, hi: read(wide_paths[lo:hi]), hr, scale,
+                                     n_seq, names, device, chunk)
 
     def __len__(self) -> int:
         return int(self.lr.shape[0])

@@ -1587,6 +1587,58 @@ def gather_pairs(lr_store: Tensor, hr_store: Optional[Tensor], frames: Tensor, d
     return lr_out, hr_out
 
 
+# the device copies of `dataset.cubic_tables(src, dst)`: {(src, dst, device): (ofs int32[dst], coef int16[dst, 4])}.  Two small
+# arrays per axis length pair, a function of the sizes alone (no parameter behind them: not a WeightCache); a data set has one or
+# two pairs, so the table is simply bounded.
+_cubic_tables_dev: dict = {}
+_CUBIC_TABLES_MAX = 64
+
+
+def _cubic_tables_on(src: int, dst: int, device) -> Tuple[Tensor, Tensor]:
+    key = (src, dst, str(device))
+    hit = _cubic_tables_dev.get(key)
+    if hit is None:
+        from .dataset import cubic_tables
+        ofs, coef = cubic_tables(src, dst)                  # ValueError for a ratio outside [1, 8], before anything is launched
+        if len(_cubic_tables_dev) >= _CUBIC_TABLES_MAX:
+            _cubic_tables_dev.clear()
+        hit = _cubic_tables_dev[key] = (torch.from_numpy(ofs).to(device), torch.from_numpy(coef).to(device))
+    return hit
+
+
+def resize_cubic_u8(frames: Tensor, size: Tuple[int, int], out: Optional[Tensor] = None) -> Tensor:
+    """uint8 planes (F, C, H, W) -> uint8 (F, C, h, w), size = (h, w): `cv2.resize(img, (w, h), interpolation=cv2.INTER_CUBIC)` of
+    every plane, bit for bit as OpenCV's fixed-point path defines it (`dataset.cubic_tables`, csrc/resize_cubic.hip; DESIGN 7e also
+    says where a SIMD build of OpenCV may differ by 1 on exact ties) -- how the reference's loaders make an LR frame from the
+    full-size one.  Each axis shrinks by a ratio in [1, 8] (ValueError otherwise: no upscaling).  The tensor is taken as it is,
+    contiguous and on the device; `out`: a contiguous uint8 (F, C, h, w) tensor on the same device to write into (returned)."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"resize_cubic_u8: expected a tensor, got {type(frames)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"resize_cubic_u8: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise ValueError(f"resize_cubic_u8: a uint8 (F, C, H, W) tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise ValueError("resize_cubic_u8: frames must be contiguous (nothing is copied here)")
+    f, c, H, W = (int(v) for v in frames.shape)
+    h, w = (int(v) for v in size)
+    if min(c, H, W) < 1:
+        raise ValueError(f"resize_cubic_u8: empty planes {tuple(frames.shape)}")
+    yofs, ycoef = _cubic_tables_on(H, h, frames.device)
+    xofs, xcoef = _cubic_tables_on(W, w, frames.device)
+    if out is None:
+        out = torch.empty((f, c, h, w), device=frames.device, dtype=torch.uint8)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (f, c, h, w) or not out.is_contiguous()
+          or out.device != frames.device):
+        raise ValueError(f"resize_cubic_u8: out: a contiguous uint8 {(f, c, h, w)} tensor on {frames.device}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    st = _stream(frames)
+    _launch("resize_cubic_u8", 0.0, float(f * c) * (H * W + h * w), frames,
+            lambda: lib().eavsr_resize_cubic_u8(_p(frames), _p(out), _p(xofs), _p(xcoef), _p(yofs), _p(ycoef), f, c, H, W, h, w, st),
+            "resize_cubic_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # LPIPS (AlexNet), the report's third column  (psnr_total.py:27-35; csrc/lpips.hip)
 # ------------------------------------------------------------------------------------------

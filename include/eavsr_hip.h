@@ -746,6 +746,23 @@ int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t
 int eavsr_gather_pairs_u8(const uint8_t* lr_store, const uint8_t* hr_store, const int32_t* frames, const int32_t* desc, float* lr_out,
                           float* hr_out, int32_t F, int32_t n, int32_t t, int32_t C, int32_t h, int32_t w, int32_t s, int32_t ph,
                           int32_t pw, void* stream);
+/* ---- LR frames from full-size frames (added to ABI 32, nothing above changes) ---------------------------------------------------------
+ * The reference's `cv2.resize(img, (w, h), interpolation=cv2.INTER_CUBIC)` of an 8-bit image (data/mvsr4x_dataset.py:192-201,
+ * data/realvsr_dataset.py:200) for F x C planes, as one launch (csrc/resize_cubic.hip): OpenCV's fixed-point separable 4-tap filter.
+ *   in (F, C, H, W) uint8, any alignment; out (F, C, h, w) uint8 (one 4-byte store per 4 samples when w % 4 == 0 and out is 4-byte
+ *   aligned, byte stores otherwise).  1 <= H / h <= 8 and 1 <= W / w <= 8.
+ *   xofs int32[w], xcoef int16[w][4], yofs int32[h], ycoef int16[h][4]: DEVICE memory, built on the host (eavsr_amd/dataset.py
+ *   cubic_tables; INTEGRATION.md restates the rule): ofs = floor of the source position, coef = the taps at ofs - 1 .. ofs + 2 in units
+ *   of 1 / 2048.  ofs tables 4-byte, coef tables 8-byte aligned.
+ *     hor[y][dx]  = sum_j xcoef[dx][j] * in[y][clamp(xofs[dx] - 1 + j, 0, W - 1)]          (int32)
+ *     v           = sum_j ycoef[dy][j] * hor[clamp(yofs[dy] - 1 + j, 0, H - 1)][dx]        (int32)
+ *     out[dy][dx] = clamp((v + 2^21) >> 22, 0, 255)                                        (arithmetic shift: exact ties round up)
+ * The kernel clamps every source index into the plane and into the rectangle its workgroup staged (bounded from H / h, W / w):
+ * whatever the tables hold, it reads inside `in` and writes inside `out`.
+ * NULL pointer: -1; bad dims, a ratio outside [1, 8], H W > 2^31 - 1, F C tiles > 2^24 - 1 workgroups (a tile is 16 x 64 outputs),
+ * misaligned tables: -2.  F = 0: nothing is launched. */
+int eavsr_resize_cubic_u8(const uint8_t* in, uint8_t* out, const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs,
+                          const int16_t* ycoef, int32_t F, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, void* stream);
 /* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
  * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
  * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
