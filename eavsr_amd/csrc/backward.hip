@@ -25,12 +25,12 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
 // blockDim.x = 256 or 1024 (planes of >= 4,096 pixels: a 96 x 96 training crop is 2,304 float4 per plane -- nine dependent
 // round trips per thread of 256, one and a fraction per thread of 1,024; the launch is latency, not bandwidth)
 __global__ __launch_bounds__(1024) void plane_sum_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                         float* __restrict__ out, int hw, float scale) {
+                                                         float* __restrict__ out, int hw, float scale, int vec) {
   __shared__ float red[16];
   const size_t base = (size_t)blockIdx.x * hw;
   const int nt = blockDim.x;
   float s0 = 0.f, s1 = 0.f;
-  if ((hw & 3) == 0) {   // whole float4 groups, 16-byte aligned planes: two independent load streams per thread
+  if (vec) {   // (the entry point's test) whole float4 groups, 16-byte aligned planes: two independent load streams per thread
     const float4* a4 = reinterpret_cast<const float4*>(a + base);
     const float4* b4 = b ? reinterpret_cast<const float4*>(b + base) : nullptr;
     const int q = hw >> 2;
@@ -69,7 +69,7 @@ constexpr int CS_MAX_SEG = 8;
 struct ChanSumArgs {
   const float* av[CS_MAX_SEG];
   float* out;
-  int nseg, n, c, hw, accumulate;
+  int nseg, n, c, hw, accumulate, vec;      // vec: hw % 4 == 0 and every segment 16-byte aligned (the entry point's test)
 };
 __global__ __launch_bounds__(1024) void channel_sum_kernel(ChanSumArgs g) {
   __shared__ float red[16];
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(1024) void channel_sum_kernel(ChanSumArgs g) {
     const float* a = g.av[sg];
     for (int b = 0; b < n; ++b) {
       const float* p = a + ((size_t)b * c + ch) * hw;
-      if ((hw & 3) == 0) {
+      if (g.vec) {
         const float4* p4 = reinterpret_cast<const float4*>(p);
         const int q = hw >> 2;
         for (int i = threadIdx.x; i < q; i += 2048) {
@@ -611,7 +611,9 @@ extern "C" int eavsr_plane_sum_f32(const float* a, const float* b, float* out, i
   EAVSR_REQUIRE(a && out, -1, "plane_sum: NULL pointer");
   EAVSR_REQUIRE(nc >= 0 && hw > 0, -1, "plane_sum: bad dims");
   if (nc == 0) return 0;
-  hipLaunchKernelGGL(plane_sum_kernel, dim3(nc), dim3(hw >= 4096 ? 1024 : 256), 0, eavsr::as_stream(stream), a, b, out, hw, scale);
+  // float4 loads only where every plane starts on 16 bytes: a view at a 4-, 8- or 12-byte offset takes the dword loops
+  const int vec = (hw & 3) == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+  hipLaunchKernelGGL(plane_sum_kernel, dim3(nc), dim3(hw >= 4096 ? 1024 : 256), 0, eavsr::as_stream(stream), a, b, out, hw, scale, vec);
   return eavsr::launch_status("plane_sum");
 }
 
@@ -622,10 +624,13 @@ extern "C" int eavsr_channel_sum_multi_f32(const void* const* a_list, int32_t ns
   EAVSR_REQUIRE(n >= 0 && c >= 0 && hw > 0, -1, "channel_sum: bad dims");
   if (c == 0) return 0;
   ChanSumArgs g;
+  uintptr_t low = 0;
   for (int s = 0; s < CS_MAX_SEG; ++s) {
     g.av[s] = reinterpret_cast<const float*>(a_list[s < nseg ? s : 0]);
     EAVSR_REQUIRE(g.av[s], -1, "channel_sum: NULL segment pointer");
+    low |= (uintptr_t)g.av[s];
   }
+  g.vec = (hw & 3) == 0 && (low & 15) == 0;
   g.out = out; g.nseg = nseg; g.n = n; g.c = c; g.hw = hw; g.accumulate = accumulate;
   hipLaunchKernelGGL(channel_sum_kernel, dim3(c), dim3(1024), 0, eavsr::as_stream(stream), g);
   return eavsr::launch_status("channel_sum");

@@ -670,8 +670,9 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
             raise ValueError("all sources must share n,h,w")
     cin = sum(int(s.shape[1]) for s in srcs)
     if dgrad:
-        if len(weights) != 1 or biases != [None] or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None:
-            raise ValueError("dgrad: one forward weight, no bias / channel sums / prologue / shuffle / sigmoid")
+        if (len(weights) != 1 or biases != [None] or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None
+                or res_scale is not None):      # (res_scale: on every route -- the materialised-weight routes below would drop it)
+            raise ValueError("dgrad: one forward weight, no bias / channel sums / prologue / shuffle / sigmoid / scaled residual")
         if int(weights[0].shape[0]) != cin:
             raise ValueError(f"dgrad: the forward weight has {int(weights[0].shape[0])} output channels, dY gives {cin}")
         k_ = int(weights[0].shape[-1])
@@ -706,9 +707,13 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
             raise ValueError("sigmoid_from: plain convolutions only")
         fused = (((k == 7 and CONV7_MODE == "bf16x6") or (k == 5 and CONV5_MODE == "bf16x6")) and len(srcs) == 1
                  and cin % 8 == 0 and sigmoid_from % 8 == 0)
-        if not fused:              # every other kernel: the activation is one more pass over those channels
-            y = conv2d(srcs, weights, biases, act, slope)
+        if not fused:              # every other kernel: the activations are one more pass over the output
+            y = conv2d(srcs, weights, biases)      # (without `act`: the tail channels take the sigmoid INSTEAD of it)
             y[:, sigmoid_from:] = torch.sigmoid(y[:, sigmoid_from:])
+            if ACT[act] == 1:
+                y[:, :sigmoid_from].clamp_(min=0.0)
+            elif ACT[act] == 2:
+                torch.nn.functional.leaky_relu(y[:, :sigmoid_from], float(slope), inplace=True)
             return y
     if k == 3 and len(srcs) == 1 and cout in (2, 3, 4, 6) and not chan_partial and ca is None and not masked and res_scale is None:
         y = _conv3x3_smallco(srcs[0], weights, biases, act, slope, residual)

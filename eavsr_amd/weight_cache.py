@@ -41,7 +41,9 @@ class WeightCache:
         d = self._d
         key = (tag, *[(id(t), t._version) for t in sources])
         cur = dict(key[1:])
-        for k in [k for k in d if any(cur.get(i, v) != v for i, v in k[1:])]:
-            del d[k]
+        # (over a copy of the keys: the weak-reference callbacks below pop entries whenever the collector frees a source, also
+        #  in the middle of this loop -- "dictionary changed size during iteration")
+        for k in [k for k in tuple(d) if any(cur.get(i, v) != v for i, v in k[1:])]:
+            d.pop(k, None)
         d[key] = (tuple(weakref.ref(t, lambda _r: d.pop(key, None)) for t in sources), value)
         return value
