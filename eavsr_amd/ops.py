@@ -10,7 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -439,28 +439,6 @@ def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None)
     return cnt
 
 
-def x6s_takes(n: int, h: int, w: int) -> bool:
-    """a single-source 3x3 64 -> 64 launch of this size runs on eavsr_conv3x3_f32x6s (the crop-sized bf16x6 kernel) in the current mode"""
-    return (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4") and CONV3_H16 is None
-            and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
-
-
-def _conv_x6(x: Tensor, weights, biases, act, slope, sigmoid_from: int = -1):
-    n, cin, h, w = x.shape
-    cout = sum(int(w_.shape[0]) for w_ in weights)
-    k = int(weights[0].shape[-1])
-    wp = _packed_conv_x6(weights)
-    b = _bias_of(biases)
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
-    st = _stream(x)
-    px = float(n * h * w)
-    _launch(f"conv{k}x{k}_{cin}to{cout}_x6", 2.0 * cin * cout * k * k * px, 4.0 * px * (cin + cout), x,
-            lambda: lib().eavsr_conv_f32x6(_p(x), _p(wp), _p(b), _p(out), n, cin, cout, h, w, k, ACT[act], float(slope),
-                                           int(sigmoid_from), st),
-            "conv_f32x6")
-    return out
-
-
 # The 16-bit modes' generic 3x3 convolution (csrc/conv3_h16.hip): None = off (fp32 everywhere, the default), "bf16" / "fp16" =
 # every plain 3x3 convolution with >= 32 output channels whose sources have channel counts % 16 == 0 rounds its operands to that
 # type (fp32 NCHW in and out).  Set by networks.set_backbone_dtype (EAVSR_CONV3_16BIT=0 keeps these convolutions fp32: A/B switch).
@@ -494,87 +472,61 @@ CONV7_H16_ENABLED = os.environ.get("EAVSR_CONV7_16BIT", "1") == "1"
 _h16x1_pack_cache = WeightCache()
 
 
-def _conv_h16x1(x: Tensor, weights, biases, act, slope, dtype):
-    n, cin, h, w = x.shape
-    cout = sum(int(w_.shape[0]) for w_ in weights)
-    k = int(weights[0].shape[-1])
-    code = h16_code(dtype)
-    wp = _h16x1_pack_cache.lookup(weights, code)
-    if wp is None:
-        wc = _chk(_cat_weights(weights).detach(), "weight")
-        wp = torch.empty(lib().eavsr_conv_weight_h16x1_bytes(k, cout, cin), device=wc.device, dtype=torch.uint8)
-        with _DeviceOf(wc):
-            N.check(lib().eavsr_pack_conv_weight_h16x1(_p(wc), _p(wp), k, cout, cin, code, _stream(wc)), "pack_conv_weight_h16x1")
-        _h16x1_pack_cache.store(weights, code, wp)
-    b = _bias_of(biases)
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
-    st = _stream(x)
-    px = float(n * h * w)
-    _launch(f"conv{k}x{k}_{cin}to{cout}_h16x1", 2.0 * cin * cout * k * k * px, 4.0 * px * (cin + cout), x,
-            lambda: lib().eavsr_conv_h16x1(_p(x), _p(wp), _p(b), _p(out), n, cin, cout, h, w, k, ACT[act], float(slope), code, st),
-            "conv_h16x1")
-    return out
-
-
-def _conv3x3_h16g(srcs, weights, biases, act, slope, dtype):
-    n, _, h, w = srcs[0].shape
-    cin = sum(int(s_.shape[1]) for s_ in srcs)
-    cout = sum(int(w_.shape[0]) for w_ in weights)
-    code = h16_code(dtype)
-    wp = _packed_h16g(weights, code)
-    b = _bias_of(biases)
-    out = torch.empty((n, cout, h, w), device=srcs[0].device, dtype=torch.float32)
-    d = N.ConvDesc()
-    for i in range(5):
-        d.src[i] = _p(srcs[i]) if i < len(srcs) else None
-        d.src_c[i] = int(srcs[i].shape[1]) if i < len(srcs) else 0
-    d.n_src = len(srcs)
-    d.ksize = 3
-    d.weight_packed = _p(wp)
-    d.bias = _p(b)
-    d.out = _p(out)
-    d.n, d.h, d.w, d.cin, d.cout = n, h, w, cin, cout
-    d.act = ACT[act]
-    d.slope = float(slope)
-    st = _stream(out)
-    px = float(n) * h * w
-    _launch(f"conv3x3_{cin}to{cout}_h16g", 2.0 * cin * cout * 9 * px, 4.0 * px * (cin + cout), out,
-            lambda: lib().eavsr_conv3x3_h16g_f32(C.byref(d), code, st), "conv3x3_h16g")
-    return out
-
-
-def _conv3x3_smallco(x: Tensor, weights, biases, act, slope, residual):
-    n, cin, h, w = x.shape
-    wt = _cat_weights(weights)
-    cout = int(wt.shape[0])
-    b = _bias_of(biases)
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
-    if residual is not None:
-        residual = _chk(residual, "residual")
-        if residual.shape != out.shape:
-            raise ValueError("residual shape mismatch")
-    st = _stream(x)
-    px = float(n) * h * w
-    if (SMALLCO_LITE and cout in (2, 3, 4, 6) and w % 4 == 0 and x.data_ptr() % 16 == 0 and h * w * cin * 4 < 2 ** 32
-            and _rn(n) * ((h + 7) // 8) * ((w + 63) // 64) >= SMALLCO_LITE_MIN_TILES):
-        wp = _packed_smallco(list(weights))
-        _launch(f"conv3x3_{cin}to{cout}", 2.0 * cin * cout * 9 * px, 4.0 * px * (cin + cout + (cout if residual is not None else 0)), x,
-                lambda: lib().eavsr_conv3x3_smallco_lite_f32(_p(x), _p(wp), _p(b), _p(residual), _p(out), n, cin, h, w, cout,
-                                                             ACT[act], float(slope), st), "conv3x3_smallco_lite")
-        return out
-    _launch(f"conv3x3_{cin}to{cout}", 2.0 * cin * cout * 9 * px, 4.0 * px * (cin + cout + (cout if residual is not None else 0)), x,
-            lambda: lib().eavsr_conv3x3_smallco_f32(_p(x), _p(wt), _p(b), _p(residual), _p(out), n, cin, h, w, cout,
-                                                    ACT[act], float(slope), st), "conv3x3_smallco")
-    return out
+def _packed_h16x1(weights: Sequence[Tensor], code: int) -> Tensor:
+    hit = _h16x1_pack_cache.lookup(weights, code)
+    if hit is not None:
+        return hit
+    w = _chk(_cat_weights(weights).detach(), "weight")
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
+    packed = torch.empty(lib().eavsr_conv_weight_h16x1_bytes(k, cout, cin), device=w.device, dtype=torch.uint8)
+    with _DeviceOf(w):
+        N.check(lib().eavsr_pack_conv_weight_h16x1(_p(w), _p(packed), k, cout, cin, code, _stream(w)), "pack_conv_weight_h16x1")
+    return _h16x1_pack_cache.store(weights, code, packed)
 
 
 # ------------------------------------------------------------------------------------------
 # dense conv  (nn.Conv2d, stride 1, "same" padding)
 # ------------------------------------------------------------------------------------------
+# The launch-size gates, each written once, over plain numbers: conv_route and the public predicates below all ask these.
+def _x6s_gate(n: int, h: int, w: int) -> bool:
+    """mode and size of the crop-sized bf16x6 kernel (eavsr_conv3x3_f32x6s): at most X6S_MAX_TILES of its 8 x 32-pixel tiles"""
+    return (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4")
+            and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
+
+
+def _wino_gate(n: int, h: int, w: int) -> bool:
+    """mode and size of the Winograd 3x3 kernels: at least WINO_MIN_TILES 8 x 32-pixel tiles"""
+    return CONV_MODE in ("winograd", "winograd4") and _rn(n) * _wino_tiles(h, w) >= WINO_MIN_TILES
+
+
+def _wino4_gate(n: int, h: int, w: int) -> bool:
+    """F(4x4, 3x3) behind _wino_gate: same 512-pixel-per-workgroup granularity (8 x 64)"""
+    return CONV_MODE == "winograd4" and 2 * _rn(n) * lib().eavsr_conv3x3_wino4_tiles(h, w) >= WINO_MIN_TILES
+
+
+def _wino5_gate(n: int, h: int, w: int, cout: int) -> bool:
+    """5x5 (the predictor's offset / mask heads) by F(2x2, 5x5): the same 6 x 6 tile pipeline, 4 x 32-pixel tiles"""
+    return CONV_MODE == "winograd4" and _rn(n) * lib().eavsr_conv5x5_wino_tiles(h, w) * ((cout + 63) // 64) >= 2 * WINO_MIN_TILES
+
+
+def _wino_ca_gate(n: int, h: int, w: int, c: int, mod16: int) -> bool:
+    """the channel-attention prologue inside the Winograd kernel's input transform (lab build)"""
+    return lab_available() and w % 4 == 0 and c % 8 == 0 and c <= 256 and mod16 == 0 and _wino_gate(n, h, w)
+
+
+def _direct_ca_gate(n: int, h: int, w: int, c: int, cout: int, mod16: int) -> bool:
+    """the channel-attention prologue of the direct kernel: its 32-row, 16-byte-DMA path"""
+    return (w % 4 == 0 and c % 4 == 0 and c <= 256 and 32 < cout <= 64 and mod16 == 0
+            and lib().eavsr_conv2d_tile_rows(n, h, w, 3) == 32)
+
+
+def x6s_takes(n: int, h: int, w: int) -> bool:
+    """a single-source 3x3 64 -> 64 launch of this size runs on eavsr_conv3x3_f32x6s (the crop-sized bf16x6 kernel) in the current mode"""
+    return CONV3_H16 is None and _x6s_gate(n, h, w)
+
+
 def _wino_fusable(x: Tensor) -> bool:
-    return (lab_available() and CONV_MODE in ("winograd", "winograd4") and x.dim() == 4 and x.shape[3] % 4 == 0 and x.shape[1] % 8 == 0 and x.shape[1] <= 256
-            and x.is_contiguous() and x.data_ptr() % 16 == 0
-            and _rn(int(x.shape[0])) * _wino_tiles(int(x.shape[2]), int(x.shape[3])) >= WINO_MIN_TILES)
+    return x.dim() == 4 and x.is_contiguous() and _wino_ca_gate(*(int(v) for v in (x.shape[0], x.shape[2], x.shape[3], x.shape[1])), x.data_ptr() % 16)
 
 
 def ca_fusable(x: Tensor, cout: int = 64) -> bool:
@@ -582,9 +534,8 @@ def ca_fusable(x: Tensor, cout: int = 64) -> bool:
     runs (its input transform applies it), or on the direct kernel's 32-row, 16-byte-DMA path."""
     if _wino_fusable(x):
         return True
-    return (x.dim() == 4 and x.shape[3] % 4 == 0 and x.shape[1] % 4 == 0 and x.shape[1] <= 256 and 32 < cout <= 64
-            and x.is_contiguous() and x.data_ptr() % 16 == 0
-            and lib().eavsr_conv2d_tile_rows(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), 3) == 32)
+    return (x.dim() == 4 and x.is_contiguous()
+            and _direct_ca_gate(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), int(x.shape[1]), cout, x.data_ptr() % 16))
 
 
 # EAVSR_FUSE_SHUFFLE=0: the upsampling tail's PixelShuffle(2) as a torch copy instead of the conv kernel's store pattern (A/B switch)
@@ -612,19 +563,188 @@ class BorderPieces:
         self.data, self.p_rows, self.p_cols = data, int(p_rows), int(p_cols)
 
 
-def conv2d(srcs, weight, bias=None, act=None, slope: float = 0.0, residual=None, chan_partial: bool = False, ca=None, ca_out: bool = False,
-           pixel_shuffle2: bool = False, sigmoid_from=None, dgrad: bool = False, res_scale=None, border: bool = False, sum_mul=None,
-           precision: str = "fp32"):
-    """see _conv2d (the implementation); this shim only normalises the `border` result: routes that do not produce border pieces
-    return None in its place"""
-    r = _conv2d(srcs, weight, bias, act, slope, residual, chan_partial, ca, ca_out, pixel_shuffle2, sigmoid_from, dgrad, res_scale, border,
-                sum_mul, precision)
-    if border and not (isinstance(r, tuple) and len(r) >= 2 and (r[-1] is None or isinstance(r[-1], BorderPieces))):
-        r = (tuple(r) if isinstance(r, tuple) else (r,)) + (None,)
-    return r
+class ConvRoute(NamedTuple):
+    """what conv_route decides for one conv2d call: ONE convolution launch and the steps behind it"""
+    family: str                         # the kernel family (a key of _CONV_KERNELS, "_ca" appended with the fused prologue)
+    name: str                           # the name ops.profile records for the launch
+    post: Tuple[str, ...] = ()          # then, in order: "plane_sum" / "scale_residual" (launches), "pixel_shuffle" / "sigmoid" (torch)
+    cat: bool = False                   # the ragged sources are concatenated first
+    materialise: bool = False           # dgrad: the launch takes dgrad_weight(weight) as a forward weight (else: packed in place)
+    part_tiles: Optional[int] = None    # the tile axis of the chan_partial / sum_mul result
+    pieces: bool = False                # border=True returns BorderPieces (else None)
+
+    @property
+    def kernels(self) -> Tuple[str, ...]:
+        """the names ops.profile records, in launch order"""
+        return (self.name,) + tuple(p for p in self.post if p in ("plane_sum", "scale_residual"))
+
+    @property
+    def families(self) -> Tuple[str, ...]:
+        return (self.family,) + self.kernels[1:]
 
 
-def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequence[Tensor]],
+def conv_route(n: int, h: int, w: int, k: int, chans: Sequence[int], cout: int, n_weights: int = 1, bias: bool = True, *,
+               act: Optional[str] = None, residual: bool = False, chan_partial: bool = False, ca: bool = False, ca_out: bool = False,
+               pixel_shuffle2: bool = False, res_scale: bool = False, sum_mul: bool = False, dgrad: bool = False,
+               sigmoid_from: Optional[int] = None, border: bool = False, precision: str = "fp32", src_mod: Optional[Sequence[int]] = None,
+               residual_mod: int = 0, ca_mod: int = 0, sum_mul_mod: int = 0, sum_mul_shaped: bool = True, grad: bool = True) -> ConvRoute:
+    """Which kernel one conv2d call runs on and what follows it, from plain values alone: no tensor, no allocation, no launch, no
+    device.  chans: the sources' channel counts; cout: the call's OUTPUT channels (dgrad: the forward weight's input channels); the
+    option flags say whether conv2d's argument of that name is given; *_mod: the operand's address modulo 16 (src_mod: one per
+    source); sum_mul_shaped: sum_mul has the output's shape; grad: autograd is enabled.  Reads the kernel modes and thresholds of
+    this module, the pinned route batch and the library's host-side tile counters.  Raises what conv2d raises for a combination its
+    docstring rules out (ValueError) and for a prologue no kernel can fuse (NotImplementedError)."""
+    chans = tuple(int(c) for c in chans)
+    cin, single = sum(chans), len(chans) == 1
+    src_mod = tuple(src_mod) if src_mod is not None else (0,) * len(chans)
+    masked = act == "relu_mask"    # out = residual > 0 ? conv : 0 (a ReLU's backward inside the input-gradient convolution): direct kernels only
+    cat = False
+
+    def route(fam, **kw):
+        ca_ = "_ca" if ca else ""
+        return ConvRoute(fam + ca_, f"conv{k}x{k}_{cin}to{cout}{_CONV_KERNELS[fam][0]}{ca_}", cat=cat, **kw)
+
+    def two_step(step, **opts):
+        """a fallback form: the route of the simpler call (on the sources as they are by now) and one more step behind it"""
+        r = conv_route(n, h, w, k, chans, cout, **{**dict(n_weights=n_weights, bias=bias, act=act, src_mod=src_mod, grad=grad), **opts})
+        return r._replace(post=r.post + step, cat=cat or r.cat, part_tiles=1 if step == ("plane_sum",) else r.part_tiles)
+
+    check_precision(precision)
+    if sum_mul and (not dgrad or chan_partial or ca or pixel_shuffle2 or sigmoid_from is not None or res_scale or masked):
+        raise ValueError("sum_mul: input-gradient convolutions only (dgrad=True; no channel sums / prologue / shuffle / sigmoid / mask)")
+    if dgrad:
+        if n_weights != 1 or bias or chan_partial or ca or pixel_shuffle2 or sigmoid_from is not None or res_scale:
+            # (res_scale: on every route -- the materialised-weight routes below would drop it)
+            raise ValueError("dgrad: one forward weight, no bias / channel sums / prologue / shuffle / sigmoid / scaled residual")
+        # only the small-launch bf16x6 kernel reads the forward weight in place (necessary conditions; the decision is below)
+        if not (k == 3 and single and cin == 64 and cout not in (2, 3, 4, 6) and x6s_takes(n, h, w)):
+            r = two_step(("plane_sum",) if sum_mul else (), bias=False, residual=residual, residual_mod=residual_mod)
+            return r._replace(materialise=True)
+    if pixel_shuffle2 and (cout % 4 or residual or chan_partial or ca):
+        raise ValueError("pixel_shuffle2: cout % 4 == 0, no residual / channel sums / channel-attention prologue")
+    if res_scale and (not residual or chan_partial or ca or pixel_shuffle2 or sigmoid_from is not None or dgrad or masked):
+        raise ValueError("res_scale: with `residual`; no channel sums / prologue / shuffle / sigmoid / dgrad / mask")
+    if masked and (not residual or chan_partial or ca or pixel_shuffle2 or sigmoid_from is not None):
+        raise ValueError("act='relu_mask': residual = the ReLU's forward output; no channel sums / prologue / shuffle / sigmoid")
+    if ca_out and not ca:          # before any early return (ADVICE r3: the bf16x6 route used to skip this check)
+        raise ValueError("ca_out needs ca")
+    x6_mode = ((k == 7 and CONV7_MODE == "bf16x6") or (k == 5 and CONV5_MODE == "bf16x6")) and single and cin % 8 == 0
+    if sigmoid_from is not None:   # validated once, for every route (ADVICE r4: routes used to differ)
+        if not 0 <= int(sigmoid_from) < cout:
+            raise ValueError(f"sigmoid_from {int(sigmoid_from)}: 0 <= value < cout = {cout}")
+        if residual or chan_partial or ca or pixel_shuffle2:
+            raise ValueError("sigmoid_from: plain convolutions only")
+        if not (x6_mode and int(sigmoid_from) % 8 == 0):      # every other kernel: the activations are one more pass over the output
+            return two_step(("sigmoid",), act=None)           # (without `act`: the tail channels take the sigmoid INSTEAD of it)
+    # ---- the kernels with a shape of their own
+    if k == 3 and single and cout in (2, 3, 4, 6) and not chan_partial and not ca and not masked and not res_scale:
+        lite = (SMALLCO_LITE and w % 4 == 0 and src_mod[0] == 0 and h * w * cin * 4 < 2 ** 32
+                and _rn(n) * ((h + 7) // 8) * ((w + 63) // 64) >= SMALLCO_LITE_MIN_TILES)
+        return route("smallco_lite" if lite else "smallco_classic", post=("pixel_shuffle",) if pixel_shuffle2 else ())
+    bare = not (residual or chan_partial or ca or pixel_shuffle2)
+    h16 = CONV3_H16 is not None and sigmoid_from is None and bare and not grad
+    if h16 and k == 7 and CONV7_H16_ENABLED and single and cin % 8 == 0 and cout >= 16:
+        return route("h16x1")      # SPyNet's feature layers (its 16 -> 2 flow head stays exact)
+    if x6_mode and bare:
+        return route("x6")
+    if h16 and k == 3 and w % 4 == 0 and cout >= 32 and all(c % 16 == 0 for c in chans) and not any(src_mod):
+        return route("h16g")
+    # ---- the descriptor kernels
+    if any(c % lib().eavsr_conv2d_ck(k) for c in chans[:-1]):
+        chans, src_mod, single, cat = (cin,), (0,), True, True      # ragged middle source: materialise (tiny SPyNet inputs only)
+    if CONV_MODE in ("winograd", "bf16x9"):      # (set through the environment: set_conv_mode() checks at the call)
+        require_lab(f"conv mode {CONV_MODE!r}")
+    lab = lab_available()
+    base_ok = k == 3 and w % 4 == 0 and all(c % 8 == 0 for c in chans) and not any(src_mod)
+    wino = _wino_gate(n, h, w) and base_ok and not masked and (not ca or (lab and single and cin <= 256 and ca_mod == 0))
+    # F(4x4, 3x3): no fused channel-attention prologue
+    wino4 = wino and (not residual or residual_mod == 0) and _wino4_gate(n, h, w)
+    if wino and not wino4 and not lab:
+        wino = False      # default build: F(2x2,3x3) is a lab kernel -- what F(4x4,3x3) does not take runs the direct kernel
+    if res_scale and not (wino4 and cin % 8 == 0 and lib().eavsr_wino4_schedule() >= 1):
+        return two_step(("scale_residual",))      # every other kernel: the convolution, then the tail as its own launch
+    if pixel_shuffle2 and not (wino4 and FUSE_PIXEL_SHUFFLE):
+        return two_step(("pixel_shuffle",))       # every other kernel: plain output, shuffled by torch
+    wino5 = (k == 5 and not ca and not masked and w % 4 == 0 and all(c % 4 == 0 for c in chans) and not any(src_mod)
+             and (not residual or residual_mod % 8 == 0) and _wino5_gate(n, h, w, cout))
+    # small launches of the 64-channel 3x3 convolution (a training crop, a pyramid level): exact bf16x6 instead of the fp32 MFMA
+    # (the explicit modes "direct" / "bf16x9" keep their own kernels: they are the A/B references)
+    x6s = k == 3 and single and cin == 64 and not ca and not pixel_shuffle2 and not wino and _x6s_gate(n, h, w)
+    if sum_mul and not (x6s and w % 4 == 0 and sum_mul_shaped and src_mod[0] == 0 and sum_mul_mod == 0
+                        and (not residual or residual_mod == 0)):
+        # the kernel's epilogue form does not apply: a plane-sum launch behind the input-gradient convolution
+        return two_step(("plane_sum",), bias=False, dgrad=True, residual=residual, residual_mod=residual_mod, precision=precision)
+    if ca:
+        if not single:
+            raise ValueError("ca=(scale, x): one source, x of the same shape, scale (n, cin)")
+        if not wino and (k != 3 or ca_mod or not (_wino_ca_gate(n, h, w, cin, src_mod[0]) or _direct_ca_gate(n, h, w, cin, cout, src_mod[0]))):
+            raise NotImplementedError("fused channel-attention prologue unavailable for this shape; use "
+                                      "scale_residual + conv2d (see ops.ca_fusable)")
+    if x6s:      # precision="bf16" (the bf16 training mode): the same launch with its operands rounded once to bf16
+        fam, tiles = "bf16s" if precision == "bf16" else "x6s", lib().eavsr_conv3x3_x6s_tiles
+    elif wino5:
+        fam, tiles = "wino5", lib().eavsr_conv5x5_wino_tiles
+    elif wino4:
+        fam, tiles = "wino4", lib().eavsr_conv3x3_wino4_tiles
+    elif wino:
+        fam, tiles = "wino", _wino_tiles
+    else:
+        x9 = CONV_MODE == "bf16x9" and base_ok and not ca and not masked and lib().eavsr_conv2d_tile_rows(n, h, w, 3) == 32
+        fam, tiles = "x9" if x9 else "direct", lambda h_, w_: lib().eavsr_conv2d_tiles(n, h_, w_, k)
+    pieces = bool(border and chan_partial and wino4 and cout == 64 and cin % 8 == 0 and not ca and not pixel_shuffle2 and not res_scale
+                  and lib().eavsr_wino4_schedule() == 1)
+    return route(fam, materialise=dgrad and not x6s,      # (e.g. a large input-gradient launch that the Winograd kernel takes)
+                 part_tiles=int(tiles(h, w)) if chan_partial or sum_mul else None, pieces=pieces)
+
+
+def _flat(entry: str, *fields: str, aux: bool = False):
+    """the launch of a kernel with a flat argument list: x, weight, then the named descriptor fields [, aux], stream"""
+    return lambda L, d, wq, a, st: getattr(L, entry)(d.src[0], wq, *(getattr(d, f) for f in fields), *((a,) if aux else ()), st)
+
+
+# family -> (suffix of the profile name, the descriptor's weight(weights, aux), the kernel's own weight(weights, dgrad, aux),
+#            launch(library, descriptor, own weight's address, aux, stream), the `what` of N.check)
+# aux: the 16-bit type code (h16x1, h16g); the first channel of the fused sigmoid or -1 (x6)
+_SMALLCO_ARGS = ("bias", "residual", "out", "n", "cin", "h", "w", "cout", "act", "slope")
+_X6_ARGS = ("bias", "out", "n", "cin", "cout", "h", "w", "ksize", "act", "slope")
+_CONV_KERNELS = {
+    "smallco_lite": ("", None, lambda ws, dg, a: _packed_smallco(list(ws)), _flat("eavsr_conv3x3_smallco_lite_f32", *_SMALLCO_ARGS), "conv3x3_smallco_lite"),
+    "smallco_classic": ("", None, lambda ws, dg, a: _cat_weights(ws), _flat("eavsr_conv3x3_smallco_f32", *_SMALLCO_ARGS), "conv3x3_smallco"),
+    "x6": ("_x6", None, lambda ws, dg, a: _packed_conv_x6(ws), _flat("eavsr_conv_f32x6", *_X6_ARGS, aux=True), "conv_f32x6"),
+    "h16x1": ("_h16x1", None, lambda ws, dg, a: _packed_h16x1(ws, a), _flat("eavsr_conv_h16x1", *_X6_ARGS, aux=True), "conv_h16x1"),
+    "h16g": ("_h16g", lambda ws, a: _packed_h16g(ws, a), None, lambda L, d, wq, a, st: L.eavsr_conv3x3_h16g_f32(C.byref(d), a, st), "conv3x3_h16g"),
+    # (the x6s kernel has its own packed form, also of the input-gradient convolution's weight, straight from the forward weight)
+    "bf16s": ("_bf16s", None, lambda ws, dg, a: _packed_conv3_bf16(ws, dgrad=dg), lambda L, d, wq, a, st: L.eavsr_conv3x3_bf16x1s(C.byref(d), wq, st), "conv3x3_bf16x1s"),
+    "x6s": ("_x6s", None, lambda ws, dg, a: _packed_conv_x6(ws, dgrad=dg), lambda L, d, wq, a, st: L.eavsr_conv3x3_f32x6s(C.byref(d), wq, st), "conv3x3_f32x6s"),
+    "wino5": ("_wino", lambda ws, a: _packed_f32(ws), lambda ws, dg, a: _packed_wino(ws, kind="f5"), lambda L, d, wq, a, st: L.eavsr_conv5x5_wino_f32(C.byref(d), wq, st), "conv5x5_wino"),
+    "wino4": ("_wino4", lambda ws, a: _packed_f32(ws), lambda ws, dg, a: _packed_wino(ws, four=True), lambda L, d, wq, a, st: L.eavsr_conv3x3_wino4_f32(C.byref(d), wq, st), "conv3x3_wino4"),
+    "wino": ("_wino", lambda ws, a: _packed_f32(ws), lambda ws, dg, a: _packed_wino(ws), lambda L, d, wq, a, st: L.eavsr_conv3x3_wino_f32(C.byref(d), wq, st), "conv3x3_wino"),
+    "x9": ("_x9", lambda ws, a: _packed_f32(ws), lambda ws, dg, a: _packed_x9(ws), lambda L, d, wq, a, st: L.eavsr_conv3x3_f32x9(C.byref(d), wq, st), "conv3x3_f32x9"),
+    "direct": ("", lambda ws, a: _packed_f32(ws), None, lambda L, d, wq, a, st: L.eavsr_conv2d_f32(C.byref(d), st), "conv2d"),
+}
+
+
+def _conv_desc(srcs: Sequence[Tensor], k: int, cout: int, weight_packed, bias, out, act, slope: float) -> "N.ConvDesc":
+    """struct eavsr_conv2d_desc of a plain convolution; the caller adds the optional operands"""
+    d = N.ConvDesc()      # (zero-filled: unused sources, every optional operand)
+    for i, s in enumerate(srcs):
+        d.src[i], d.src_c[i] = _p(s), int(s.shape[1])
+    d.n_src, d.ksize = len(srcs), k
+    d.weight_packed, d.bias, d.out = _p(weight_packed), _p(bias), _p(out)
+    d.n, d.h, d.w = int(srcs[0].shape[0]), int(srcs[0].shape[2]), int(srcs[0].shape[3])
+    d.cin, d.cout = sum(int(s.shape[1]) for s in srcs), cout
+    d.act, d.slope = ACT[act], float(slope)
+    return d
+
+
+def _conv_cost(n: int, h: int, w: int, k: int, cin: int, cout: int, residual: bool, reads_per_input: int = 1) -> Tuple[float, float]:
+    """algorithmic (FLOPs, bytes) of one convolution launch as `_launch` records them.  reads_per_input: 2 with the channel-attention
+    prologue (the input and `x`), 3 when the effective input is written back as well (ca_out)"""
+    px = float(n) * h * w
+    return 2.0 * cin * cout * k * k * px, 4.0 * px * (cin * reads_per_input + cout + (cout if residual else 0))
+
+
+def conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequence[Tensor]],
            bias: Union[None, Tensor, Sequence[Optional[Tensor]]] = None, act: Optional[str] = None,
            slope: float = 0.0, residual: Optional[Tensor] = None, chan_partial: bool = False,
            ca: Optional[Tuple[Tensor, Tensor]] = None, ca_out: bool = False, pixel_shuffle2: bool = False,
@@ -632,7 +752,7 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
            sum_mul: Optional[Tensor] = None, precision: str = "fp32"):
     """conv over the virtual channel-concatenation of `srcs`; `weight` may be a list of weights
     that are concatenated along cout (several heads in one launch).
-    border=True (with chan_partial=True): a third result, the sums of the output's four border lines per border tile
+    border=True (with chan_partial=True): a last result, the sums of the output's four border lines per border tile
     (`BorderPieces`, for ca_scale_pre(.., border=)) where the grouped F(4x4,3x3) kernel runs, None on every other route.
     res_scale (n, cout) with `residual`: out = residual + res_scale[n, co] * act(conv + bias) -- RCABlock's tail as the epilogue of
     the F(4x4,3x3) kernel (the attention from ca_scale_pre BEFORE the launch); other routes: the convolution, then scale_residual.
@@ -651,227 +771,99 @@ def _conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequenc
     precision="bf16" (the bf16 training mode; autograd passes it): where the crop-sized kernel takes the launch (x6s_takes), it runs
     with its operands rounded once to bf16 (eavsr_conv3x3_bf16x1s); every other route ignores it and stays as it is.
     Returns out, then the per-tile channel sums when chan_partial=True, then the effective input when
-    ca_out=True."""
-    check_precision(precision)
-    if sum_mul is not None:
-        if not dgrad or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None or res_scale is not None or act == "relu_mask":
-            raise ValueError("sum_mul: input-gradient convolutions only (dgrad=True; no channel sums / prologue / shuffle / sigmoid / mask)")
-        sum_mul = _chk(sum_mul, "sum_mul")
-    if isinstance(srcs, torch.Tensor):
-        srcs = [srcs]
+    ca_out=True.  Which kernel runs, and every combination that is refused: conv_route."""
+    # ---- the arguments, normalised
+    check_precision(precision)      # (before any tensor is looked at)
+    srcs = [_chk(s, f"src{i}") for i, s in enumerate([srcs] if isinstance(srcs, torch.Tensor) else srcs)]
     weights = [weight] if isinstance(weight, torch.Tensor) else list(weight)
     biases = [bias] if (bias is None or isinstance(bias, torch.Tensor)) else list(bias)
-    srcs = [_chk(s, f"src{i}") for i, s in enumerate(srcs)]
+    residual, res_scale, sum_mul = (None if t is None else _chk(t, nm) for t, nm in
+                                    ((residual, "residual"), (res_scale, "res_scale"), (sum_mul, "sum_mul")))
+    if ca is not None:
+        ca = (_chk(ca[0], "ca scale"), _chk(ca[1], "ca x"))
+    sigmoid_from = None if sigmoid_from is None else int(sigmoid_from)
+    # ---- the facts of the call
     if not 1 <= len(srcs) <= 5:
         raise ValueError("1..5 sources")
-    n, _, h, w = srcs[0].shape
-    for s in srcs:
-        if s.shape[0] != n or tuple(s.shape[2:]) != (h, w):
-            raise ValueError("all sources must share n,h,w")
-    cin = sum(int(s.shape[1]) for s in srcs)
-    if dgrad:
-        if (len(weights) != 1 or biases != [None] or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None
-                or res_scale is not None):      # (res_scale: on every route -- the materialised-weight routes below would drop it)
-            raise ValueError("dgrad: one forward weight, no bias / channel sums / prologue / shuffle / sigmoid / scaled residual")
-        if int(weights[0].shape[0]) != cin:
-            raise ValueError(f"dgrad: the forward weight has {int(weights[0].shape[0])} output channels, dY gives {cin}")
-        k_ = int(weights[0].shape[-1])
-        # only the small-launch bf16x6 kernel reads the forward weight in place (necessary conditions; the decision is below)
-        if not (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4") and k_ == 3 and len(srcs) == 1 and cin == 64
-                and int(weights[0].shape[1]) not in (2, 3, 4, 6) and CONV3_H16 is None
-                and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES):
-            y = conv2d(srcs, dgrad_weight(weights[0]), None, act, slope, residual)
-            return y if sum_mul is None else (y, plane_sum(y, sum_mul).view(n, 1, -1))
-    cout = sum(int(x.shape[0]) for x in weights) if not dgrad else int(weights[0].shape[1])
-    k = int(weights[0].shape[-1])
+    n, _, h, w = (int(v) for v in srcs[0].shape)
+    if any(s.shape[0] != n or tuple(s.shape[2:]) != (h, w) for s in srcs):
+        raise ValueError("all sources must share n,h,w")
+    chans = [int(s.shape[1]) for s in srcs]
+    cin, k = sum(chans), int(weights[0].shape[-1])
+    cout = int(weights[0].shape[1]) if dgrad else sum(int(x.shape[0]) for x in weights)
+    if dgrad and len(weights) == 1 and int(weights[0].shape[0]) != cin:
+        raise ValueError(f"dgrad: the forward weight has {int(weights[0].shape[0])} output channels, dY gives {cin}")
     if not dgrad and any(int(x.shape[1]) != cin for x in weights):
         raise ValueError(f"weight expects {[int(x.shape[1]) for x in weights]} input channels, sources give {cin}")
-    if pixel_shuffle2 and (cout % 4 or residual is not None or chan_partial or ca is not None):
-        raise ValueError("pixel_shuffle2: cout % 4 == 0, no residual / channel sums / channel-attention prologue")
-    if res_scale is not None:
-        if residual is None or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None or dgrad or act == "relu_mask":
-            raise ValueError("res_scale: with `residual`; no channel sums / prologue / shuffle / sigmoid / dgrad / mask")
-        res_scale = _chk(res_scale, "res_scale")
-        if tuple(res_scale.shape) != (n, cout):
-            raise ValueError(f"res_scale must be (n, cout) = ({n}, {cout})")
-    masked = act == "relu_mask"    # out = residual > 0 ? conv : 0 (a ReLU's backward inside the input-gradient convolution): direct kernels only
-    if masked and (residual is None or chan_partial or ca is not None or pixel_shuffle2 or sigmoid_from is not None):
-        raise ValueError("act='relu_mask': residual = the ReLU's forward output; no channel sums / prologue / shuffle / sigmoid")
-    if ca_out and ca is None:      # before any early return (ADVICE r3: the bf16x6 route used to skip this check)
-        raise ValueError("ca_out needs ca")
-    if sigmoid_from is not None:   # validated once, for every route (ADVICE r4: routes used to differ)
-        sigmoid_from = int(sigmoid_from)
-        if not 0 <= sigmoid_from < cout:
-            raise ValueError(f"sigmoid_from {sigmoid_from}: 0 <= value < cout = {cout}")
-        if residual is not None or chan_partial or ca is not None or pixel_shuffle2:
-            raise ValueError("sigmoid_from: plain convolutions only")
-        fused = (((k == 7 and CONV7_MODE == "bf16x6") or (k == 5 and CONV5_MODE == "bf16x6")) and len(srcs) == 1
-                 and cin % 8 == 0 and sigmoid_from % 8 == 0)
-        if not fused:              # every other kernel: the activations are one more pass over the output
-            y = conv2d(srcs, weights, biases)      # (without `act`: the tail channels take the sigmoid INSTEAD of it)
-            y[:, sigmoid_from:] = torch.sigmoid(y[:, sigmoid_from:])
-            if ACT[act] == 1:
-                y[:, :sigmoid_from].clamp_(min=0.0)
-            elif ACT[act] == 2:
-                torch.nn.functional.leaky_relu(y[:, :sigmoid_from], float(slope), inplace=True)
-            return y
-    if k == 3 and len(srcs) == 1 and cout in (2, 3, 4, 6) and not chan_partial and ca is None and not masked and res_scale is None:
-        y = _conv3x3_smallco(srcs[0], weights, biases, act, slope, residual)
-        return torch.nn.functional.pixel_shuffle(y, 2) if pixel_shuffle2 else y
-    if (CONV3_H16 is not None and k == 7 and CONV7_H16_ENABLED and sigmoid_from is None and len(srcs) == 1 and cin % 8 == 0 and cout >= 16
-            and residual is None and not chan_partial and ca is None and not pixel_shuffle2 and not torch.is_grad_enabled()):
-        return _conv_h16x1(srcs[0], weights, biases, act, slope, CONV3_H16)      # SPyNet's feature layers (its 16 -> 2 flow head stays exact)
-    if (((k == 7 and CONV7_MODE == "bf16x6") or (k == 5 and CONV5_MODE == "bf16x6")) and len(srcs) == 1 and cin % 8 == 0
-            and residual is None and not chan_partial and ca is None and not pixel_shuffle2):
-        return _conv_x6(srcs[0], weights, biases, act, slope, -1 if sigmoid_from is None else int(sigmoid_from))
-    if (CONV3_H16 is not None and k == 3 and sigmoid_from is None and residual is None and not chan_partial and ca is None
-            and not pixel_shuffle2 and w % 4 == 0 and cout >= 32 and not torch.is_grad_enabled()
-            and all(int(s_.shape[1]) % 16 == 0 and s_.data_ptr() % 16 == 0 for s_ in srcs)):
-        return _conv3x3_h16g(srcs, weights, biases, act, slope, CONV3_H16)
-    ck = lib().eavsr_conv2d_ck(k)
-    if any(int(s.shape[1]) % ck for s in srcs[:-1]):
-        srcs = [torch.cat(srcs, 1)]  # ragged middle source: materialise (tiny SPyNet inputs only)
-    b = _bias_of(biases)
-    out = torch.empty((n, cout, h, w), device=srcs[0].device, dtype=torch.float32)
-    base_ok = (k == 3 and w % 4 == 0 and all(int(s_.shape[1]) % 8 == 0 and s_.data_ptr() % 16 == 0 for s_ in srcs))
-    x9_ok = base_ok and ca is None and not masked
-    if CONV_MODE in ("winograd", "bf16x9"):      # (set through the environment: set_conv_mode() checks at the call)
-        require_lab(f"conv mode {CONV_MODE!r}")
-    lab = lab_available()
-    use_wino = (CONV_MODE in ("winograd", "winograd4") and base_ok and not masked
-                and _rn(n) * _wino_tiles(h, w) >= WINO_MIN_TILES
-                and (ca is None or (lab and len(srcs) == 1 and cin <= 256 and ca[1].data_ptr() % 16 == 0)))
-    # F(4x4, 3x3): same 512-pixel-per-workgroup granularity (8 x 64), no fused channel-attention prologue
-    use_wino4 = (use_wino and CONV_MODE == "winograd4" and out.data_ptr() % 16 == 0
-                 and (residual is None or residual.data_ptr() % 16 == 0)
-                 and 2 * _rn(n) * lib().eavsr_conv3x3_wino4_tiles(h, w) >= WINO_MIN_TILES)
-    if use_wino and not use_wino4 and not lab:
-        use_wino = False      # default build: F(2x2,3x3) is a lab kernel -- what F(4x4,3x3) does not take runs the direct kernel
-    if res_scale is not None and not (use_wino4 and cin % 8 == 0 and lib().eavsr_wino4_schedule() >= 1):
-        # every other kernel: the convolution, then the tail as its own launch
-        return scale_residual(conv2d(srcs, weights, biases, act=act, slope=slope), res_scale, residual)
-    if pixel_shuffle2 and not (use_wino4 and FUSE_PIXEL_SHUFFLE):      # every other kernel: plain output, shuffled by torch
-        return torch.nn.functional.pixel_shuffle(conv2d(srcs, weights, biases, act=act, slope=slope), 2)
-    # 5x5 (the predictor's offset / mask heads) by F(2x2, 5x5): the same 6 x 6 tile pipeline, 4 x 32-pixel tiles
-    use_wino5 = (CONV_MODE == "winograd4" and k == 5 and ca is None and not masked and w % 4 == 0 and out.data_ptr() % 8 == 0
-                 and all(int(s_.shape[1]) % 4 == 0 and s_.data_ptr() % 16 == 0 for s_ in srcs)
-                 and (residual is None or residual.data_ptr() % 8 == 0)
-                 and _rn(n) * lib().eavsr_conv5x5_wino_tiles(h, w) * ((cout + 63) // 64) >= 2 * WINO_MIN_TILES)
-    # small launches of the 64-channel 3x3 convolution (a training crop, a pyramid level): exact bf16x6 instead of the fp32 MFMA
-    # (the explicit modes "direct" / "bf16x9" keep their own kernels: they are the A/B references)
-    use_x6s = (CONV3_SMALL == "x6s" and CONV_MODE in ("winograd", "winograd4") and k == 3 and len(srcs) == 1 and cin == 64
-               and ca is None and not pixel_shuffle2 and not use_wino
-               and _rn(n) * lib().eavsr_conv3x3_x6s_tiles(h, w) <= X6S_MAX_TILES)
-    if sum_mul is not None and not (use_x6s and w % 4 == 0 and tuple(sum_mul.shape) == (n, cout, h, w) and
-                                    all(t_ is None or t_.data_ptr() % 16 == 0 for t_ in (srcs[0], out, residual, sum_mul))):
-        y = conv2d(srcs, weights, None, act, slope, residual, dgrad=True, precision=precision)      # the kernel's epilogue form does not apply: a launch
-        return y, plane_sum(y, sum_mul).view(n, 1, -1)
-    if dgrad and not use_x6s:      # (e.g. a large launch that the Winograd kernel takes)
+    if residual is not None and tuple(residual.shape) != (n, cout, h, w):
+        raise ValueError("residual shape mismatch")
+    if res_scale is not None and tuple(res_scale.shape) != (n, cout):
+        raise ValueError(f"res_scale must be (n, cout) = ({n}, {cout})")
+    if ca is not None and (tuple(ca[1].shape) != (n, cin, h, w) or tuple(ca[0].shape) != (n, cin)):
+        raise ValueError("ca=(scale, x): one source, x of the same shape, scale (n, cin)")
+    mod16 = lambda t: 0 if t is None else t.data_ptr() % 16
+    r = conv_route(n, h, w, k, chans, cout, len(weights), any(b is not None for b in biases), act=act, residual=residual is not None,
+                   chan_partial=chan_partial, ca=ca is not None, ca_out=ca_out, pixel_shuffle2=pixel_shuffle2,
+                   res_scale=res_scale is not None, sum_mul=sum_mul is not None, dgrad=dgrad, sigmoid_from=sigmoid_from, border=border,
+                   precision=precision, src_mod=[mod16(s) for s in srcs], residual_mod=mod16(residual),
+                   ca_mod=0 if ca is None else mod16(ca[1]), sum_mul_mod=mod16(sum_mul),
+                   sum_mul_shaped=sum_mul is None or tuple(sum_mul.shape) == (n, cout, h, w), grad=torch.is_grad_enabled())
+    # ---- what the route asks for in front of the launch, and what the launch itself applies (the rest: r.post)
+    if r.cat:
+        srcs = [torch.cat(srcs, 1)]
+    if r.materialise:
         weights, dgrad = [dgrad_weight(weights[0])], False
-    wp = None if use_x6s else _packed_f32(weights)      # (the x6s kernel has its own packed form)
-    part = None
-    if sum_mul is not None:      # (use_x6s holds)
-        part = torch.empty((n, lib().eavsr_conv3x3_x6s_tiles(h, w), cout), device=out.device, dtype=torch.float32)
-    if chan_partial:
-        tiles = (lib().eavsr_conv3x3_x6s_tiles(h, w) if use_x6s else lib().eavsr_conv5x5_wino_tiles(h, w) if use_wino5 else lib().eavsr_conv3x3_wino4_tiles(h, w) if use_wino4 else _wino_tiles(h, w) if use_wino
-                 else lib().eavsr_conv2d_tiles(n, h, w, k))
-        part = torch.empty((n, tiles, cout), device=out.device, dtype=torch.float32)
-    if residual is not None:
-        residual = _chk(residual, "residual")
-        if residual.shape != out.shape:
-            raise ValueError("residual shape mismatch")
-    d = N.ConvDesc()
-    for i in range(5):
-        d.src[i] = _p(srcs[i]) if i < len(srcs) else None
-        d.src_c[i] = int(srcs[i].shape[1]) if i < len(srcs) else 0
-    d.n_src = len(srcs)
-    d.ksize = k
-    d.weight_packed = _p(wp) if wp is not None else None
-    d.bias = _p(b)
-    d.residual = _p(residual)
-    d.out = _p(out)
-    d.chan_partial = _p(part)
-    d.n, d.h, d.w, d.cin, d.cout = n, h, w, cin, cout
-    d.act = ACT[act]
-    d.slope = float(slope)
-    d.res_scale = _p(res_scale)
-    d.sum_mul = _p(sum_mul)
+    fam = r.family[:-3] if ca is not None else r.family
+    l_act = None if "sigmoid" in r.post else act
+    l_res, l_scale = (None, None) if "scale_residual" in r.post else (residual, res_scale)
+    l_mul = None if "plane_sum" in r.post else sum_mul
+    aux = h16_code(CONV3_H16) if fam in ("h16x1", "h16g") else -1 if sigmoid_from is None or "sigmoid" in r.post else int(sigmoid_from)
+    # ---- allocate, describe, launch
+    dev = srcs[0].device
+    out = torch.empty((n, cout, h, w), device=dev, dtype=torch.float32)
+    # The kernels with 16-byte stores want an aligned output.  Not a routing input: the caching allocator aligns a fresh tensor
+    # far beyond 16 bytes, so this never chose a route -- an allocator that stops doing so must not pass silently.
+    if out.data_ptr() % 16:
+        raise RuntimeError(f"conv2d: the output was allocated at {out.data_ptr():#x}, not on a 16-byte boundary")
+    part = torch.empty((n, r.part_tiles, cout), device=dev, dtype=torch.float32) if chan_partial or l_mul is not None else None
+    xs = torch.empty_like(ca[1]) if ca is not None and ca_out else None
+    _, desc_weight, own_weight, call, what = _CONV_KERNELS[fam]
+    wd = None if desc_weight is None else desc_weight(weights, aux)
+    wq = None if own_weight is None else own_weight(weights, dgrad, aux)
+    b = _bias_of(biases)
+    d = _conv_desc(srcs, k, cout, wd, b, out, l_act, slope)
+    d.residual, d.chan_partial, d.res_scale, d.sum_mul = _p(l_res), _p(part), _p(l_scale), _p(l_mul)
     pieces = None
-    if (border and chan_partial and use_wino4 and cout == 64 and cin % 8 == 0 and ca is None and not pixel_shuffle2 and res_scale is None
-            and lib().eavsr_wino4_schedule() == 1):
+    if r.pieces:
         pr, pc = C.c_int32(0), C.c_int32(0)
         N.check(lib().eavsr_conv3x3_wino4_border_pieces(h, w, C.byref(pr), C.byref(pc)), "conv3x3_wino4_border_pieces")
         stride = max(pr.value, pc.value)
-        pieces = BorderPieces(torch.empty((n, 4, stride, 64), device=out.device, dtype=torch.float32), pr.value, pc.value)
+        pieces = BorderPieces(torch.empty((n, 4, stride, 64), device=dev, dtype=torch.float32), pr.value, pc.value)
         d.border_pieces, d.border_stride = _p(pieces.data), stride
-    if pixel_shuffle2 and use_wino4:
+    if pixel_shuffle2 and "pixel_shuffle" not in r.post:
         d.out_shuffle = 2
         out = out.view(n, cout // 4, 2 * h, 2 * w)      # the same buffer, written in the shuffled layout
-    xs = None
     if ca is not None:
-        scale, cx = _chk(ca[0], "ca scale"), _chk(ca[1], "ca x")
-        if len(srcs) != 1 or cx.shape != srcs[0].shape or tuple(scale.shape) != (n, cin):
-            raise ValueError("ca=(scale, x): one source, x of the same shape, scale (n, cin)")
-        if not use_wino and (k != 3 or not ca_fusable(srcs[0], cout) or cx.data_ptr() % 16):
-            raise NotImplementedError("fused channel-attention prologue unavailable for this shape; use "
-                                      "scale_residual + conv2d (see ops.ca_fusable)")
-        d.ca_scale, d.ca_x = _p(scale), _p(cx)
-        if ca_out:
-            xs = torch.empty_like(cx)
-            d.ca_out = _p(xs)
-    elif ca_out:
-        raise ValueError("ca_out needs ca")
+        d.ca_scale, d.ca_x, d.ca_out = _p(ca[0]), _p(ca[1]), _p(xs)
     st = _stream(out)
-    px = float(n) * h * w
-    if use_x6s and precision == "bf16":
-        wq = _packed_conv3_bf16(weights, dgrad=dgrad)
-        _launch(f"conv3x3_{cin}to{cout}_bf16s", 2.0 * cin * cout * 9 * px,
-                4.0 * px * (cin + cout + (cout if residual is not None else 0)), out,
-                lambda: lib().eavsr_conv3x3_bf16x1s(C.byref(d), _p(wq), st), "conv3x3_bf16x1s")
-        return out if not (chan_partial or sum_mul is not None) else (out, part)
-    if use_x6s:
-        wq = _packed_conv_x6(weights, dgrad=dgrad)
-        _launch(f"conv3x3_{cin}to{cout}_x6s", 2.0 * cin * cout * 9 * px,
-                4.0 * px * (cin + cout + (cout if residual is not None else 0)), out,
-                lambda: lib().eavsr_conv3x3_f32x6s(C.byref(d), _p(wq), st), "conv3x3_f32x6s")
-        return out if not (chan_partial or sum_mul is not None) else (out, part)
-    if use_wino5:
-        wu = _packed_wino(weights, kind="f5")
-        _launch(f"conv5x5_{cin}to{cout}_wino", 2.0 * cin * cout * 25 * px,
-                4.0 * px * (cin + cout + (cout if residual is not None else 0)), out,
-                lambda: lib().eavsr_conv5x5_wino_f32(C.byref(d), _p(wu), st), "conv5x5_wino")
-        return out if not chan_partial else (out, part)
-    if use_wino4:
-        wu = _packed_wino(weights, four=True)
-        _launch(f"conv3x3_{cin}to{cout}_wino4" + ("_ca" if ca is not None else ""), 2.0 * cin * cout * 9 * px,
-                4.0 * px * (cin * (1 if ca is None else (3 if ca_out else 2)) + cout + (cout if residual is not None else 0)), out,
-                lambda: lib().eavsr_conv3x3_wino4_f32(C.byref(d), _p(wu), st), "conv3x3_wino4")
-        res = [out] + ([part] if chan_partial else []) + ([xs] if xs is not None else []) + ([pieces] if border else [])
-        return res[0] if len(res) == 1 else tuple(res)
-    if use_wino:
-        wu = _packed_wino(weights)
-        _launch(f"conv3x3_{cin}to{cout}_wino" + ("_ca" if ca is not None else ""), 2.0 * cin * cout * 9 * px,
-                4.0 * px * (cin * (1 if ca is None else (3 if ca_out else 2)) + cout + (cout if residual is not None else 0)), out,
-                lambda: lib().eavsr_conv3x3_wino_f32(C.byref(d), _p(wu), st), "conv3x3_wino")
-        res = [out] + ([part] if chan_partial else []) + ([xs] if xs is not None else [])
-        return res[0] if len(res) == 1 else tuple(res)
-    if CONV_MODE == "bf16x9" and x9_ok and lib().eavsr_conv2d_tile_rows(n, h, w, 3) == 32:
-        wx = _packed_x9(weights)
-        _launch(f"conv3x3_{cin}to{cout}_x9", 2.0 * cin * cout * 9 * px,
-                4.0 * px * (cin + cout + (cout if residual is not None else 0)), out,
-                lambda: lib().eavsr_conv3x3_f32x9(C.byref(d), _p(wx), st), "conv3x3_f32x9")
-        return out if not chan_partial else (out, part)
-    _launch(f"conv{k}x{k}_{cin}to{cout}" + ("_ca" if ca is not None else ""), 2.0 * cin * cout * k * k * px,
-            4.0 * px * (cin * (1 if ca is None else (3 if ca_out else 2)) + cout + (cout if residual is not None else 0)), out,
-            lambda: lib().eavsr_conv2d_f32(C.byref(d), st), "conv2d")
-    if not chan_partial and xs is None:
-        return out
-    res = [out]
-    if chan_partial:
-        res.append(part)
-    if xs is not None:
-        res.append(xs)
-    return tuple(res)
+    flops, nbytes = _conv_cost(n, h, w, k, cin, cout, l_res is not None, 1 if ca is None else 3 if ca_out else 2)
+    _launch(r.name, flops, nbytes, out, lambda: call(lib(), d, _p(wq), aux, st), what)
+    # ---- the second step of a fallback form
+    for step in r.post:
+        if step == "plane_sum":
+            part = plane_sum(out, sum_mul).view(n, 1, -1)
+        elif step == "scale_residual":
+            out = scale_residual(out, res_scale, residual)
+        elif step == "pixel_shuffle":
+            out = torch.nn.functional.pixel_shuffle(out, 2)
+        else:      # "sigmoid": the tail channels, and `act` on the others
+            out[:, sigmoid_from:] = torch.sigmoid(out[:, sigmoid_from:])
+            if ACT[act] == 1:
+                out[:, :sigmoid_from].clamp_(min=0.0)
+            elif ACT[act] == 2:
+                torch.nn.functional.leaky_relu(out[:, :sigmoid_from], float(slope), inplace=True)
+    res = [out] + ([part] if part is not None else []) + ([xs] if xs is not None else []) + ([pieces] if border else [])
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 # ------------------------------------------------------------------------------------------

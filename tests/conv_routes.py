@@ -529,6 +529,25 @@ def cases() -> Tuple[Case, ...]:
     return tuple(out)
 
 
+@contextlib.contextmanager
+def case_setup(ops, case):
+    """the case's modes, thresholds, route batch and grad mode for the body; everything is put back on exit"""
+    m, thr = case.m, dict(case.thr)
+    was = ops.CONV5_MODE, ops.CONV7_MODE, ops.CONV3_H16
+    with contextlib.ExitStack() as st:
+        st.enter_context(ops.modes(conv=m["conv"]))      # a lab mode on the product library: LabBuildRequired = a skip (conftest.py)
+        st.enter_context(thresholds(ops, thr["wino_min"], thr["x6s_max"], m["small"]))
+
+        def back():
+            ops.CONV5_MODE, ops.CONV7_MODE, ops.CONV3_H16 = was
+        st.callback(back)
+        ops.CONV5_MODE, ops.CONV7_MODE = m["conv5"], m["conv7"]
+        ops.set_conv3_h16(m["h16"])
+        st.enter_context(ops.route_batch(case.route_batch))
+        st.enter_context(torch.enable_grad() if m["grad"] else torch.no_grad())
+        yield
+
+
 # ------------------------------------------------------------------------------------------ a case's tensors and its reference
 @functools.lru_cache(maxsize=128)
 def inputs(n, h, w, k, chans, couts, opts) -> dict:

@@ -1,7 +1,11 @@
-"""The helper behind tests/test_hip_conv_routes.py on the CPU: `predict_route` names every product route somewhere in the case
-matrix and changes sides exactly at each gate, `reference` agrees with a plain torch restatement of every option, the threshold
-context manager restores what it found, and `boundary_shapes` returns the launches next to a threshold.  The tile counts come from
-the library's host-side counters (no device)."""
+"""The router of ops.conv2d on the CPU.  `ops.conv_route` -- the route decision over plain numbers -- gives, for every case of the
+matrix, the kernels, families, tile count and border pieces that tests/conv_routes.py's independent `predict_route` names (what
+tests/test_hip_conv_routes.py then checks against the launches themselves), and the public gates `x6s_takes`, `wgrad_bf16_takes` and
+`ca_fusable` agree with it at the boundary shapes.  The helper itself: `predict_route` names every product route somewhere in the
+case matrix and changes sides exactly at each gate, `reference` agrees with a plain torch restatement of every option, the
+threshold context manager restores what it found, and `boundary_shapes` returns the launches next to a threshold.  The tile counts
+come from the library's host-side counters (no device)."""
+import contextlib
 import types
 
 import pytest
@@ -12,9 +16,8 @@ from tests import conv_routes as R
 
 
 def test_every_product_route_is_asserted_by_some_case():
-    """each kernel family _conv2d, _conv3x3_smallco, _conv_x6, _conv_h16x1 and _conv3x3_h16g can launch on the product library (and
-    the two second steps of the fallback forms) is in the predicted kernel list of at least one case; with the lab library loaded
-    the retired schedules are too"""
+    """each kernel family of ops._CONV_KERNELS that conv2d can launch on the product library (and the two second steps of the
+    fallback forms) is in the predicted kernel list of at least one case; with the lab library loaded the retired schedules are too"""
     seen, seen_lab = set(), set()
     for c in R.cases():
         seen.update(c.route(lab=False).families)
@@ -23,6 +26,103 @@ def test_every_product_route_is_asserted_by_some_case():
     assert not seen & set(R.LAB_FAMILIES) - {"x9"} and not {"wino", "wino4_ca", "x9"} - seen_lab, (seen, seen_lab)
     for name, (shape, k, chans, couts, md) in R.ROUTE_SHAPES.items():
         assert R.predict_route(*shape, k, chans, couts, modes=md, thr=R.LOWERED).families == (R.ROUTE_FAMILY[name],), name
+    from eavsr_amd import ops
+    assert {f[:-3] if f.endswith("_ca") else f for f in R.PRODUCT_FAMILIES + R.LAB_FAMILIES} - {"scale_residual", "plane_sum"} == set(ops._CONV_KERNELS)
+
+
+@pytest.fixture
+def ops():
+    from eavsr_amd import ops as _ops
+    state = lambda: (_ops.WINO_MIN_TILES, _ops.X6S_MAX_TILES, _ops.CONV3_SMALL, _ops.CONV_MODE, _ops.CONV5_MODE, _ops.CONV7_MODE,
+                     _ops.CONV3_H16, _ops._ROUTE_BATCH, torch.is_grad_enabled())
+    before = state()
+    yield _ops
+    assert state() == before, "a test of this file left a threshold, a mode, a pinned route batch or a grad mode behind"
+
+
+@contextlib.contextmanager
+def _under(ops, case):
+    """the body under the case's setup; yields False instead, where that is a lab-only conv mode on the product library (what the
+    GPU test skips: LabBuildRequired)"""
+    with contextlib.ExitStack() as st:
+        try:
+            st.enter_context(R.case_setup(ops, case))
+        except ops.LabBuildRequired:
+            assert case.m["conv"] in R.LAB_MODES and not ops.lab_available(), case.id
+            yield False
+            return
+        yield True
+
+
+def _route_of(ops, case, **kw):
+    """ops.conv_route on the plain facts of a case (under its setup): a pointer `o` floats past a 16-byte boundary has the address
+    residue 4 o"""
+    o, off = case.o, dict(case.offsets)
+    mod = lambda name: 4 * off.get(name, 0) % 16
+    facts = dict(act=o["act"], residual=o["residual"], chan_partial=o["chan_partial"], ca=o["ca"], ca_out=o["ca_out"],
+                 pixel_shuffle2=o["pixel_shuffle2"], res_scale=o["res_scale"], sum_mul=o["sum_mul"], dgrad=o["dgrad"],
+                 sigmoid_from=o["sigmoid_from"], border=o["border"], precision=o["precision"], src_mod=[mod("src")] * len(case.chans),
+                 residual_mod=mod("residual"), ca_mod=mod("ca_x"), sum_mul_mod=mod("sum_mul"), sum_mul_shaped=True,
+                 grad=torch.is_grad_enabled())
+    return ops.conv_route(case.n, case.h, case.w, case.k, case.chans, case.cout, len(case.couts), case.bias, **{**facts, **kw})
+
+
+def test_conv_route_names_what_predict_route_names_for_every_case(ops):
+    """the route decision of ops.py against the restatement that never looked at it, on the whole matrix: the same exception type
+    where one is predicted; otherwise the same kernel names in launch order (the second step of a fallback form included), the
+    same families, tile count of the sums and border pieces"""
+    lab = ops.lab_available()
+    differ, left_out = [], 0
+    for c in R.cases():
+        want = c.route(lab=lab)
+        with _under(ops, c) as ok:
+            if not ok:
+                left_out += 1
+                continue
+            try:
+                got = _route_of(ops, c)
+                got = (None, got.kernels, got.families, got.part_tiles, got.pieces)
+            except (ValueError, NotImplementedError) as e:
+                got = (type(e).__name__, (), (), None, False)
+        if got != (want.raises, want.kernels, want.families, want.part_tiles, want.pieces):
+            differ.append((c.id, got, want))
+    assert not differ, (len(differ), differ[:5])
+    assert left_out == (0 if lab else sum(c.m["conv"] in R.LAB_MODES for c in R.cases()))
+
+
+def test_public_gates_agree_with_conv_route_at_the_boundary_shapes(ops):
+    """x6s_takes / wgrad_bf16_takes (what autograd and the model ask before a launch) and ca_fusable share their predicates with
+    the router: on each side of every group-A gate, the crop-sized kernel runs exactly where x6s_takes says and the Winograd kernel
+    does not take the launch first; the bf16 forms and the in-place input-gradient weight follow it; the bf16 weight gradient asks
+    w % 4 == 0 on top; the prologue is accepted exactly where ca_fusable says"""
+    seen = set()
+    for c in R.cases():
+        if c.group != "A" or c.k != 3:
+            continue
+        with _under(ops, c) as ok:
+            if not ok:
+                continue
+            takes = ops.x6s_takes(c.n, c.h, c.w)
+            plain = ops.conv_route(c.n, c.h, c.w, 3, (64,), 64)
+            x6s = takes and not plain.family.startswith("wino")
+            seen.add((c.gate.split("-")[0], takes, plain.family))
+            assert (plain.family == "x6s") == x6s, (c.id, takes, plain)
+            assert (ops.conv_route(c.n, c.h, c.w, 3, (64,), 64, precision="bf16").family == "bf16s") == x6s, c.id
+            dg = ops.conv_route(c.n, c.h, c.w, 3, (64,), 64, bias=False, dgrad=True)
+            assert dg.materialise == (not x6s) and dg.family == plain.family, (c.id, dg)
+            t = torch.empty(c.n, 1, c.h, c.w)
+            assert ops.wgrad_bf16_takes([t], [[t]], 3) == (takes and c.w % 4 == 0), c.id
+            assert not ops.wgrad_bf16_takes([t], [[t]], 5) and not ops.wgrad_bf16_takes([t], [[t[:, :, :, 1:]]], 3)
+            if c.o["ca"]:
+                try:
+                    fused = _route_of(ops, c).family.endswith("_ca")
+                except NotImplementedError:
+                    fused = False
+                assert ops.ca_fusable(torch.empty(c.n, 64, c.h, c.w), c.cout) == fused, c.id
+                seen.add(("ca", fused))
+    # both answers of each gate were seen
+    assert {("x6s_max", True, "x6s"), ("x6s_max", False, "direct"), ("wino_min", True, "x6s"), ("wino_min", True, "wino4"),
+            ("ca", True), ("ca", False)} <= seen, seen
 
 
 def test_every_gate_has_a_case_on_each_side_and_the_kernel_changes_exactly_there():

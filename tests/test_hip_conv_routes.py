@@ -3,8 +3,6 @@
 assert for the kernel family that ran.  Groups: A the launch-size gates from both sides, B every option on every route and its
 fallback form on the others (the combinations the docstring rules out raise before any launch), C pointers 4 / 8 / 12 bytes past a
 16-byte boundary, D one batch run whole and row by row under ops.route_batch, E degenerate sizes, F the 16-bit modes' routing."""
-import contextlib
-
 import pytest
 import torch
 
@@ -65,23 +63,7 @@ def _place(t, dev, off=0):
     return v
 
 
-@contextlib.contextmanager
-def _setup(ops, case):
-    """the case's modes, thresholds and route batch for the body; everything is put back on exit"""
-    m, thr = case.m, dict(case.thr)
-    was = ops.CONV5_MODE, ops.CONV7_MODE, ops.CONV3_H16
-    with contextlib.ExitStack() as st:
-        st.enter_context(ops.modes(conv=m["conv"]))      # a lab mode on the product library: LabBuildRequired = a skip (conftest.py)
-        st.enter_context(R.thresholds(ops, thr["wino_min"], thr["x6s_max"], m["small"]))
-
-        def back():
-            ops.CONV5_MODE, ops.CONV7_MODE, ops.CONV3_H16 = was
-        st.callback(back)
-        ops.CONV5_MODE, ops.CONV7_MODE = m["conv5"], m["conv7"]
-        ops.set_conv3_h16(m["h16"])
-        st.enter_context(ops.route_batch(case.route_batch))
-        st.enter_context(torch.enable_grad() if m["grad"] else torch.no_grad())
-        yield
+_setup = R.case_setup      # the case's modes, thresholds, route batch and grad mode (shared with tests/test_conv_routes_host.py)
 
 
 def _call(ops, case, dev, rows=slice(None)):

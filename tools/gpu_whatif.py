@@ -65,12 +65,22 @@ measure("no DCNv2 kernel")
 ops.dcnv2_il = orig_dcn
 # (5) the small-cout vector-ALU convolutions (64 -> 6 heads and 18 -> 2 of every pyramid level, conv_last): 112-184 registers per
 #     lane, so they cannot run beside a resident Winograd workgroup -- how much of their time is on the step's critical path?
-orig_small = ops._conv3x3_smallco
-ops._conv3x3_smallco = lambda x, weights, biases, act, slope, residual: cache.setdefault(
-    ("sc", tuple(x.shape), sum(int(w_.shape[0]) for w_ in weights)),
-    torch.zeros(x.shape[0], sum(int(w_.shape[0]) for w_ in weights), x.shape[2], x.shape[3], device=x.device))
+orig_conv2d = ops.conv2d
+def without(skip):
+    """ops.conv2d with the single-source calls of skip(ksize, cout) left out: a cached tensor of zeros in the output's shape"""
+    def f(srcs, weight, *a_, **k_):
+        xs_ = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
+        ws_ = [weight] if isinstance(weight, torch.Tensor) else list(weight)
+        co, ks = sum(int(w_.shape[0]) for w_ in ws_), int(ws_[0].shape[-1])
+        if len(xs_) != 1 or not skip(ks, co):
+            return orig_conv2d(srcs, weight, *a_, **k_)
+        x = xs_[0]
+        y = cache.setdefault(("conv", ks, tuple(x.shape), co), torch.zeros(x.shape[0], co, x.shape[2], x.shape[3], device=x.device))
+        return torch.nn.functional.pixel_shuffle(y, 2) if k_.get("pixel_shuffle2") else y
+    return f
+ops.conv2d = without(lambda ks, co: ks == 3 and co in (2, 3, 4, 6))
 measure("no small-cout convolutions")
-ops._conv3x3_smallco = orig_small
+ops.conv2d = orig_conv2d
 
 # (6) the predictor front end (co-resident: 46 registers, 21 KB of LDS)
 orig_fe = ops.adapt_frontend
@@ -82,17 +92,9 @@ except Exception as e:  # noqa: BLE001
     print("no adapt_frontend: skipped", type(e).__name__, e)
 ops.adapt_frontend = orig_fe
 # (7) the bf16x6 convolutions: the predictor's 5x5 heads, SPyNet's 7x7 layers (CU-owning kernels, 144-157 KB of LDS)
-orig_x6 = ops._conv_x6
-def no_x6(k_skip):
-    def f(x, weights, biases, act, slope):
-        if int(weights[0].shape[-1]) != k_skip:
-            return orig_x6(x, weights, biases, act, slope)
-        co = sum(int(w_.shape[0]) for w_ in weights)
-        return cache.setdefault(("x6", k_skip, tuple(x.shape), co), torch.zeros(x.shape[0], co, x.shape[2], x.shape[3], device=x.device))
-    return f
-ops._conv_x6 = no_x6(5)
+ops.conv2d = without(lambda ks, co: ks == 5)
 measure("no 5x5 heads convolution")
-ops._conv_x6 = no_x6(7)
+ops.conv2d = without(lambda ks, co: ks == 7)
 measure("no SPyNet 7x7 convolutions")
-ops._conv_x6 = orig_x6
+ops.conv2d = orig_conv2d
 measure("base again")
