@@ -196,6 +196,11 @@ SIGNATURES = {
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
     # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)
     "eavsr_resize_cubic_u8": (C.c_int, [vp] * 6 + [i32] * 6 + [vp]),
+    # the outgoing PNG file: scanline filters and a Huffman-only deflate coder (csrc/png.hip; additions to ABI 32)
+    "eavsr_png_filter_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
+    "eavsr_png_capacity": (C.c_int64, [i64, i64]),
+    "eavsr_deflate_workspace_bytes": (C.c_int64, [i32, i64, i64]),
+    "eavsr_deflate_huffman_u8": (C.c_int, [vp] * 5 + [i32, i64, i64, vp]),
     # LPIPS (AlexNet), the report's third column (csrc/lpips.hip; additions to ABI 32)
     "eavsr_lpips_conv_weight_elems": (C.c_int64, [i32, i32, i32]),
     "eavsr_lpips_pack_conv_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),

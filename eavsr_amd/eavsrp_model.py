@@ -566,7 +566,22 @@ def long_clip_options(opt=None):
         cc = env == "1"
     elif not isinstance(cc, bool):
         raise ValueError(f"opt.cpu_cache={cc!r}: True or False")
+    png_encoder_option(opt)      # validated with the others; read where frames are written (harness.super_resolve)
     return fc, cc
+
+
+def png_encoder_option(opt=None) -> str:
+    """"host" or "device": who encodes the PNG files `harness.super_resolve` writes -- `opt.png_encoder`, falling back to the
+    environment where the options do not carry it (EAVSR_PNG_ENCODER=host|device), "host" where neither does.  Not among the
+    reference's options."""
+    pe = getattr(opt, "png_encoder", None)
+    if pe is None:
+        pe = os.environ.get("EAVSR_PNG_ENCODER", "") or "host"
+        if pe not in ("host", "device"):
+            raise ValueError(f"EAVSR_PNG_ENCODER={pe!r}: host or device")
+    elif pe not in ("host", "device"):
+        raise ValueError(f"opt.png_encoder={pe!r}: 'host' or 'device'")
+    return pe
 
 
 class EAVSRPModel:
@@ -586,6 +601,7 @@ class EAVSRPModel:
         self.isTrain = getattr(opt, "isTrain", False)
         # opt.frame_chunk / opt.cpu_cache (not among the reference's options): the opt-in long-clip inference path (EAVSRP.forward_long)
         self.frame_chunk, self.cpu_cache = long_clip_options(opt)
+        self.png_encoder = png_encoder_option(opt)
         # opt.train_precision (not among the reference's options): the opt-in bf16 training mode (networks.set_train_precision)
         if getattr(opt, "train_precision", None) is not None:
             N.set_train_precision(opt.train_precision)

@@ -153,6 +153,101 @@ def read_png(path: str) -> Tensor:
     return torch.frombuffer(out, dtype=torch.uint8).view(h, w, c).permute(2, 0, 1).contiguous()
 
 
+def _png_file(idat: bytes, h: int, w: int, c: int) -> bytes:
+    """signature, IHDR (8-bit grey or RGB, no interlace), one IDAT holding `idat` (a complete zlib stream), IEND"""
+    return (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 0, 0, 0, 0))
+            + _png_chunk(b"IDAT", idat) + _png_chunk(b"IEND", b""))
+
+
+PNG_ENCODERS = ("host", "device")
+
+
+def check_png_encoder(encoder) -> str:
+    if encoder not in PNG_ENCODERS:
+        raise ValueError(f"png_encoder={encoder!r}: one of {PNG_ENCODERS}")
+    return encoder
+
+
+class _PngStaging:
+    """The host side of the device PNG encoder: two pinned staging buffers used in turn.  `enqueue(rgb8)` launches the
+    filter and entropy passes (`ops.png_encode`) on the current stream and, on a side stream behind them, the copy of the streams and
+    their sizes into one of the buffers, followed by an event; it returns a job without waiting for anything.  `files(job)` waits for
+    that job's event alone and wraps every stream into a file (the chunk CRC-32 is `zlib.crc32` over the compressed bytes, which are
+    on the host by then).  The compressed sizes are not known to the host when the copy is enqueued, so the copy covers every frame's
+    whole slot (`eavsr_png_capacity`); a copy sized to the data would need a wait in between.  A buffer is reused by the job after
+    the next one: take a job's files before enqueueing the second job after it."""
+
+    def __init__(self, stripe_rows: int = 32):
+        self.stripe_rows = stripe_rows
+        self.slots = [None, None]      # (pinned bytes, pinned sizes)
+        self.turn = 0
+        self.side = None
+
+    def _slot(self, nbytes: int, frames: int):
+        cur = self.slots[self.turn]
+        if cur is None or cur[0].numel() < nbytes or cur[1].numel() < frames:
+            cur = self.slots[self.turn] = (torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), torch.empty(frames, dtype=torch.int64, pin_memory=True))
+        self.turn ^= 1
+        return cur
+
+    def enqueue(self, rgb8: Tensor):
+        from . import ops
+        enc = ops.png_encode(rgb8, self.stripe_rows)      # refuses a CPU tensor before anything else happens
+        f, h, w, c = (int(v) for v in rgb8.shape)
+        host_bytes, host_sizes = self._slot(enc.data.numel(), f)
+        device = rgb8.device
+        if self.side is None or self.side.device != device:
+            self.side = torch.cuda.Stream(device)
+        self.side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(self.side):
+            host_bytes[:enc.data.numel()].copy_(enc.data, non_blocking=True)
+            host_sizes[:f].copy_(enc.sizes, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self.side)
+        enc.data.record_stream(self.side)
+        enc.sizes.record_stream(self.side)
+        return {"done": done, "bytes": host_bytes, "sizes": host_sizes, "frames": f, "cap": enc.data.numel() // max(f, 1), "hwc": (h, w, c)}
+
+    @staticmethod
+    def files(job) -> List[bytes]:
+        job["done"].synchronize()
+        h, w, c = job["hwc"]
+        raw = job["bytes"].numpy()
+        sizes = job["sizes"][:job["frames"]].tolist()
+        return [_png_file(raw[i * job["cap"]:i * job["cap"] + n].tobytes(), h, w, c) for i, n in enumerate(sizes)]
+
+
+_STAGING: Dict[int, "_PngStaging"] = {}
+
+
+def _shared_staging(stripe_rows: int) -> "_PngStaging":
+    """the staging object `encode_png_frames` reuses between calls (its pinned buffers grow to the largest item and stay); each
+    call takes its files before it returns, so the two buffers are free again.  Not for concurrent use from several threads."""
+    if stripe_rows not in _STAGING:
+        _STAGING[stripe_rows] = _PngStaging(stripe_rows)
+    return _STAGING[stripe_rows]
+
+
+def encode_png_frames(rgb8: Tensor, stripe_rows: int = 32) -> List[bytes]:
+    """uint8 device frames (F, H, W, C), C 1 or 3 (`ops.rgb8` / `ops.frame_metrics(.., rgb8=True)`) -> F complete PNG files as bytes:
+    signature, IHDR, one IDAT, IEND.  Scanline filters and the entropy coder run on the device (`ops.png_encode`: per-row filter
+    choice, Huffman coding without LZ77 matching); the host adds the chunk framing and CRC-32.  `read_png` and any PNG reader decode
+    them; the pixels are the input's."""
+    if not isinstance(rgb8, torch.Tensor) or rgb8.dim() != 4 or rgb8.dtype != torch.uint8:
+        raise ValueError(f"encode_png_frames: uint8 (F, H, W, C), got {getattr(rgb8, 'dtype', type(rgb8))} {tuple(getattr(rgb8, 'shape', ()))}")
+    staging = _shared_staging(stripe_rows)
+    return staging.files(staging.enqueue(rgb8.contiguous()))
+
+
+def _write_file(path: str, data: bytes) -> str:
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path
+
+
 def save_visuals(res: Dict[str, Tensor], fnames: Sequence, root: str, load_iter="0", full_res: bool = False) -> List[str]:
     """The frame writing of test_basic.py:85-92 for one test item: frame i of `res['data_sr_seq'][0]` goes to
     `<root>/sr_{full|patch}_<load_iter>/<fname[i][0][:3]>/<fname[i][0][-9:]>` (the scene is the first three characters of the
@@ -180,17 +275,23 @@ def _frame_name(fnames, i: int, b: int = 0) -> str:
     return name[b] if isinstance(name, (list, tuple)) else name
 
 
-def save_frames_rgb8(rgb8: Tensor, fnames: Sequence, root: str, load_iter="0", full_res: bool = False) -> List[str]:
+def save_frames_rgb8(rgb8: Tensor, fnames: Sequence, root: str, load_iter="0", full_res: bool = False, encoder: str = "host") -> List[str]:
     """`save_visuals` for frames that already are 8-bit interleaved: rgb8 (t, H, W, C) uint8, the quantised frames of one item as
-    `ops.frame_metrics(..., rgb8=True)` / `ops.rgb8` leave them; the same paths (test_basic.py:85-92)."""
+    `ops.frame_metrics(..., rgb8=True)` / `ops.rgb8` leave them; the same paths (test_basic.py:85-92).  encoder="device": the files
+    come from `encode_png_frames` (the frames must be on the device) -- other bytes, the same pixels."""
+    check_png_encoder(encoder)
     if rgb8.dim() != 4 or rgb8.dtype != torch.uint8:
         raise ValueError(f"save_frames_rgb8: uint8 (t, H, W, C), got {rgb8.dtype} {tuple(rgb8.shape)}")
-    frames = rgb8.cpu()      # one copy for the item
+    files = encode_png_frames(rgb8) if encoder == "device" else None
+    frames = rgb8.cpu() if files is None else rgb8      # one copy for the item
     paths = []
     for i in range(frames.shape[0]):
         name = _frame_name(fnames, i)
         folder = os.path.join(root, "sr_%s_%s" % ("full" if full_res else "patch", load_iter), name[:3])
-        paths.append(write_png(frames[i], os.path.join(folder, name[-9:]), hwc=True))
+        if files is None:
+            paths.append(write_png(frames[i], os.path.join(folder, name[-9:]), hwc=True))
+        else:
+            paths.append(_write_file(os.path.join(folder, name[-9:]), files[i]))
     return paths
 
 
@@ -407,7 +508,7 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
 
 
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
-                  frame_chunk: Optional[int] = None, cache: str = "device", lpips=None) -> Dict:
+                  frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -417,11 +518,22 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
       * writes `<out_dir>/<name>` for every frame (of clip 0) from the kernel's 8-bit frames (`ops.rgb8`) when `out_dir` is given,
       * scores the chunk against `hr` (same layouts as `frames`, at the output size) with `ops.frame_metrics` -- and `lpips`, an
         `eavsr_amd.lpips.LPIPSAlex` or the path of its weights -- when `hr` is given.
+    `png_encoder`: "host" (the default: `write_png`, zlib on one host thread, after a blocking copy of the frames) or "device"
+    (filters and entropy coding on the device, `ops.png_encode`; the sink then enqueues the encoder and an asynchronous copy
+    of the compressed bytes into one of two pinned buffers and waits for nothing; the files of a chunk are written when the next
+    chunk has been enqueued, the last chunk's when the forward has ended).  None: `opt.png_encoder` of a model wrapper, else
+    EAVSR_PNG_ENCODER, else "host".  The files differ in bytes, not in pixels; 'written' and the report are the same.
     `names`: one name per frame (default: the paths' base names, else `000_00000.png`, ...); a name's first three characters are its
     scene in the report.  Returns 'frames', 'seconds' (device-synchronised on both sides), 'frames_per_s', 'peak_bytes'
     (`torch.cuda.max_memory_allocated` over the run), 'written', and with `hr` the 'frame_psnr' / 'frame_ssim' / 'frame_names' /
     'report' (/ 'frame_lpips') of `evaluate(per_frame=True)`, in (n, t) order."""
     from . import ops
+    if png_encoder is None:      # a model wrapper has read its options already; the bare network has none
+        png_encoder = getattr(model, "png_encoder", None)
+    if png_encoder is None:
+        from .eavsrp_model import png_encoder_option
+        png_encoder = png_encoder_option(getattr(model, "opt", None))
+    check_png_encoder(png_encoder)
     net = getattr(model, "netEAVSRP", model)
     device = next(net.parameters()).device
     if device.type != "cuda":
@@ -457,6 +569,14 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         raise ValueError("super_resolve: lpips needs hr")
     written: List[str] = []
     sse_parts, ssim_parts, lpips_parts, counts = [], [], [], []
+    staging = _PngStaging() if (out_dir is not None and png_encoder == "device") else None
+    pending = []      # at most one (job, paths): the chunk whose files are still on their way
+
+    def write_pending():
+        while pending:
+            job, targets = pending.pop(0)
+            for path, data in zip(targets, _PngStaging.files(job)):
+                written.append(_write_file(path, data))
 
     def hr_chunk(a, b):
         part = hr[:, a:b]
@@ -482,7 +602,11 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                 lpips_parts.append(lpips(flat, ref, 255.0).view(n, k))
         elif out_dir is not None:
             rgb8 = ops.rgb8(flat, 255.0)
-        if out_dir is not None:
+        if staging is not None:
+            job = staging.enqueue(rgb8[:k])      # clip 0, as save_visuals; nothing here waits for the device
+            write_pending()                      # the previous chunk's files, while this chunk's encoder runs
+            pending.append((job, [os.path.join(out_dir, _frame_name(names, first + j)) for j in range(k)]))
+        elif out_dir is not None:
             host = rgb8[:k].cpu()      # clip 0, as save_visuals
             for j in range(k):
                 written.append(write_png(host[j], os.path.join(out_dir, _frame_name(names, first + j)), hwc=True))
@@ -492,6 +616,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     t0 = time.time()
     with torch.no_grad():
         net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink)
+    write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,

@@ -1637,6 +1637,102 @@ def resize_cubic_u8(frames: Tensor, size: Tuple[int, int], out: Optional[Tensor]
 
 
 # ------------------------------------------------------------------------------------------
+# the outgoing PNG file: scanline filters and a Huffman-only deflate coder  (csrc/png.hip)
+# ------------------------------------------------------------------------------------------
+class Deflated(NamedTuple):
+    """F zlib streams in one buffer: frame f is data[offsets[f] : offsets[f] + sizes[f]]; offsets / sizes are int64 on the device"""
+    data: Tensor
+    offsets: Tensor
+    sizes: Tensor
+
+
+def _bytes_on_device(t, what: str, dim: int) -> Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: tensor is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if t.dtype != torch.uint8 or t.dim() != dim:
+        raise ValueError(f"{what}: a uint8 tensor of {dim} dimensions, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: must be contiguous (nothing is copied here)")
+    return t
+
+
+def png_filter(rgb8: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """uint8 frames (F, H, W, C), C 1 or 3 -- what `rgb8` / `frame_metrics(.., rgb8=True)` leave -> the PNG scanlines (F, H, 1 + W C):
+    byte 0 of a row is its filter type (0 - 4), chosen per row by the smallest sum of absolute signed filtered bytes, ties to the
+    lowest number (libpng's default heuristic); neighbours outside the image are 0.  `out`: a contiguous uint8 tensor of that shape
+    on the same device to write into (returned)."""
+    x = _bytes_on_device(rgb8, "png_filter", 4)
+    f, h, w, c = (int(v) for v in x.shape)
+    if c not in (1, 3) or min(h, w) < 1:
+        raise ValueError(f"png_filter: (F, H, W, C) with C 1 or 3 and H, W >= 1, got {tuple(x.shape)}")
+    shape = (f, h, 1 + w * c)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.uint8)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous()
+          or out.device != x.device):
+        raise ValueError(f"png_filter: out: a contiguous uint8 {shape} tensor on {x.device}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    if f == 0:
+        return out
+    st = _stream(x)
+    _launch("png_filter_u8", 0.0, float(x.numel() + out.numel()), x,
+            lambda: lib().eavsr_png_filter_u8(_p(x), _p(out), f, h, w, c, st), "png_filter")
+    return out
+
+
+def deflate_huffman(data: Tensor, stripe_bytes: int, workspace: Optional[Tensor] = None) -> Deflated:
+    """uint8 (F, nbytes), any bytes -> F zlib streams that inflate to them, coded on the device (csrc/png.hip): every stripe of
+    `stripe_bytes` is one dynamic-Huffman block of literals only (no LZ77 matching), or stored blocks where that is not smaller.
+    Returns `Deflated(data, offsets, sizes)`: the streams lie at offsets[f] = f x capacity in a buffer allocated from the shape
+    alone (`eavsr_png_capacity`), sizes[f] bytes each; nothing is read back, so the call does not wait for the device.
+    `workspace`: a uint8 tensor of at least `deflate_workspace_bytes(F, nbytes, stripe_bytes)` bytes to reuse between calls."""
+    x = _bytes_on_device(data, "deflate_huffman", 2)
+    f, nbytes = (int(v) for v in x.shape)
+    stripe = int(stripe_bytes)
+    cap = lib().eavsr_png_capacity(nbytes, stripe)
+    need = lib().eavsr_deflate_workspace_bytes(f, nbytes, stripe)
+    if cap < 0 or need < 0:
+        raise ValueError(f"deflate_huffman: {lib().eavsr_last_error().decode(errors='replace')}")
+    if workspace is None:
+        workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.numel() < need
+          or not workspace.is_contiguous() or workspace.device != x.device):
+        raise ValueError(f"deflate_huffman: workspace: a contiguous uint8 tensor of at least {need} bytes on {x.device}")
+    out = torch.empty(f * cap, device=x.device, dtype=torch.uint8)
+    offsets = torch.empty(f, device=x.device, dtype=torch.int64)
+    sizes = torch.empty(f, device=x.device, dtype=torch.int64)
+    if f == 0:      # nothing to launch (and an empty tensor has no address to pass)
+        return Deflated(out, offsets, sizes)
+    st = _stream(x)
+    # bytes: the input is read twice (histogram, packing); the streams are written, then read and written again by the gather --
+    # their size is data, so the profile counts the two reads alone, a lower bound
+    _launch("deflate_huffman_u8", 0.0, 2.0 * x.numel(), x,
+            lambda: lib().eavsr_deflate_huffman_u8(_p(x), _p(out), _p(offsets), _p(sizes), _p(workspace), f, nbytes, stripe, st),
+            "deflate_huffman")
+    return Deflated(out, offsets, sizes)
+
+
+def deflate_workspace_bytes(frames: int, nbytes: int, stripe_bytes: int) -> int:
+    need = lib().eavsr_deflate_workspace_bytes(int(frames), int(nbytes), int(stripe_bytes))
+    if need < 0:
+        raise ValueError(f"deflate_workspace_bytes: {lib().eavsr_last_error().decode(errors='replace')}")
+    return int(need)
+
+
+def png_encode(rgb8: Tensor, stripe_rows: int = 32) -> Deflated:
+    """uint8 frames (F, H, W, C), C 1 or 3 -> the IDAT payload of every frame's PNG file: `png_filter`, then `deflate_huffman` with
+    stripes of `stripe_rows` whole scanlines.  (`harness.encode_png_frames` wraps the payloads into files.)"""
+    x = _bytes_on_device(rgb8, "png_encode", 4)
+    if isinstance(stripe_rows, bool) or not isinstance(stripe_rows, int) or stripe_rows < 1:
+        raise ValueError(f"png_encode: stripe_rows={stripe_rows!r}: a positive number of scanlines")
+    rows = png_filter(x)
+    f, h, r = (int(v) for v in rows.shape)
+    return deflate_huffman(rows.view(f, h * r), min(stripe_rows, h) * r)
+
+
+# ------------------------------------------------------------------------------------------
 # LPIPS (AlexNet), the report's third column  (psnr_total.py:27-35; csrc/lpips.hip)
 # ------------------------------------------------------------------------------------------
 _lpips_pack_cache = WeightCache()

@@ -763,6 +763,30 @@ int eavsr_gather_pairs_u8(const uint8_t* lr_store, const uint8_t* hr_store, cons
  * misaligned tables: -2.  F = 0: nothing is launched. */
 int eavsr_resize_cubic_u8(const uint8_t* in, uint8_t* out, const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs,
                           const int16_t* ycoef, int32_t F, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, void* stream);
+/* ---- the outgoing PNG file: scanline filters and a Huffman-only deflate coder (added to ABI 32, nothing above changes) -----------------
+ * csrc/png.hip.  No global atomics; two calls on equal input write equal bytes.
+ *
+ * Filter pass: in (F, H, W, C) uint8, C 1 or 3 (what eavsr_rgb8_f32 / eavsr_frame_metrics_f32 leave) -> out (F, H, 1 + W C): byte 0 of
+ * every row is its PNG filter type, then the filtered bytes.  The type is chosen per row: of filters 0 (none), 1 (sub), 2 (up),
+ * 3 (average), 4 (Paeth) the one whose filtered bytes, read as signed, have the smallest sum of absolute values; a tie goes to the
+ * lowest number.  Neighbours outside the image (left of column 0, above row 0 of every frame) are 0.  Any alignment.
+ * NULL pointer: -1; C not 1 or 3, H or W < 1, F > 65535, W C > 2^24, H (W C + 1) > 2^31 - 1: -2.  F = 0: nothing is launched. */
+int eavsr_png_filter_u8(const uint8_t* in, uint8_t* out, int32_t F, int32_t H, int32_t W, int32_t C, void* stream);
+/* Entropy pass: in (F, nbytes) uint8, any bytes -> F zlib streams (RFC 1950 / 1951) that inflate to them.  A frame is cut into stripes
+ * of stripe_bytes (the last one shorter); a stripe becomes ONE non-final dynamic-Huffman block of literals and end-of-block only (one
+ * distance code of zero bits; code lengths <= 15 bits, code-length code <= 7 bits) followed by an empty stored block, so that it ends on
+ * a byte boundary -- or, where that is not smaller, stored blocks of at most 65535 bytes.  A frame's stream is 78 01, its stripes, the
+ * final block 03 00 and the big-endian Adler-32 of its bytes (computed per stripe on the device, folded in stripe order).
+ *   eavsr_png_capacity(nbytes, stripe_bytes): bytes of ONE frame's slot in `out` (from the shape alone):
+ *       stripes x (stripe_bytes + 5 ceil(stripe_bytes / 65535) + 9) + 8, with stripe_bytes taken as min(stripe_bytes, nbytes).
+ *   out: F slots of that many bytes; frame f's stream starts at offsets[f] = f x capacity and is sizes[f] bytes long (both DEVICE int64).
+ *   workspace: eavsr_deflate_workspace_bytes(F, nbytes, stripe_bytes) bytes, 8-byte aligned, as offsets and sizes.
+ * NULL pointer: -1; F > 65535, nbytes or stripe_bytes outside 1 .. 2^31 - 1, more than 65535 stripes per frame, misaligned
+ * workspace / offsets / sizes: -2 (the two size queries return -2 as well).  F = 0: nothing is launched. */
+int64_t eavsr_png_capacity(int64_t nbytes, int64_t stripe_bytes);
+int64_t eavsr_deflate_workspace_bytes(int32_t F, int64_t nbytes, int64_t stripe_bytes);
+int eavsr_deflate_huffman_u8(const uint8_t* in, uint8_t* out, int64_t* offsets, int64_t* sizes, void* workspace, int32_t F, int64_t nbytes,
+                             int64_t stripe_bytes, void* stream);
 /* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
  * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
  * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
