@@ -25,6 +25,7 @@ Out of scope here: file lists and option parsing, a host-memory store, random nu
 from __future__ import annotations
 
 import functools
+import os
 import random
 from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
@@ -181,6 +182,29 @@ def _interleaved(x: torch.Tensor) -> bool:
     return x.shape[3] in (1, 3) and x.shape[1] not in (1, 3)
 
 
+def _check_device_reader(reader: str, what: str) -> None:
+    if reader != "device":
+        raise ValueError(f"{what}: reader={reader!r}: a callable, or 'device' for harness.decode_png_frames")
+
+
+def _png_shape(path) -> Tuple[int, int, int]:
+    """(C, H, W) of the planes `harness.decode_png_frames(.., channels=3)` makes of a PNG file, from its chunks alone"""
+    with open(os.fspath(path), "rb") as f:
+        h, w, c, _ = harness.parse_png(f.read(), os.fspath(path))
+    return min(c, 3), h, w
+
+
+def _decode_files(paths, shape, dev, chunk: int) -> torch.Tensor:
+    """one PNG file per frame -> a preallocated uint8 (F, C, H, W) device tensor, `chunk` files per `decode_png_frames` call"""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"FramePairs: chunk {chunk}")
+    store = torch.empty((len(paths),) + tuple(shape), device=dev, dtype=torch.uint8)
+    for lo in range(0, len(paths), chunk):
+        harness.decode_png_frames(paths[lo:lo + chunk], dev, channels=3, out=store[lo:lo + chunk])
+    return store
+
+
 class FramePairs:
     """The store: every LR frame and its HR frame as bytes on the device, CHW.
 
@@ -213,12 +237,32 @@ class FramePairs:
 
     @classmethod
     def from_files(cls, lr_paths: Sequence[str], hr_paths: Optional[Sequence[str]], scale: int, n_seq: int,
-                   names: Optional[Sequence[str]] = None, device=None, reader=harness.read_png) -> "FramePairs":
-        """Read one file per frame.  `reader(path)` returns a uint8 (C, H, W) tensor or array; the default, `harness.read_png`, is
-        a pure-Python decoder and SLOW (seconds per full-size frame) -- pass your own (an imageio / cv2 / PIL wrapper returning
-        CHW bytes) for a real dataset.  Decoding speed is not this module's business; the store is built once."""
+                   names: Optional[Sequence[str]] = None, device=None, reader=harness.read_png, chunk: int = 16) -> "FramePairs":
+        """Read one file per frame.  `reader(path)` returns a uint8 (C, H, W) tensor or array; the default, `harness.read_png`, undoes
+        the PNG scanline filters in a Python loop (seconds per full-size frame).  reader="device" decodes non-interlaced 8-bit grey /
+        RGB / RGBA PNG files with `harness.decode_png_frames` instead: zlib in a thread pool, the scanline unfilter on the
+        device, `chunk` files at a time straight into the preallocated stores -- decoded frames never exist on the host.  The sizes
+        are checked on the first LR and HR file, before the bulk of the work.  Other formats: pass your own reader."""
         if hr_paths is not None and len(hr_paths) != len(lr_paths):
             raise ValueError(f"FramePairs.from_files: {len(lr_paths)} LR and {len(hr_paths)} HR files")
+        if isinstance(reader, str):
+            _check_device_reader(reader, "FramePairs.from_files")
+            scale, n_seq = int(scale), int(n_seq)
+            n = len(lr_paths)
+            if n_seq < 1 or n == 0 or n % n_seq != 0:
+                raise ValueError(f"FramePairs.from_files: {n} frames are not whole scenes of n_seq {n_seq}")
+            if names is not None and len(names) != n:
+                raise ValueError(f"FramePairs.from_files: {len(names)} names for {n} frames")
+            lr_shape = _png_shape(lr_paths[0])
+            if hr_paths is not None:
+                c, h, w = lr_shape
+                if scale < 1 or _png_shape(hr_paths[0]) != (c, scale * h, scale * w):
+                    raise ValueError(f"FramePairs.from_files: hr must be scale {scale} x lr {lr_shape} = {(c, scale * h, scale * w)}, "
+                                     f"got {_png_shape(hr_paths[0])} ({hr_paths[0]})")
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            lr = _decode_files(lr_paths, lr_shape, dev, chunk)
+            hr = _decode_files(hr_paths, _png_shape(hr_paths[0]), dev, chunk) if hr_paths is not None else None
+            return cls(lr, hr, scale, n_seq, names=names, device=dev)
         read = lambda paths: torch.stack([torch.as_tensor(np.asarray(reader(p))) for p in paths])
         return cls(read(lr_paths), read(hr_paths) if hr_paths is not None else None, scale, n_seq, names=names, device=device)
 
@@ -276,9 +320,22 @@ class FramePairs:
     @classmethod
     def from_wide_files(cls, wide_paths: Sequence[str], hr_paths: Optional[Sequence[str]], scale: int, n_seq: int,
                         names: Optional[Sequence[str]] = None, device=None, reader=harness.read_png, chunk: int = 16) -> "FramePairs":
-        """`from_wide` from one file per frame, read `chunk` wide files at a time (`reader`: see `from_files`)."""
+        """`from_wide` from one file per frame, read `chunk` wide files at a time (`reader`: see `from_files`).  reader="device": a
+        chunk of wide frames is decoded on the device (`harness.decode_png_frames`) and resized there; the HR files are decoded in
+        chunks into a preallocated device tensor."""
         if hr_paths is not None and len(hr_paths) != len(wide_paths):
             raise ValueError(f"FramePairs.from_wide_files: {len(wide_paths)} wide and {len(hr_paths)} HR files")
+        if isinstance(reader, str):
+            _check_device_reader(reader, "FramePairs.from_wide_files")
+            if len(wide_paths) == 0:
+                raise ValueError("FramePairs.from_wide_files: 0 frames")
+            if hr_paths is not None and _png_shape(hr_paths[0]) != _png_shape(wide_paths[0]):
+                raise ValueError(f"FramePairs.from_wide_files: wide and hr frames must have the same size: wide "
+                                 f"{_png_shape(wide_paths[0])}, hr {_png_shape(hr_paths[0])}")
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            hr = _decode_files(hr_paths, _png_shape(hr_paths[0]), dev, chunk) if hr_paths is not None else None
+            get = lambda lo, hi: harness.decode_png_frames(wide_paths[lo:hi], dev, channels=3)
+            return cls._from_wide_chunks("FramePairs.from_wide_files", len(wide_paths), get, hr, scale, n_seq, names, dev, chunk)
         read = lambda paths: torch.stack([torch.as_tensor(np.asarray(reader(p))) for p in paths])
         hr = _as_u8_frames(read(hr_paths), "hr") if hr_paths is not None else None
         return cls._from_wide_chunks("FramePairs.from_wide_files", len(wide_paths), lambda lo, hi: read(wide_paths[lo:hi]), hr, scale,

@@ -567,6 +567,7 @@ def long_clip_options(opt=None):
     elif not isinstance(cc, bool):
         raise ValueError(f"opt.cpu_cache={cc!r}: True or False")
     png_encoder_option(opt)      # validated with the others; read where frames are written (harness.super_resolve)
+    png_decoder_option(opt)      # likewise; read where frames are read (harness.super_resolve, at every call)
     return fc, cc
 
 
@@ -582,6 +583,20 @@ def png_encoder_option(opt=None) -> str:
     elif pe not in ("host", "device"):
         raise ValueError(f"opt.png_encoder={pe!r}: 'host' or 'device'")
     return pe
+
+
+def png_decoder_option(opt=None) -> str:
+    """"host" or "device": who undoes the scanline filters of the PNG files `harness.super_resolve` reads -- `opt.png_decoder`,
+    falling back to the environment where the options do not carry it (EAVSR_PNG_DECODER=host|device), "host" where neither does.
+    Not among the reference's options."""
+    pd = getattr(opt, "png_decoder", None)
+    if pd is None:
+        pd = os.environ.get("EAVSR_PNG_DECODER", "") or "host"
+        if pd not in ("host", "device"):
+            raise ValueError(f"EAVSR_PNG_DECODER={pd!r}: host or device")
+    elif pd not in ("host", "device"):
+        raise ValueError(f"opt.png_decoder={pd!r}: 'host' or 'device'")
+    return pd
 
 
 class EAVSRPModel:

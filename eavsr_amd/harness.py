@@ -102,28 +102,49 @@ def write_png(image: Tensor, path: str, level: int = 6, hwc: Optional[bool] = No
     return path
 
 
-def read_png(path: str) -> Tensor:
-    """Decoder for the files `write_png` writes and for any non-interlaced 8-bit grey / RGB / RGBA PNG (all five scanline
-    filters): (C, H, W) uint8.  For round trips and for feeding stored frames back; not a general PNG reader."""
-    data = open(path, "rb").read()
+def parse_png(data: bytes, what: str = ""):
+    """The chunk walk of a PNG file held in memory -> (h, w, c, idat): the size, the bytes per pixel (1 grey, 3 RGB, 4 RGBA) and the
+    concatenated IDAT bodies (one zlib stream).  Checks the signature, every chunk's CRC-32 and the IHDR (8 bits per sample, colour
+    type 0 / 2 / 6, no interlace); ancillary chunks are ignored.  ValueError, prefixed with `what` (the file's name), for anything
+    else, a missing IHDR or IDAT and a file that ends inside a chunk.  Shared by `read_png` and `decode_png_frames`."""
     if data[:8] != b"\x89PNG\r\n\x1a\n":
-        raise ValueError(f"{path}: not a PNG file")
+        raise ValueError(f"{what}: not a PNG file")
     pos, idat, hdr = 8, [], None
     while pos < len(data):
+        if pos + 8 > len(data):
+            raise ValueError(f"{what}: truncated: the file ends inside a chunk header")
         n, tag = struct.unpack(">I4s", data[pos:pos + 8])
+        if pos + 12 + n > len(data):
+            raise ValueError(f"{what}: truncated: the file ends inside chunk {tag!r}")
         body = data[pos + 8:pos + 8 + n]
         if zlib.crc32(tag + body) & 0xFFFFFFFF != struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0]:
-            raise ValueError(f"{path}: CRC mismatch in chunk {tag!r}")
+            raise ValueError(f"{what}: CRC mismatch in chunk {tag!r}")
         if tag == b"IHDR":
+            if n != 13:
+                raise ValueError(f"{what}: IHDR of {n} bytes")
             hdr = struct.unpack(">IIBBBBB", body)
         elif tag == b"IDAT":
             idat.append(body)
         pos += 12 + n
+    if hdr is None:
+        raise ValueError(f"{what}: no IHDR chunk")
     w, h, depth, ctype, _, _, interlace = hdr
     if depth != 8 or ctype not in (0, 2, 6) or interlace:
-        raise ValueError(f"{path}: only non-interlaced 8-bit grey / RGB / RGBA")
-    c = {0: 1, 2: 3, 6: 4}[ctype]
-    raw = bytearray(zlib.decompress(b"".join(idat)))
+        raise ValueError(f"{what}: only non-interlaced 8-bit grey / RGB / RGBA")
+    if not idat:
+        raise ValueError(f"{what}: no IDAT chunk")
+    if w < 1 or h < 1:
+        raise ValueError(f"{what}: an image of {w} x {h}")
+    return h, w, {0: 1, 2: 3, 6: 4}[ctype], b"".join(idat)
+
+
+def read_png(path: str) -> Tensor:
+    """Decoder for the files `write_png` writes and for any non-interlaced 8-bit grey / RGB / RGBA PNG (all five scanline
+    filters): (C, H, W) uint8.  For round trips and for feeding stored frames back; not a general PNG reader.  The scanline filters
+    are undone in a Python loop (seconds per full-size frame): `decode_png_frames` does that half on the device."""
+    data = open(path, "rb").read()
+    h, w, c, idat = parse_png(data, path)
+    raw = bytearray(zlib.decompress(idat))
     stride = w * c
     out = bytearray(h * stride)
     prev = bytearray(stride)
@@ -166,6 +187,15 @@ def check_png_encoder(encoder) -> str:
     if encoder not in PNG_ENCODERS:
         raise ValueError(f"png_encoder={encoder!r}: one of {PNG_ENCODERS}")
     return encoder
+
+
+PNG_DECODERS = ("host", "device")
+
+
+def check_png_decoder(decoder) -> str:
+    if decoder not in PNG_DECODERS:
+        raise ValueError(f"png_decoder={decoder!r}: one of {PNG_DECODERS}")
+    return decoder
 
 
 class _PngStaging:
@@ -237,6 +267,121 @@ def encode_png_frames(rgb8: Tensor, stripe_rows: int = 32) -> List[bytes]:
         raise ValueError(f"encode_png_frames: uint8 (F, H, W, C), got {getattr(rgb8, 'dtype', type(rgb8))} {tuple(getattr(rgb8, 'shape', ()))}")
     staging = _shared_staging(stripe_rows)
     return staging.files(staging.enqueue(rgb8.contiguous()))
+
+
+class _PngDecodeStaging:
+    """The host side of the device PNG decoder: two pinned buffers used in turn, each with the event of the copy that last
+    read it.  `slot(nbytes)` hands out the next buffer once that copy has ended, so a caller looping over chunks inflates chunk k + 1
+    into one buffer while chunk k's copy and kernel still run from the other.  Not for concurrent use from several threads."""
+
+    def __init__(self):
+        self.slots = [None, None]      # [pinned bytes, event or None]
+        self.turn = 0
+
+    def slot(self, nbytes: int):
+        cur = self.slots[self.turn]
+        if cur is not None and cur[1] is not None:
+            cur[1].synchronize()
+            cur[1] = None
+        if cur is None or cur[0].numel() < nbytes:
+            cur = self.slots[self.turn] = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), None]
+        self.turn ^= 1
+        return cur
+
+
+_DECODE_STAGING = _PngDecodeStaging()
+_DECODE_POOLS: Dict[int, "object"] = {}
+
+
+def _decode_pool(threads: Optional[int]):
+    """the thread pool of `decode_png_frames`, kept between calls; sized by the CPUs this process may run on, never by the machine's"""
+    if threads is None:
+        threads = min(16, len(os.sched_getaffinity(0)))
+    if isinstance(threads, bool) or not isinstance(threads, int) or threads < 1:
+        raise ValueError(f"decode_png_frames: threads={threads!r}: a positive number of workers")
+    if threads not in _DECODE_POOLS:
+        from concurrent.futures import ThreadPoolExecutor
+        _DECODE_POOLS[threads] = ThreadPoolExecutor(max_workers=threads, thread_name_prefix="eavsr-png")
+    return _DECODE_POOLS[threads]
+
+
+def _png_item_name(item, i: int) -> str:
+    return f"<bytes #{i}>" if isinstance(item, (bytes, bytearray, memoryview)) else os.fspath(item)
+
+
+def inflate_png_frames(files, threads: Optional[int] = None):
+    """The host half of `decode_png_frames`: read and `parse_png` every file, inflate every IDAT stream into one row of a pinned
+    staging buffer (`zlib.decompress` releases the GIL: a thread pool), validate.  Returns (rows, h, w, c, slot): rows a pinned uint8
+    (F, h, 1 + w c) view of the slot's buffer; set slot[1] to the event of the copy that reads it."""
+    import numpy as np
+    files = list(files)
+    if not files:
+        raise ValueError("decode_png_frames: no files")
+    pool = _decode_pool(threads)
+    names = [_png_item_name(f, i) for i, f in enumerate(files)]
+
+    def parse(i):
+        f = files[i]
+        data = bytes(f) if isinstance(f, (bytes, bytearray, memoryview)) else open(os.fspath(f), "rb").read()
+        return parse_png(data, names[i])
+    parsed = list(pool.map(parse, range(len(files))))
+    h, w, c, _ = parsed[0]
+    for i, (hi, wi, ci, _) in enumerate(parsed):
+        if (hi, wi, ci) != (h, w, c):
+            raise ValueError(f"{names[i]}: {hi} x {wi} x {ci}, but {names[0]} is {h} x {w} x {c}: one call decodes frames of one size")
+    r = 1 + w * c
+    slot = _DECODE_STAGING.slot(len(files) * h * r)
+    rows = slot[0][:len(files) * h * r].view(len(files), h, r)
+    host = rows.numpy()
+
+    def inflate(i):
+        try:
+            raw = zlib.decompress(parsed[i][3])
+        except zlib.error as e:
+            raise ValueError(f"{names[i]}: zlib: {e}") from None
+        if len(raw) != h * r:
+            raise ValueError(f"{names[i]}: the IDAT stream inflates to {len(raw)} bytes, {h} scanlines of 1 + {w} x {c} bytes are {h * r}")
+        host[i] = np.frombuffer(raw, np.uint8).reshape(h, r)
+    list(pool.map(inflate, range(len(files))))
+    types = host[:, :, 0]
+    if int(types.max()) > 4:
+        i = int(np.argmax(types.max(1) > 4))
+        raise ValueError(f"{names[i]}: scanline filter {int(types[i].max())}")
+    return rows, h, w, c, slot
+
+
+def decode_png_frames(files, device=None, channels: int = 3, out: Optional[Tensor] = None, threads: Optional[int] = None) -> Tensor:
+    """PNG files -> uint8 (F, min(c, channels), H, W) planes ON THE DEVICE.  `files`: paths and / or `bytes` holding whole files, all
+    non-interlaced 8-bit grey / RGB / RGBA of ONE size.  The host reads, walks the chunks (`parse_png`) and inflates (zlib in a pool of
+    `threads` workers, default min(16, the CPUs this process may use)) into one of two pinned buffers; then ONE asynchronous copy and
+    ONE launch (`ops.png_unfilter`) undo the scanline filters and leave the planes -- in `out` (for example store[lo:hi])
+    when given.  Nothing waits for the device, so a loop over chunks inflates chunk k + 1 while chunk k is copied and unfiltered.
+    channels=3 drops alpha as `read_png(p)[:3]` does.  ValueError naming the file, before anything is launched: a broken file
+    (`parse_png`), frames of differing size, a zlib error, an inflated length other than h (1 + w c), a filter type above 4."""
+    from . import ops
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 4:
+        raise ValueError(f"decode_png_frames: channels={channels!r}: 1 .. 4")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError(f"decode_png_frames: device {dev}: the unfilter runs on the GPU only (`read_png` is the host decoder)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    rows, h, w, c, slot = inflate_png_frames(files, threads)
+    f = int(rows.shape[0])
+    if channels == 4 and c != 4:
+        raise ValueError(f"decode_png_frames: channels=4 needs RGBA files, these have {c} bytes per pixel")
+    shape = (f, min(c, channels), h, w)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape
+                            or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"decode_png_frames: out: a contiguous uint8 {shape} tensor on {dev}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    with torch.cuda.device(dev):
+        dev_rows = torch.empty(tuple(rows.shape), device=dev, dtype=torch.uint8)
+        dev_rows.copy_(rows, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        slot[1] = done
+        return ops.png_unfilter(dev_rows, c, channels, out=out)
 
 
 def _write_file(path: str, data: bytes) -> str:
@@ -508,7 +653,8 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
 
 
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
-                  frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None) -> Dict:
+                  frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
+                  png_decoder: Optional[str] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -523,6 +669,9 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     of the compressed bytes into one of two pinned buffers and waits for nothing; the files of a chunk are written when the next
     chunk has been enqueued, the last chunk's when the forward has ended).  None: `opt.png_encoder` of a model wrapper, else
     EAVSR_PNG_ENCODER, else "host".  The files differ in bytes, not in pixels; 'written' and the report are the same.
+    `png_decoder`: who decodes `frames` / `hr` given as lists of paths -- "host" (the default: `read_png`, a Python loop per byte) or
+    "device" (`decode_png_frames`, zlib in a thread pool and the scanline unfilter on the device; the 8-bit clip is then on
+    the device already).  None: `opt.png_decoder` of a model wrapper, else EAVSR_PNG_DECODER, else "host".  The same pixels.
     `names`: one name per frame (default: the paths' base names, else `000_00000.png`, ...); a name's first three characters are its
     scene in the report.  Returns 'frames', 'seconds' (device-synchronised on both sides), 'frames_per_s', 'peak_bytes'
     (`torch.cuda.max_memory_allocated` over the run), 'written', and with `hr` the 'frame_psnr' / 'frame_ssim' / 'frame_names' /
@@ -534,6 +683,10 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         from .eavsrp_model import png_encoder_option
         png_encoder = png_encoder_option(getattr(model, "opt", None))
     check_png_encoder(png_encoder)
+    if png_decoder is None:
+        from .eavsrp_model import png_decoder_option
+        png_decoder = png_decoder_option(getattr(model, "opt", None))
+    check_png_decoder(png_decoder)
     net = getattr(model, "netEAVSRP", model)
     device = next(net.parameters()).device
     if device.type != "cuda":
@@ -541,8 +694,17 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     paths = None
     if isinstance(frames, (list, tuple)):
         paths = [os.fspath(p) for p in frames]
-        frames = torch.stack([read_png(p)[:3] for p in paths], 0)
-        frames = frames.pin_memory()
+        if png_decoder == "device":
+            frames = decode_png_frames(paths, device, channels=3)
+        else:
+            frames = torch.stack([read_png(p)[:3] for p in paths], 0)
+            frames = frames.pin_memory()
+    if isinstance(hr, (list, tuple)):
+        hr_paths = [os.fspath(p) for p in hr]
+        if png_decoder == "device":
+            hr = decode_png_frames(hr_paths, device, channels=3)
+        else:
+            hr = torch.stack([read_png(p)[:3] for p in hr_paths], 0)
 
     def as_clip(x, what):
         if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):

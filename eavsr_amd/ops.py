@@ -1732,6 +1732,39 @@ def png_encode(rgb8: Tensor, stripe_rows: int = 32) -> Deflated:
     return deflate_huffman(rows.view(f, h * r), min(stripe_rows, h) * r)
 
 
+def png_unfilter(rows: Tensor, c: int, channels: int = 3, out: Optional[Tensor] = None) -> Tensor:
+    """The scanline half of a PNG decode (csrc/png_decode.hip).  rows: uint8 (F, H, 1 + W c) on the device, the inflated
+    IDAT payloads of F frames of one size (per scanline its filter-type byte 0 - 4, then W c filtered bytes); c: bytes per pixel, 1
+    (grey), 3 (RGB) or 4 (RGBA).  Returns planar uint8 (F, min(c, channels), H, W): channels=3 drops the alpha of an RGBA file as
+    `read_png(p)[:3]` does, channels=4 keeps it (and needs c = 4).  `out`: a contiguous uint8 tensor of that shape on the same device
+    to write into (returned) -- a slice store[lo:hi] of a preallocated store, at any byte alignment.  A type byte above 4 is
+    reconstructed as type 0: `harness.decode_png_frames` rejects such files before anything is launched."""
+    x = _bytes_on_device(rows, "png_unfilter", 3)
+    f, h, r = (int(v) for v in x.shape)
+    if isinstance(c, bool) or not isinstance(c, int) or c not in (1, 3, 4):
+        raise ValueError(f"png_unfilter: c={c!r}: 1 (grey), 3 (RGB) or 4 (RGBA) bytes per pixel")
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 4:
+        raise ValueError(f"png_unfilter: channels={channels!r}: 1 .. 4")
+    if channels == 4 and c != 4:
+        raise ValueError(f"png_unfilter: channels=4 needs RGBA rows (c=4), got c={c}")
+    if h < 1 or r < 1 + c or (r - 1) % c:
+        raise ValueError(f"png_unfilter: rows (F, H, 1 + W c) with H, W >= 1 and c={c}, got {tuple(x.shape)}")
+    w, cout = (r - 1) // c, min(c, channels)
+    shape = (f, cout, h, w)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.uint8)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous()
+          or out.device != x.device):
+        raise ValueError(f"png_unfilter: out: a contiguous uint8 {shape} tensor on {x.device}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    if f == 0:
+        return out
+    st = _stream(x)
+    _launch("png_unfilter_u8", 0.0, float(x.numel() + out.numel()), x,
+            lambda: lib().eavsr_png_unfilter_u8(_p(x), _p(out), f, h, w, c, cout, st), "png_unfilter")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # LPIPS (AlexNet), the report's third column  (psnr_total.py:27-35; csrc/lpips.hip)
 # ------------------------------------------------------------------------------------------

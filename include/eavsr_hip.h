@@ -787,6 +787,21 @@ int64_t eavsr_png_capacity(int64_t nbytes, int64_t stripe_bytes);
 int64_t eavsr_deflate_workspace_bytes(int32_t F, int64_t nbytes, int64_t stripe_bytes);
 int eavsr_deflate_huffman_u8(const uint8_t* in, uint8_t* out, int64_t* offsets, int64_t* sizes, void* workspace, int32_t F, int64_t nbytes,
                              int64_t stripe_bytes, void* stream);
+/* ---- the incoming PNG file: the scanline unfilter (added to ABI 32, nothing above changes) --------------------------------------------
+ * csrc/png_decode.hip.  The inflate of a PNG file stays with the caller (zlib); this is the other half of the decode.
+ *   rows (F, H, 1 + W C) uint8: the inflated IDAT payloads of F frames of one size: per scanline its filter-type byte, then W C filtered
+ *   bytes.  C: bytes per pixel, 1 (grey), 3 (RGB) or 4 (RGBA), 8 bits per sample.  Any alignment; only bytes of `rows` are read.
+ *   out (F, Cout, H, W) uint8 PLANAR, 1 <= Cout <= C: the first Cout channels (Cout = 3 on RGBA drops alpha; it is still reconstructed,
+ *   later alpha bytes depend on it).  Any alignment (whole dwords are stored where a plane's row allows, bytes elsewhere).
+ * Filter types (PNG specification 9.2): 0 none, 1 sub, 2 up, 3 average (floor((a + b) / 2) of the 9-bit sum), 4 Paeth (ties in the order
+ * a, b, c); a: the byte C to the left, b: the byte above, c: the byte above a; neighbours left of the first pixel and above the first row
+ * are 0; sums mod 256.  A type byte above 4 is treated as 0: the caller validates files, the kernel only never faults on them.
+ * One wave per frame, lane l on row 64 band + l one pixel behind lane l - 1; no atomics, two calls on equal input write equal bytes.
+ * Rows of more than 4096 pixels hand a band's last row to the next band through 4 F W bytes of scratch, allocated and freed in stream
+ * order (hipMallocAsync) by this call; narrower rows use LDS and allocate nothing.
+ * NULL pointer: -1; C not 1, 3 or 4, Cout outside 1 .. C, H or W < 1, W C > 2^31 - 2: -2; the scratch allocation failed: -3.
+ * F = 0: nothing is launched. */
+int eavsr_png_unfilter_u8(const uint8_t* rows, uint8_t* out, int32_t F, int32_t H, int32_t W, int32_t C, int32_t Cout, void* stream);
 /* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
  * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
  * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
