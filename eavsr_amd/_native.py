@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("EAVSR_LIB_PATH") or os.path.join(
     _HERE, "lib", "libeavsr_lab.so" if os.environ.get("EAVSR_BUILD_LAB", "0") == "1" else "libeavsr_hip.so")
 
 ABI_VERSION = 32
+WARP_PAIR_BORDER = 0x10      # EAVSR_WARP_PAIR_BORDER: or-ed into outb_il8 of eavsr_flow_warp_pair_f32 (border padding)
 
 p_f32 = C.c_void_p  # device pointers travel as integers
 i32 = C.c_int32
@@ -60,6 +61,7 @@ SIGNATURES = {
     "eavsr_selftest_mfma_f32": (C.c_int, [vp, vp]),
     "eavsr_flow_warp_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "eavsr_flow_warp_pair_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "eavsr_flow_warp_single_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "eavsr_dcnv2_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "eavsr_dcnv2_generic_f32": (C.c_int, [vp] * 6 + [i32] * 15 + [vp]),
     "eavsr_dcn_weight_x9_bytes": (C.c_int64, [i32, i32]),
@@ -101,6 +103,7 @@ SIGNATURES = {
     "eavsr_pack_conv_weight_x6": (C.c_int, [vp, vp, i32, i32, i32, vp]),
     "eavsr_pack_conv_weight_x6_dgrad": (C.c_int, [vp, vp, i32, i32, i32, vp]),
     "eavsr_pack_conv_weight_x6_multi": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+    "eavsr_conv_f32x6_tiles_per_workgroup": (i32, [i32, i32, i32, i32, i32, i32]),
     "eavsr_conv_f32x6": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "eavsr_ca_scale_f32": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "eavsr_ca_scale_mean_f32": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),

@@ -109,7 +109,13 @@ __device__ unsigned long long g_c7_stamps[8];
 #define C7_STAMP(i) do { } while (0)
 #endif
 
-template <int KS, int MT, int NT, int WMT, int NP = 3, int DT = 0>
+// PERSIST: a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, .. of its output-channel tile as ONE stream of chunks and
+// weight slabs -- the weights are the same for every tile, so the slab ring simply goes on, and the next tile's first patch is
+// requested at the top of the current tile's last chunk and stored, like any chunk's, behind a slab barrier: the epilogue's stores
+// leave with the next tile's first operands already in registers, and no tile but a workgroup's first pays the prologue's round
+// trips.  Per tile the same operations in the same order as the one-tile form (needs an even number of chunks and of slabs per
+// chunk, so that both rings come round to stage 0 at a tile's start: the launcher checks).
+template <int KS, int MT, int NT, int WMT, int NP = 3, int DT = 0, bool PERSIST = false>
 __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
   static_assert((NP == 3 && DT == 0) || (NP == 1 && (DT == 1 || DT == 2)), "three exact bf16 planes, or one rounded fp16 / bf16 plane");
   using K = C7<KS, MT, NT, NP>;
@@ -134,34 +140,45 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
 #endif
   const int l31 = lane & 31, kg = lane >> 5;
 
-  int bid = eavsr_xcd_remap(blockIdx.x, gridDim.x);
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int bn = bid / a.tiles_y;
+  const int ntiles = a.tiles_x * a.tiles_y * a.n;      // per output-channel tile (the launcher checks the range)
+  int tile = PERSIST ? (int)blockIdx.x : eavsr_xcd_remap(blockIdx.x, gridDim.x);
+  int bn, y0, x0;                                      // the tile the accumulators belong to
+  auto place = [&](int t_, int& bn_, int& y0_, int& x0_) __attribute__((always_inline)) {
+    const int tx = t_ % a.tiles_x;
+    t_ /= a.tiles_x;
+    bn_ = t_ / a.tiles_y;
+    y0_ = (t_ - bn_ * a.tiles_y) * S_TH;
+    x0_ = tx * S_TW;
+  };
+  place(tile, bn, y0, x0);
   const int cot = blockIdx.y;
-  const int y0 = ty * S_TH, x0 = tx * S_TW;
   const int h = a.h, w = a.w;
   const size_t plane = (size_t)h * w;
   const int nch = a.cin >> 3;
 
-  // ---- patch producer: thread t owns patch pixels t and t + 512 --------------------------------------------------
+  // ---- patch producer: thread t owns patch pixels t and t + 512 (of tile `pbn`, .. : one tile ahead at a tile's last chunk) ----
   bool pok[2];
   unsigned pgo[2], plo[2];
+  int pbn;
+  auto aim_patch = [&](int t_) __attribute__((always_inline)) {
+    int py0, px0;
+    place(t_, pbn, py0, px0);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int p = tid + i * 512;
-    const int r = p / S_IW, c = p - r * S_IW;
-    const int gy = y0 - S_PAD + r, gx = x0 - S_PAD + c;
-    // the last column is never a tap of anybody: kept zero (the zero tap of the last k-step reads it, below)
-    pok[i] = p < S_NPIX && c < S_IW - 1 && gy >= 0 && gy < h && gx >= 0 && gx < w;
-    pgo[i] = pok[i] ? (unsigned)(gy * w + gx) : 0u;
-    plo[i] = (unsigned)p * 16u;
-  }
+    for (int i = 0; i < 2; ++i) {
+      const int p = tid + i * 512;
+      const int r = p / S_IW, c = p - r * S_IW;
+      const int gy = py0 - S_PAD + r, gx = px0 - S_PAD + c;
+      // the last column is never a tap of anybody: kept zero (the zero tap of the last k-step reads it, below)
+      pok[i] = p < S_NPIX && c < S_IW - 1 && gy >= 0 && gy < h && gx >= 0 && gx < w;
+      pgo[i] = pok[i] ? (unsigned)(gy * w + gx) : 0u;
+      plo[i] = (unsigned)p * 16u;
+    }
+  };
+  aim_patch(tile);
   const bool second = tid + 512 < S_NPIX;    // 7x7: 346 (NT = 2) / 34 (NT = 1) threads own a second pixel
   float pv[2][8];
   auto load_patch = [&](int ch) __attribute__((always_inline)) {
-    const float* sp = a.x + ((size_t)bn * a.cin + (size_t)ch * 8) * plane;
+    const float* sp = a.x + ((size_t)pbn * a.cin + (size_t)ch * 8) * plane;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -245,24 +262,34 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // the bias is the accumulators' initial value (32 dependent global loads in the epilogue were 10 % of a workgroup's time)
+  auto init_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
-  for (int m = 0; m < MT; ++m)
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float bv = s_bias[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg];
+      for (int r = 0; r < 16; ++r) {
+        const float bv = s_bias[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg];
 #pragma unroll
-      for (int t = 0; t < S_NT; ++t) acc[m][t][r] = bv;
-    }
+        for (int t = 0; t < S_NT; ++t) acc[m][t][r] = bv;
+      }
+  };
+  init_acc();
   if (nslabs > 1) issue_slab(1, S_NSLAB > 1 ? 0 : 1, S_NSLAB > 1 ? 1 : 0);
   u32x4 acur[NP][MT], bcur[S_NT][NP];
   read_a(0, 0, acur);
   read_b(0, 0, bcur);
   C7_STAMP(0);      // prologue
 
+  for (;;) {      // the tiles of this workgroup (one, unless PERSIST)
+  const bool has_next = PERSIST && tile + (int)gridDim.x < ntiles;
   for (int ch = 0; ch < nch; ++ch) {
     const int pst = ch & 1;
-    const bool more = ch + 1 < nch;
-    if (more) load_patch(ch + 1);
+    const bool last_ch = ch + 1 == nch;
+    const bool more = !last_ch || has_next;      // the stream goes on behind this chunk: the tile's next chunk, or the next tile's first
+    if (!last_ch) load_patch(ch + 1);
+    else if (has_next) {
+      aim_patch(tile + (int)gridDim.x);
+      load_patch(0);
+    }
 #pragma unroll
     for (int ks = 0; ks < S_KSTEPS; ++ks) {
       constexpr int STORE_KS = KS == 7 ? 11 : KS == 5 ? 7 : 3;   // (7x7, 5x5: behind a slab barrier, the chunk's loads have landed by its vmcnt(0))
@@ -278,6 +305,7 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
         __syncthreads();
         C7_STAMP(3);  // barrier
         if (gs + 2 < nslabs) issue_slab(gs + 2, ch + (si + 2) / S_NSLAB, (si + 2) % S_NSLAB);
+        else if (has_next) issue_slab(gs + 2 - nslabs, (gs + 2 - nslabs) / S_NSLAB, (si + 2) % S_NSLAB);      // (nslabs even: the same stage)
         C7_STAMP(4);  // DMA issue
       }
       if (ks == STORE_KS && more) store_patch(pst ^ 1);     // published by the slab barriers behind it
@@ -340,6 +368,7 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
 
   C7_STAMP(1);
   // ---- epilogue: bias, activation, NCHW stores (lanes 0-31 / 32-63: 32 consecutive pixels of two channels 4 apart) ----
+  {
   int gx = x0 + l31;
   asm volatile("" : "+v"(gx));      // keeps the address arithmetic below here (hoisted above the loop its 64-bit results spill)
   const bool xok = gx < w;
@@ -364,6 +393,12 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
         if (cok && xok && y0 + wave * S_NT + t < h) ob[(size_t)cu * plane + (size_t)t * w] = v;
       }
     }
+  }
+  if (!has_next) break;
+  tile += (int)gridDim.x;
+  place(tile, bn, y0, x0);
+  init_acc();
+  }
 #ifdef EAVSR_C7_STAMPS
   C7_STAMP(5);      // epilogue issued
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -463,15 +498,39 @@ __global__ void pack7_multi_kernel(PackMultiArgs a, int cout, int cin, int kk, i
 
 int mt_of(int cout) { return cout > 32 ? 2 : 1; }
 
-template <int KS, int MT, int NT, int WMT, int NP = 3, int DT = 0>
-int launch7(const C7Args& a, void* stream) {
+// compute units of the current device (0: unknown -- nobody walks tiles then)
+int cu_count() {
+  static int cus_pd[eavsr::kMaxDevices] = {};
+  static eavsr::PerDeviceOnce once_pd;
+  const int dev_ = eavsr::current_device();
+  std::call_once(once_pd.flag[dev_], [&] {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess && v > 0) cus_pd[dev_] = v;
+  });
+  return cus_pd[dev_];
+}
+
+// The persistent form's grid: a workgroup owns a CU's LDS, so `slots` = CUs / output-channel tiles workgroups per channel tile are
+// resident at once; `tiles` of them take rounds = ceil(tiles / slots) whoever hands them out.  The grid is the FEWEST workgroups
+// that still finish in `rounds` tiles each (every one walks rounds or rounds - 1 tiles).  0: one tile per workgroup, as launched
+// before -- a launch of one round, an odd number of chunks, a device that does not say how many CUs it has.
+int persist_grid(long tiles, int cot_n, int cin) {
+  const int slots = cu_count() / cot_n;
+  if (slots < 1 || tiles <= slots || (cin >> 3) % 2) return 0;
+  const long rounds = (tiles + slots - 1) / slots;
+  return (int)((tiles + rounds - 1) / rounds);
+}
+
+template <int KS, int MT, int NT, int WMT, int NP = 3, int DT = 0, bool PERSIST = false>
+int launch7(const C7Args& a, void* stream, int grid_x = 0) {
   using K = C7<KS, MT, NT, NP>;
+  static_assert(!PERSIST || K::NSLAB % 2 == 0, "the slab ring must come round to stage 0 at a tile's start");
   static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
   const int dev_ = eavsr::current_device();
   static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
   hipError_t& attr_err = attr_err_pd[dev_];
   std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x6_kernel<KS, MT, NT, WMT, NP, DT>),
+    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x6_kernel<KS, MT, NT, WMT, NP, DT, PERSIST>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
   });
   if (attr_err != hipSuccess) {
@@ -482,8 +541,8 @@ int launch7(const C7Args& a, void* stream) {
   b.tiles_y = eavsr::cdiv(a.h, K::TH);
   const long blocks = (long)b.tiles_x * b.tiles_y * b.n;
   EAVSR_REQUIRE(blocks < (1L << 31), -1, "conv_f32x6: too many tiles");
-  dim3 grid((unsigned)blocks, eavsr::cdiv(a.cout, 32 * MT));
-  hipLaunchKernelGGL((conv_x6_kernel<KS, MT, NT, WMT, NP, DT>), grid, dim3(64 * S_NW), K::LDS_BYTES, eavsr::as_stream(stream), b);
+  dim3 grid((unsigned)(PERSIST ? grid_x : blocks), eavsr::cdiv(a.cout, 32 * MT));
+  hipLaunchKernelGGL((conv_x6_kernel<KS, MT, NT, WMT, NP, DT, PERSIST>), grid, dim3(64 * S_NW), K::LDS_BYTES, eavsr::as_stream(stream), b);
   return eavsr::launch_status("conv_f32x6");
 }
 
@@ -496,6 +555,11 @@ int dispatch7(const C7Args& a, void* stream) {
   const long wg1 = (long)a.tiles_x * eavsr::cdiv(a.h, 8) * a.n;
   EAVSR_REQUIRE(wg1 * 2 < (1L << 31), -1, "conv_f32x6: too many tiles");
   if (mt_of(a.cout) == 2) {     // (the packed weight has two 32-channel tiles per `cot`)
+    if constexpr (KS == 5 && NP == 3) {
+      // the predictor's heads on a stack of images (several rounds of workgroups): each workgroup walks its tiles
+      const int g = wg2 >= 128 ? persist_grid(wg2, eavsr::cdiv(a.cout, 64), a.cin) : 0;
+      if (g > 0) return launch7<KS, 2, 2, 2, NP, DT, true>(a, stream, g);
+    }
     if (wg2 >= 128) return launch7<KS, 2, 2, 2, NP, DT>(a, stream);
     if (wg1 >= 128) return launch7<KS, 2, 1, 2, NP, DT>(a, stream);
     return launch7<KS, 1, 1, 2, NP, DT>(a, stream);
@@ -616,6 +680,14 @@ extern "C" int eavsr_pack_conv_weight_bf16x1_multi(const float* const* weights, 
                        c, ksize * ksize, mt_of(c), total);
   }
   return eavsr::launch_status("pack_conv_weight_bf16x1_multi");
+}
+
+// How many tiles the busiest workgroup of eavsr_conv_f32x6 walks at this shape on the current device (1: one tile per workgroup)
+extern "C" int32_t eavsr_conv_f32x6_tiles_per_workgroup(int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ksize) {
+  if (ksize != 5 || n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || mt_of(cout) != 2) return 1;
+  const long wg2 = (long)eavsr::cdiv(w, S_TW) * eavsr::cdiv(h, 16) * n;
+  const int g = wg2 >= 128 ? persist_grid(wg2, eavsr::cdiv(cout, 64), cin) : 0;
+  return g > 0 ? (int32_t)((wg2 + g - 1) / g) : 1;
 }
 
 extern "C" int eavsr_conv_f32x6(const float* x, const void* weight_x6, const float* bias, float* out, int32_t n, int32_t cin,

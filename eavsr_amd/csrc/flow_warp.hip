@@ -92,7 +92,11 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(
 // both warped by the refined offset): the flow is read and the corner weights are computed once per (pixel, channel
 // chunk) as before, but one launch covers both tensors.  The second output may be written in the "IL8" layout
 // [n][c/8][h][w][8] that eavsr_dcnv2_il_f32 samples from (the warp of feat_prop feeds DCNv2 and nothing else).
-template <int b_il8>      // second output: 0 NCHW fp32, 1 IL8 fp32, 2 IL8 fp16, 3 IL8 bf16
+// ONLY: 0 = both tensors; 1 / 2 = the launch covers the first / the second tensor alone (eavsr_flow_warp_single_f32: the two warps
+// of the alignment module no longer meet in one launch once its predictors are computed ahead of the recurrence) -- every
+// workgroup takes that tensor's path below, so the output is the pair launch's output of that tensor bit for bit; the other
+// tensor's pointers are not touched.
+template <int b_il8, int PADMODE, int ONLY>      // second output: 0 NCHW fp32, 1 IL8 fp32, 2 IL8 fp16, 3 IL8 bf16
 __global__ __launch_bounds__(256) void flow_warp_pair_kernel(
     const float* __restrict__ xa, const float* __restrict__ xb, const float* __restrict__ flow,
     const float* __restrict__ flow2, float* __restrict__ outa, float* __restrict__ outb, int n, int c, int h, int w,
@@ -102,10 +106,11 @@ __global__ __launch_bounds__(256) void flow_warp_pair_kernel(
   lid /= tiles_x;
   const int ty = lid % tiles_y;
   lid /= tiles_y;
-  const int chunk = lid % (2 * c_chunks);
-  const int bn = lid / (2 * c_chunks);
-  const bool second = chunk >= c_chunks;
-  const int c0 = (second ? chunk - c_chunks : chunk) * kChanPerThread;
+  constexpr int kTensors = ONLY ? 1 : 2;
+  const int chunk = lid % (kTensors * c_chunks);
+  const int bn = lid / (kTensors * c_chunks);
+  const bool second = ONLY == 2 || (ONLY == 0 && chunk >= c_chunks);
+  const int c0 = (ONLY == 0 && second ? chunk - c_chunks : chunk) * kChanPerThread;
   const int px = tx * 64 + threadIdx.x;
   const int py = ty * 4 + threadIdx.y;
   if (px >= w || py >= h) return;
@@ -124,6 +129,10 @@ __global__ __launch_bounds__(256) void flow_warp_pair_kernel(
   const float ny = 2.0f * gy / (float)max(h - 1, 1) - 1.0f;
   float ix = ((nx + 1.0f) / 2.0f) * (float)(w - 1);
   float iy = ((ny + 1.0f) / 2.0f) * (float)(h - 1);
+  if (PADMODE == EAVSR_PAD_BORDER) {
+    ix = fminf((float)(w - 1), fmaxf(ix, 0.0f));
+    iy = fminf((float)(h - 1), fmaxf(iy, 0.0f));
+  }
   ix = fminf(fmaxf(ix, -4.0f), (float)w + 4.0f);
   iy = fminf(fmaxf(iy, -4.0f), (float)h + 4.0f);
   const float fx0 = floorf(ix), fy0 = floorf(iy);
@@ -320,27 +329,67 @@ extern "C" int eavsr_flow_warp_f32(const float* x, const float* flow, const floa
   return eavsr::launch_status("flow_warp");
 }
 
+namespace {
+
+// the launch behind both entries below; only: 0 = both tensors, 1 = xa -> outa alone, 2 = xb -> outb alone
+int launch_warp_pair(const char* who, const float* xa, const float* xb, const float* flow, const float* flow2, float* outa, float* outb,
+                     int n, int c, int h, int w, int layout, int padmode, int only, void* stream) {
+  const int c_chunks = eavsr::cdiv(c, kChanPerThread);
+  const int tiles_x = eavsr::cdiv(w, 64), tiles_y = eavsr::cdiv(h, 4);
+  const long nblk = (long)tiles_x * tiles_y * c_chunks * (only ? 1 : 2) * n;
+  EAVSR_REQUIRE(nblk < (1L << 31), -1, "%s: too many tiles", who);
+  const dim3 grid((unsigned)nblk), block(64, 4, 1);
+  hipStream_t st = eavsr::as_stream(stream);
+#define EAVSR_WARP_PAIR3(M, P, O) hipLaunchKernelGGL((flow_warp_pair_kernel<M, P, O>), grid, block, 0, st, xa, xb, flow, flow2, outa, outb, n, c, h, w, c_chunks, tiles_x, tiles_y)
+#define EAVSR_WARP_PAIR2(M, P) do { if (only == 2) EAVSR_WARP_PAIR3(M, P, 2); else EAVSR_WARP_PAIR3(M, P, 0); } while (0)
+#define EAVSR_WARP_PAIR(M) do { if (padmode == EAVSR_PAD_BORDER) EAVSR_WARP_PAIR2(M, EAVSR_PAD_BORDER); else EAVSR_WARP_PAIR2(M, EAVSR_PAD_ZEROS); } while (0)
+  if (only == 1) {      // (the first tensor's path knows no layout)
+    if (padmode == EAVSR_PAD_BORDER) EAVSR_WARP_PAIR3(0, EAVSR_PAD_BORDER, 1);
+    else EAVSR_WARP_PAIR3(0, EAVSR_PAD_ZEROS, 1);
+  } else if (layout == 0) EAVSR_WARP_PAIR(0);
+  else if (layout == 1) EAVSR_WARP_PAIR(1);
+  else if (layout == 2) EAVSR_WARP_PAIR(2);
+  else EAVSR_WARP_PAIR(3);
+#undef EAVSR_WARP_PAIR
+#undef EAVSR_WARP_PAIR2
+#undef EAVSR_WARP_PAIR3
+  return eavsr::launch_status(who);
+}
+
+}  // namespace
+
+// outb_il8: the second output's layout (0 NCHW, 1 IL8 fp32, 2 IL8 fp16, 3 IL8 bf16), | EAVSR_WARP_PAIR_BORDER for border padding
 extern "C" int eavsr_flow_warp_pair_f32(const float* xa, const float* xb, const float* flow, const float* flow2, float* outa,
                                         float* outb, int32_t n, int32_t c, int32_t h, int32_t w, int32_t outb_il8,
                                         void* stream) {
   EAVSR_REQUIRE(xa && xb && flow && outa && outb, -1, "flow_warp_pair: NULL pointer");
   EAVSR_REQUIRE(n >= 0 && c >= 0 && h >= 0 && w >= 0, -1, "flow_warp_pair: negative dimension");
   EAVSR_REQUIRE((long)h * w < (1L << 31), -1, "flow_warp_pair: plane too large");
-  EAVSR_REQUIRE(outb_il8 >= 0 && outb_il8 <= 3, -1, "flow_warp_pair: outb_il8 %d (0 NCHW, 1 IL8 fp32, 2 IL8 fp16, 3 IL8 bf16)", outb_il8);
-  EAVSR_REQUIRE(!outb_il8 || (c % 8 == 0 && (((uintptr_t)outb) & 15) == 0), -2,
+  const int layout = outb_il8 & ~EAVSR_WARP_PAIR_BORDER;
+  const int padmode = (outb_il8 & EAVSR_WARP_PAIR_BORDER) ? EAVSR_PAD_BORDER : EAVSR_PAD_ZEROS;
+  EAVSR_REQUIRE(layout >= 0 && layout <= 3, -1, "flow_warp_pair: outb_il8 %d (0 NCHW, 1 IL8 fp32, 2 IL8 fp16, 3 IL8 bf16)", outb_il8);
+  EAVSR_REQUIRE(!layout || (c % 8 == 0 && (((uintptr_t)outb) & 15) == 0), -2,
                 "flow_warp_pair: the IL8 output needs c %% 8 == 0 and a 16-byte aligned buffer");
   if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
-  const int c_chunks = eavsr::cdiv(c, kChanPerThread);
-  const int tiles_x = eavsr::cdiv(w, 64), tiles_y = eavsr::cdiv(h, 4);
-  const long nblk = (long)tiles_x * tiles_y * c_chunks * 2 * n;
-  EAVSR_REQUIRE(nblk < (1L << 31), -1, "flow_warp_pair: too many tiles");
-  const dim3 grid((unsigned)nblk), block(64, 4, 1);
-  hipStream_t st = eavsr::as_stream(stream);
-#define EAVSR_WARP_PAIR(M) hipLaunchKernelGGL(flow_warp_pair_kernel<M>, grid, block, 0, st, xa, xb, flow, flow2, outa, outb, n, c, h, w, c_chunks, tiles_x, tiles_y)
-  if (outb_il8 == 0) EAVSR_WARP_PAIR(0);
-  else if (outb_il8 == 1) EAVSR_WARP_PAIR(1);
-  else if (outb_il8 == 2) EAVSR_WARP_PAIR(2);
-  else EAVSR_WARP_PAIR(3);
-#undef EAVSR_WARP_PAIR
-  return eavsr::launch_status("flow_warp_pair");
+  return launch_warp_pair("flow_warp_pair", xa, xb, flow, flow2, outa, outb, n, c, h, w, layout, padmode, 0, stream);
+}
+
+// ONE tensor warped by one half of the pair kernel (the same kernel code, so the same bits as that launch's output of the same
+// tensor).  out_layout 0: NCHW fp32 by the first tensor's path; 1 / 2 / 3: IL8 fp32 / fp16 / bf16 by the second tensor's path.
+// padding_mode: EAVSR_PAD_ZEROS / EAVSR_PAD_BORDER.
+extern "C" int eavsr_flow_warp_single_f32(const float* x, const float* flow, const float* flow2, void* out, int32_t n, int32_t c,
+                                          int32_t h, int32_t w, int32_t out_layout, int32_t padding_mode, void* stream) {
+  EAVSR_REQUIRE(x && flow && out, -1, "flow_warp_single: NULL pointer");
+  EAVSR_REQUIRE(n >= 0 && c >= 0 && h >= 0 && w >= 0, -1, "flow_warp_single: negative dimension");
+  EAVSR_REQUIRE((long)h * w < (1L << 31), -1, "flow_warp_single: plane too large");
+  EAVSR_REQUIRE(out_layout >= 0 && out_layout <= 3, -1, "flow_warp_single: out_layout %d (0 NCHW, 1 IL8 fp32, 2 IL8 fp16, 3 IL8 bf16)", out_layout);
+  EAVSR_REQUIRE(padding_mode == EAVSR_PAD_ZEROS || padding_mode == EAVSR_PAD_BORDER, -2, "flow_warp_single: padding_mode %d (zeros, border)",
+                padding_mode);
+  EAVSR_REQUIRE(!out_layout || (c % 8 == 0 && (((uintptr_t)out) & 15) == 0), -2,
+                "flow_warp_single: the IL8 output needs c %% 8 == 0 and a 16-byte aligned buffer");
+  if (n == 0 || c == 0 || h == 0 || w == 0) return 0;
+  float* o = reinterpret_cast<float*>(out);
+  if (out_layout == 0)
+    return launch_warp_pair("flow_warp_single", x, nullptr, flow, flow2, o, nullptr, n, c, h, w, 0, padding_mode, 1, stream);
+  return launch_warp_pair("flow_warp_single", nullptr, x, flow, flow2, nullptr, o, n, c, h, w, out_layout, padding_mode, 2, stream);
 }

@@ -31,6 +31,11 @@ PREPACK = os.environ.get("EAVSR_PREPACK", "1") != "0"
 # EAVSR_TAIL_16BIT=0 keeps it on the fp32 kernels (A/B switch).
 TAIL_IN_16BIT = os.environ.get("EAVSR_TAIL_16BIT", "1") == "1"
 
+# EAVSR_HOIST=0: the alignment predictors inside the recurrence, one time step at a time (the A/B switch of EAVSRP._predict_branch)
+HOIST_PREDICTORS = os.environ.get("EAVSR_HOIST", "1") != "0"
+# the predictor stack (front-end outputs + head channels of 2 t - 1 row blocks) above which a branch keeps the per-step form
+HOIST_MAX_BYTES = int(os.environ.get("EAVSR_HOIST_MAX_BYTES", str(16 << 30)))
+
 Tensor = torch.Tensor
 
 
@@ -246,8 +251,8 @@ class EAVSRP(nn.Module):
         f2, f4 = AG.pyramid(f1)                                    # :218-220
         feats: Dict[str, List[Tensor]] = {
             "spatial": _FrameList([f1[i * n:(i + 1) * n] for i in range(t)], f1),
-            "spatial_d2": [f2[i * n:(i + 1) * n] for i in range(t)],
-            "spatial_d4": [f4[i * n:(i + 1) * n] for i in range(t)],
+            "spatial_d2": _FrameList([f2[i * n:(i + 1) * n] for i in range(t)], f2),
+            "spatial_d4": _FrameList([f4[i * n:(i + 1) * n] for i in range(t)], f4),
         }
         for iter_ in (1, 2):
             for direction in ("backward", "forward"):
@@ -256,6 +261,46 @@ class EAVSRP(nn.Module):
                 flows = flows_backward if direction == "backward" else flows_forward
                 feats = self.propagate(feats, flows, module)
         return self.upsample(lrs, feats, lr_tm)
+
+    def _predict_branch(self, align, feats, flows, backward):
+        """The alignment predictors of ALL time steps of one branch, ahead of its recurrence: in MultiAdSTN.forward
+        (networks.py:597-631) everything in front of the warp of `feat_prop` reads the encoder pyramids, SPyNet's flows and the
+        branch's weights only.  Returns (off1, heads1, off2, heads2) -- refined offsets (rows, 2, h, w) and head channels
+        (rows, 15 D, h, w), frame-major; row block j of the first-order pair belongs to the time step whose flow is flows[:, j],
+        row block j of the second-order pair to the step whose `flow_n1` is flows[:, j] (backward) / flows[:, j + 1] (forward) --
+        or None where `propagate` keeps the per-step form: gradients, the 16-bit modes, the un-fused DCNv2 modes, pyramids that
+        are not views of frame-major tensors, a stack beyond HOIST_MAX_BYTES.
+        Every input is a contiguous run of rows of a frame-major tensor, so nothing is gathered; the refinement chains run once per
+        order (t n and (t - 1) n images), their front ends write into ONE stack and the 5x5 heads are ONE launch over it."""
+        n, t, _, h, w = flows.size()
+        pyr = [getattr(feats[k], "stacked", None) for k in _PYR]
+        if any(p_ is None for p_ in pyr) or len(feats["spatial"]) != t + 1:
+            return None
+        return self._predict_rows(align, pyr, flows.transpose(0, 1).reshape(t * n, 2, h, w), n, backward)      # (a view: compute_flow returns views of the frame-major flows)
+
+    def _predict_rows(self, align, pyr, fl, n, backward):
+        """`_predict_branch` on frame-major tensors: pyr = the three pyramid levels ((t + 1) n rows each), fl = the flows (t n rows)"""
+        t, h, w = int(fl.shape[0]) // n, int(fl.shape[2]), int(fl.shape[3])
+        if t < 1 or AG.needs_grad(fl, pyr, list(align.parameters())) or not align.can_split(pyr[0][:n], fl[:n]):
+            return None
+        rows1, rows2 = t * n, (t - 1) * n
+        if (rows1 + rows2) * h * w * 4 * (self.n_feats + 15 * align.deform_groups) > HOIST_MAX_BYTES:
+            return None
+        lo = lambda rows: [p_[:rows] for p_ in pyr]             # frames 0 .. of every level
+        hi = lambda rows: [p_[p_.shape[0] - rows:] for p_ in pyr]      # frames .. t
+        stack = fl.new_empty(rows1 + rows2, self.n_feats, h, w)
+        # first order: (cur = frame j, nbr = j + 1) backward, (cur = j + 1, nbr = j) forward, flow j
+        cur, nbr = (lo(rows1), hi(rows1)) if backward else (hi(rows1), lo(rows1))
+        off1, _ = align.predict_front(nbr, cur, fl, out=stack[:rows1])
+        off2 = None
+        if rows2:
+            # second order: (cur = j, nbr = j + 2, flow_n1 = j, flow_n2 = j + 1) backward, (cur = j + 2, nbr = j, j + 1, j) forward
+            cur, nbr = (lo(rows2), hi(rows2)) if backward else (hi(rows2), lo(rows2))
+            f_n1, f_n2 = (fl[:rows2], fl[n:]) if backward else (fl[n:], fl[:rows2])
+            flow_n2 = ops.add(f_n1, ops.flow_warp(f_n2, f_n1))                              # :309-310
+            off2, _ = align.predict_front(nbr, cur, flow_n2, out=stack[rows1:])
+        heads = align.heads_of(stack)
+        return off1, heads[:rows1], off2, heads[rows1:]
 
     def propagate(self, feats, flows, module_name):
         """eavsrp_model.py:242-329."""
@@ -277,9 +322,23 @@ class EAVSRP(nn.Module):
         stacked = None
         if not AG.needs_grad(flows, feats["spatial"][0], list(backbone.parameters())):
             stacked = flows.new_empty(len(feats["spatial"]) * n, self.n_feats, h, w)
+        # inference, fp32: the predictors of every time step first, in batched launches; the loop keeps warp + DCNv2 (`sample`)
+        pred = self._predict_branch(align, feats, flows, backward) if (HOIST_PREDICTORS and t > 0) else None
         for i, idx in enumerate(frame_idx):
             cur = [feats[k][mapping_idx[idx]] for k in _PYR]
-            if i > 0:
+            if i > 0 and pred is not None:
+                off1, heads1, off2, heads2 = pred
+                j = flow_idx[i]
+                cond_n1 = align.sample(feat_prop, off1[j * n:(j + 1) * n], heads1[j * n:(j + 1) * n])
+                if i > 1:
+                    j = idx if backward else idx - 2
+                    cond_n2 = align.sample(feats[module_name][-2], off2[j * n:(j + 1) * n], heads2[j * n:(j + 1) * n])
+                else:
+                    if zeros is None:
+                        zeros = torch.zeros_like(cond_n1)
+                    cond_n2 = zeros
+                feat_prop = fusion([cond_n1, cur[0], cond_n2])                          # :313-314
+            elif i > 0:
                 nbr = [feats[k][mapping_idx[idx + step]] for k in _PYR]
                 flow_n1 = flows[:, flow_idx[i]].contiguous()
                 cond_n1 = align(nbr, cur, feat_prop, flow_n1)
@@ -424,7 +483,7 @@ class EAVSRP(nn.Module):
         for iter_ in (1, 2):
             for direction in ("backward", "forward"):
                 module = f"{direction}_{iter_}"
-                self._propagate_long(store, module, list(branches), n, t)
+                self._propagate_long(store, module, list(branches), n, t, hoist=single)
                 branches.append(module)
 
         # -- stage 3, per chunk: reconstruction + upsampling tail
@@ -463,7 +522,7 @@ class EAVSRP(nn.Module):
         part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
         return ops.u8_to_f32(part, hwc=hwc)
 
-    def _propagate_long(self, store, module_name, others, n, t):
+    def _propagate_long(self, store, module_name, others, n, t, hoist=False):
         """`propagate` (eavsrp_model.py:242-329) on a frame store, inference only: the same launches per time step; what a step
         reads comes from the store, whose schedule (`framestore.propagate_reads` / `prefetch_schedule`) has it on the device by
         then, and the step's result goes back to it."""
@@ -474,12 +533,30 @@ class EAVSRP(nn.Module):
         align, fusion, backbone = self.deform_align[module_name], self.fusion[module_name], self.backbone[module_name]
         store.begin(FS.prefetch_schedule(FS.propagate_reads(t, backward, others)))
         feat_prop, zeros, hist = None, None, []
+        # hoist (one chunk = `forward`'s launches, frames resident on the device): the branch's predictors ahead of its time loop, as
+        # `propagate`.  A chunked run asked for activations that do not grow with t and the host cache keeps a window of frames on
+        # the device: both stay with the per-step form
+        pred = None
+        if hoist and HOIST_PREDICTORS and store.cache == "device" and t > 1:
+            pred = self._predict_rows(align, [store.get_range(k, 0, t) for k in _PYR], store.get_range(fkey, 0, t - 1), n, backward)
         for i, idx in enumerate(order):
             store.step(i)
             cur = [store.get(k, idx) for k in _PYR]
             if i == 0:
                 feat_prop = cur[0].new_zeros(cur[0].shape[0], self.n_feats, *cur[0].shape[2:])
                 store.new_branch(module_name, feat_prop)
+            elif pred is not None:
+                off1, heads1, off2, heads2 = pred
+                j = idx if backward else idx - 1
+                cond_n1 = align.sample(feat_prop, off1[j * n:(j + 1) * n], heads1[j * n:(j + 1) * n])
+                if i > 1:
+                    j = idx if backward else idx - 2
+                    cond_n2 = align.sample(hist[-2], off2[j * n:(j + 1) * n], heads2[j * n:(j + 1) * n])
+                else:
+                    if zeros is None:
+                        zeros = torch.zeros_like(cond_n1)
+                    cond_n2 = zeros
+                feat_prop = fusion([cond_n1, cur[0], cond_n2])                          # :313-314
             else:
                 nbr = [store.get(k, idx + step) for k in _PYR]
                 flow_n1 = store.get(fkey, idx if backward else idx - 1)

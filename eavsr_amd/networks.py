@@ -157,8 +157,11 @@ class _AdaptBase(nn.Module):
         self.concat = conv(inplanes * 2, inplanes * 2, groups=inplanes * 2, mode="CL")
         self.concat2 = conv(inplanes * 2, inplanes, groups=inplanes, mode="CL")
 
-    def _frontend(self, x, h_hr):
+    def _frontend(self, x, h_hr, out=None):
+        """out (inference only): rows of a frame-major stack to write into"""
         c1, c2 = self.concat[0], self.concat2[0]
+        if out is not None:
+            return ops.adapt_frontend(x, h_hr, c1.weight, c1.bias, c2.weight, c2.bias, out=out)
         return AG.adapt_frontend(x, h_hr, c1.weight, c1.bias, c2.weight, c2.bias)
 
 
@@ -195,7 +198,10 @@ class AdaptBlockOffset(_AdaptBase):
         """the three 5x5 heads as one (n, 15 D, h, w) tensor: transform g*4+{0..3}, translation 4D + g*2+{0,1}, mask logits
         6D + g*9+k -- what `forward` expands into (offset, mask) and what the fused DCNv2 kernel consumes directly.
         mask_activated: the 9 D mask channels leave as sigmoid(logit) (networks.py:313-314 applied in the convolution's epilogue)"""
-        f = self._frontend(x, h_hr)
+        return self.heads_of(self._frontend(x, h_hr), mask_activated)
+
+    def heads_of(self, f, mask_activated=False):
+        """`heads` behind the front end: the 5x5 convolutions on its output f (n, 64, h, w) -- any number of images in one launch"""
         ws = [self.transform_matrix_conv.weight, self.translation_conv.weight, self.mask_conv.weight]
         bs = [self.transform_matrix_conv.bias, self.translation_conv.bias, self.mask_conv.bias]
         if (BACKBONE_DTYPE is not None and HEADS_IN_16BIT and f.shape[1] == 64 and 15 * self.D <= 128
@@ -262,25 +268,60 @@ class MultiAdSTN(ModulatedDeformConv2d):
                 and ((self.in_channels // self.deform_groups) // 8) & ((self.in_channels // self.deform_groups) // 8 - 1) == 0
                 and nbr.shape == feat_prop.shape)
 
-    def forward(self, nbr_feat_l, ref_feat_l, feat_prop, offset, flag=False):
+    def refine(self, nbr_feat_l, ref_feat_l, offset):
+        """the three-level residual-flow refinement (networks.py:598-619): flow (n,2,h,w) -> refined offset.  Reads the encoder
+        pyramids and the flow only -- nothing of the recurrence."""
         n, _, h, w = offset.shape
+        h4, w4 = int(math.floor(h * 0.25)), int(math.floor(w * 0.25))
+        h2, w2 = int(math.floor(h * 0.5)), int(math.floor(w * 0.5))
+        off_d4 = AG.resize_bilinear_ac(offset, (h4, w4), 0.25)            # :600
+        off_d2 = AG.resize_bilinear_ac(offset, (h2, w2), 0.5)             # :601
+        # level 3 (:604-608)
+        warp4 = AG.flow_warp(nbr_feat_l[2], off_d4)
+        p1 = self._level(self.flow_l3, self.trans_l3, warp4, ref_feat_l[2])
+        p1_up = AG.resize_bilinear_ac(p1, (2 * h4, 2 * w4), 2.0)
+        # level 2 (:609-613)
+        warp2 = AG.flow_warp(nbr_feat_l[1], off_d2, flow2=p1_up)
+        p2 = self._level(self.flow_l2, self.trans_l2, warp2, ref_feat_l[1])
+        p2_up = AG.resize_bilinear_ac(p2, (2 * h2, 2 * w2), 2.0, pre_add=p1_up)
+        # level 1 (:614-619)
+        warp1 = AG.flow_warp(nbr_feat_l[0], offset, flow2=p2_up)
+        p3 = self._level(self.flow_l1, self.trans_l1, warp1, ref_feat_l[0])
+        return AG.add(p3, p2_up, offset)
+
+    # -- the module in two halves (inference, fp32 hot path): everything up to the predictor's heads reads per-frame inputs only
+    # (encoder pyramids, SPyNet's flow, this module's weights) and can run for ALL time steps of a branch before the first one;
+    # the recurrent state enters with the warp of feat_prop and the DCNv2 alone (networks.py:623, :627-630).  The two halves run
+    # the launches of `forward`'s fused branch, minus the pair launch's first half, on more images: the same bits.
+    def can_split(self, nbr, offset) -> bool:
+        """`predict` / `sample` apply: the fused fp32 alignment of `forward` (see _fused_alignment), no gradients anywhere"""
+        return BACKBONE_DTYPE is None and self._fused_alignment(nbr, nbr, offset)
+
+    def predict_front(self, nbr_feat_l, ref_feat_l, flow, out=None):
+        """(refined offset, the predictor front end's output) of any number of images; `out`: rows of a stack for the latter"""
+        offset = self.refine(nbr_feat_l, ref_feat_l, flow)
+        nbr = ops.flow_warp_single(nbr_feat_l[0], offset)                                        # :621
+        return offset, self.adastn._frontend(nbr, ref_feat_l[0], out=out)                        # :625 (first half)
+
+    def heads_of(self, f):
+        """the 15 D head channels of front-end outputs f, the masks activated where `sample`'s kernel takes them so"""
+        return self.adastn.heads_of(f, mask_activated=ops.heads_mask_activated(int(self.weight.shape[1]), self.deform_groups))
+
+    def predict(self, nbr_feat_l, ref_feat_l, flow):
+        """what `sample` needs beside the recurrent state: (refined offset (n,2,h,w), heads (n,15 D,h,w))"""
+        offset, f = self.predict_front(nbr_feat_l, ref_feat_l, flow)
+        return offset, self.heads_of(f)
+
+    def sample(self, feat_prop, offset, heads):
+        """the recurrent half: ONE warp of feat_prop, written in the IL8 layout, and the heads-mode DCNv2 (:623, :627-630)"""
+        feat_il = ops.flow_warp_single(feat_prop, offset, il8=True)
+        act = ops.heads_mask_activated(int(self.weight.shape[1]), self.deform_groups)
+        return ops.dcnv2_il(feat_il, heads, None, self.weight, self.bias, self.deform_groups,
+                            nprod=int(ops.DCN_MODE[2]), heads=True, mask_activated=act)
+
+    def forward(self, nbr_feat_l, ref_feat_l, feat_prop, offset, flag=False):
         if not flag:
-            h4, w4 = int(math.floor(h * 0.25)), int(math.floor(w * 0.25))
-            h2, w2 = int(math.floor(h * 0.5)), int(math.floor(w * 0.5))
-            off_d4 = AG.resize_bilinear_ac(offset, (h4, w4), 0.25)            # :600
-            off_d2 = AG.resize_bilinear_ac(offset, (h2, w2), 0.5)             # :601
-            # level 3 (:604-608)
-            warp4 = AG.flow_warp(nbr_feat_l[2], off_d4)
-            p1 = self._level(self.flow_l3, self.trans_l3, warp4, ref_feat_l[2])
-            p1_up = AG.resize_bilinear_ac(p1, (2 * h4, 2 * w4), 2.0)
-            # level 2 (:609-613)
-            warp2 = AG.flow_warp(nbr_feat_l[1], off_d2, flow2=p1_up)
-            p2 = self._level(self.flow_l2, self.trans_l2, warp2, ref_feat_l[1])
-            p2_up = AG.resize_bilinear_ac(p2, (2 * h2, 2 * w2), 2.0, pre_add=p1_up)
-            # level 1 (:614-619)
-            warp1 = AG.flow_warp(nbr_feat_l[0], offset, flow2=p2_up)
-            p3 = self._level(self.flow_l1, self.trans_l1, warp1, ref_feat_l[0])
-            offset = AG.add(p3, p2_up, offset)
+            offset = self.refine(nbr_feat_l, ref_feat_l, offset)
         if self._fused_alignment(nbr_feat_l[0], feat_prop, offset):
             # inference hot path: both warps by the refined offset in ONE launch, the second one written in the IL8 layout the
             # DCNv2 kernel samples from; the predictor's 15 D head channels go to that kernel as they are (affine -> offsets

@@ -225,10 +225,18 @@ def flow_warp(x: Tensor, flow: Tensor, padding_mode: str = "zeros", flow2: Optio
     return out
 
 
-def flow_warp_pair(xa: Tensor, xb: Tensor, flow: Tensor, flow2: Optional[Tensor] = None, b_il8=False):
+def _warp_pad_code(padding_mode: str, who: str) -> int:
+    pm = {"zeros": 0, "border": 1}.get(padding_mode)
+    if pm is None:
+        raise ValueError(f"{who}: padding_mode={padding_mode!r}: 'zeros' or 'border'")
+    return pm
+
+
+def flow_warp_pair(xa: Tensor, xb: Tensor, flow: Tensor, flow2: Optional[Tensor] = None, b_il8=False, padding_mode: str = "zeros"):
     """(flow_warp(xa, flow [+ flow2]), flow_warp(xb, flow [+ flow2])) in one launch (networks.py:621,623); with b_il8 the
     second result comes in the IL8 layout (n, c/8, h, w, 8) of `dcnv2_il` -- fp32 (True) or rounded to 'fp16' / 'bf16' for
     `dcnv2_il16`."""
+    pad = _warp_pad_code(padding_mode, "flow_warp_pair")
     xa, xb, flow = _chk(xa, "xa"), _chk(xb, "xb"), _chk(flow, "flow")
     n, c, h, w = xa.shape
     if xb.shape != xa.shape or tuple(flow.shape) != (n, 2, h, w):
@@ -250,8 +258,39 @@ def flow_warp_pair(xa: Tensor, xb: Tensor, flow: Tensor, flow2: Optional[Tensor]
     st = _stream(xa)
     _launch("flow_warp_pair", 16.0 * n * c * h * w, 4.0 * n * h * w * (4 * c + 2 + (2 if flow2 is not None else 0)), xa,
             lambda: lib().eavsr_flow_warp_pair_f32(_p(xa), _p(xb), _p(flow), _p(flow2), _p(outa), _p(outb), n, c, h, w,
-                                                   mode, st), "flow_warp_pair")
+                                                   mode | (N.WARP_PAIR_BORDER if pad else 0), st), "flow_warp_pair")
     return outa, outb
+
+
+def flow_warp_single(x: Tensor, flow: Tensor, flow2: Optional[Tensor] = None, il8=False, padding_mode: str = "zeros") -> Tensor:
+    """flow_warp(x, flow [+ flow2]) by ONE half of `flow_warp_pair`'s kernel as a launch of its own (the same kernel code, the same
+    bits as that launch's result for the same tensor): il8=False -- (n, c, h, w), the pair's first result; il8=True / 'fp16' /
+    'bf16' -- the IL8 layout (n, c/8, h, w, 8) of `dcnv2_il` / `dcnv2_il16`, the pair's second result.  The alignment module's two
+    warps once its predictors run ahead of the recurrence (networks.MultiAdSTN.predict / .sample)."""
+    x, flow = _chk(x, "x"), _chk(flow, "flow")
+    n, c, h, w = x.shape
+    if tuple(flow.shape) != (n, 2, h, w):
+        raise ValueError("flow_warp_single: x (n,c,h,w) and flow (n,2,h,w)")
+    if flow2 is not None:
+        flow2 = _chk(flow2, "flow2")
+        if flow2.shape != flow.shape:
+            raise ValueError("flow2 must have the shape of flow")
+    if il8 and c % 8:
+        raise ValueError("flow_warp_single: IL8 output needs c % 8 == 0")
+    pad = _warp_pad_code(padding_mode, "flow_warp_single")
+    if isinstance(il8, str):
+        code = h16_code(il8)                      # 1 fp16, 2 bf16
+        out, mode = torch.empty((n, c // 8, h, w, 8), device=x.device, dtype=_H16_TORCH[code]), 1 + code
+    elif il8:
+        out, mode = torch.empty((n, c // 8, h, w, 8), device=x.device, dtype=torch.float32), 1
+    else:
+        out, mode = torch.empty_like(x), 0
+    st = _stream(x)
+    # (recorded under the kernel's name: both forms launch flow_warp_pair_kernel)
+    _launch("flow_warp_pair", 8.0 * n * c * h * w,
+            4.0 * n * h * w * (2 * c + 2 + (2 if flow2 is not None else 0)), x,
+            lambda: lib().eavsr_flow_warp_single_f32(_p(x), _p(flow), _p(flow2), _p(out), n, c, h, w, mode, pad, st), "flow_warp_single")
+    return out
 
 
 # ------------------------------------------------------------------------------------------
@@ -1286,14 +1325,18 @@ def _packed_wino(weights: Sequence[Tensor], four: bool = False, kind: Optional[s
 # ------------------------------------------------------------------------------------------
 # predictor pieces
 # ------------------------------------------------------------------------------------------
-def adapt_frontend(x: Tensor, h_hr: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor) -> Tensor:
+def adapt_frontend(x: Tensor, h_hr: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """`out`: an existing contiguous fp32 tensor of x's shape to write into (rows of a frame-major stack) instead of a new one"""
     x, h_hr = _chk(x, "x"), _chk(h_hr, "h_hr")
     if x.shape != h_hr.shape:
         raise ValueError("x and h_hr must have the same shape")
     n, c, h, w = x.shape
     if tuple(w1.shape) != (2 * c, 1, 3, 3) or tuple(w2.shape) != (c, 2, 3, 3):
         raise ValueError("adapt_frontend weight shapes")
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("adapt_frontend: `out` must be a contiguous fp32 GPU tensor of x's shape")
     w1, b1, w2, b2 = (_chk(v.detach(), "param") for v in (w1, b1, w2, b2))
     st = _stream(x)
     _launch("adapt_frontend", 2.0 * 27 * c * n * h * w, 4.0 * 3 * c * n * h * w, x,

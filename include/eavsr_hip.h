@@ -45,6 +45,8 @@ extern "C" {
  * `interpolation` and `align_corners` to F.grid_sample): nearest-neighbour sampling, align_corners=False */
 #define EAVSR_WARP_NEAREST 0x10
 #define EAVSR_WARP_NO_ALIGN_CORNERS 0x20
+/* or-ed into outb_il8 of eavsr_flow_warp_pair_f32: border padding (coordinate clamping) instead of zeros (added to ABI 32) */
+#define EAVSR_WARP_PAIR_BORDER 0x10
 
 /* flow layouts of eavsr_flow_warp_f32 */
 #define EAVSR_FLOW_NCHW 0 /* networks.py:699-739      (n,2,h,w): ch0 = x disp, ch1 = y disp */
@@ -81,6 +83,15 @@ int eavsr_flow_warp_f32(const float* x, const float* flow, const float* flow2, f
  * c % 8 == 0), or IL8 rounded to fp16 (outb_il8 = 2) / bf16 (outb_il8 = 3) for eavsr_dcnv2_il16. */
 int eavsr_flow_warp_pair_f32(const float* xa, const float* xb, const float* flow, const float* flow2, float* outa,
                              float* outb, int32_t n, int32_t c, int32_t h, int32_t w, int32_t outb_il8, void* stream);
+
+/* ONE of the two warps above as a launch of its own (added to ABI 32, nothing above changes): one half of the pair kernel, the
+ * same kernel code, so bit-identical to that call's output of the same tensor.  out_layout 0: NCHW fp32 (the path of xa -> outa);
+ * 1 / 2 / 3: IL8 fp32 / fp16 / bf16 (the path of xb -> outb, c % 8 == 0).  padding_mode EAVSR_PAD_ZEROS or EAVSR_PAD_BORDER.
+ * EAVSRP.propagate computes the offset predictors of a whole branch ahead of the recurrence (they read per-frame inputs only):
+ * the neighbour's warp (layout 0) runs there on all time steps at once, the warp of the propagated features (layout 1) is what
+ * is left inside a time step. */
+int eavsr_flow_warp_single_f32(const float* x, const float* flow, const float* flow2, void* out, int32_t n, int32_t c, int32_t h,
+                               int32_t w, int32_t out_layout, int32_t padding_mode, void* stream);
 
 
 /* ---- a7: DCNv2 ------------------------------------------------------------------------------
@@ -304,6 +315,11 @@ int eavsr_pack_conv_weight_x6_multi(const float* const* weights, void* const* pa
                                     int32_t ksize, int32_t c, void* stream);
 int eavsr_conv_f32x6(const float* x, const void* weight_x6, const float* bias, float* out, int32_t n, int32_t cin, int32_t cout,
                      int32_t h, int32_t w, int32_t ksize, int32_t act, float slope, int32_t sigmoid_from, void* stream);
+/* Tiles the busiest workgroup of eavsr_conv_f32x6 walks at this shape on the current device (added to ABI 32, nothing above
+ * changes).  1: one tile per workgroup.  More: the 5x5 64 -> 120 launch of more than one round of workgroups (the predictor's heads
+ * on a stack of images) is persistent -- a workgroup walks its tiles as one stream of chunks, the next tile's operands requested
+ * under the current tile's last chunk and epilogue; per tile the same operations in the same order. */
+int32_t eavsr_conv_f32x6_tiles_per_workgroup(int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ksize);
 /* The 3x3 form for SMALL launches (ABI 27): 64 input channels, one source, the same exact bf16x6 arithmetic; the descriptor's bias,
  * activation (incl. EAVSR_ACT_RELU_MASK), residual and per-tile channel sums (eavsr_conv3x3_x6s_tiles(h, w) rows per sample, 8 x 32
  * pixel tiles) -- no channel-attention prologue, no pixel-shuffle store (-2: call eavsr_conv2d_f32).  RCABlock's convolutions
