@@ -2225,6 +2225,8 @@ def conv_wgrad(dy: Tensor, srcs: Sequence[Tensor], ksize: int, out: Optional[Ten
     blocks = lib().eavsr_conv_wgrad_blocks(n, h, w, ksize)
     if blocks <= 0:
         raise NotImplementedError(f"conv_wgrad: kernel size {ksize}")
+    if n == 0:      # an empty batch has no device pointer to pass (the entry points refuse NULL): zeros, or what was there
+        return dw if accumulate else dw.zero_()
     st = _stream(dy)
     if ksize == 1 and max(int(s.shape[1]) for s in srcs) > 64:
         # every 64-channel block of a source in ONE launch + one reduction (DCNv2's 576-channel column tensor: nine of each before)
@@ -2302,6 +2304,12 @@ def conv_wgrad_multi(dys: Sequence[Tensor], srcs_list: Sequence[Sequence[Tensor]
     if bias_out is not None and (tuple(bias_out.shape) != (cout,) or not bias_out.is_contiguous() or bias_out.dtype != torch.float32
                                  or bias_out.device != dw.device):
         raise ValueError("conv_wgrad_multi: bias_out must be a contiguous fp32 (cout,) tensor on dy's device")
+    if n == 0:      # as conv_wgrad: no pointers to pass
+        if not accumulate:
+            dw.zero_()
+            if bias_out is not None:
+                bias_out.zero_()
+        return dw
     ws = torch.empty(blocks * (64 * 64 * ksize * ksize + 64), device=dw.device, dtype=torch.float32)
     st = _stream(dw)
     dyl = _ptr_array(dys)
