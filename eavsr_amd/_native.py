@@ -206,6 +206,8 @@ SIGNATURES = {
     "eavsr_deflate_huffman_u8": (C.c_int, [vp] * 5 + [i32, i64, i64, vp]),
     # the incoming PNG file: the scanline unfilter (csrc/png_decode.hip; addition to ABI 32)
     "eavsr_png_unfilter_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    # scene-cut statistics of 8-bit frames: luma histogram and frame-to-frame SAD (csrc/scene.hip; addition to ABI 32)
+    "eavsr_frame_change_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     # LPIPS (AlexNet), the report's third column (csrc/lpips.hip; additions to ABI 32)
     "eavsr_lpips_conv_weight_elems": (C.c_int64, [i32, i32, i32]),
     "eavsr_lpips_pack_conv_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),

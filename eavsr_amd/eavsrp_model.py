@@ -409,7 +409,7 @@ class EAVSRP(nn.Module):
         return self.conv_last(hr, residual=skip)                                     # :359-360
 
     # -- long clips ------------------------------------------------------------------------
-    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None):
+    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None):
         """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
 
         The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
@@ -428,7 +428,13 @@ class EAVSRP(nn.Module):
         `np.float32(img) / 255`), so that a host-resident scene crosses the link as bytes.
 
         sink: `sink(first_frame, sr_chunk)` is called once per finished chunk with sr_chunk (n, frames, 3, s h, s w); the SR clip is
-        then never allocated as a whole and None is returned.  Without a sink: the (n, t, 3, s h, s w) tensor `forward` returns."""
+        then never allocated as a whole and None is returned.  Without a sink: the (n, t, 3, s h, s w) tensor `forward` returns.
+
+        emit=(a, b), 0 <= a < b <= t (`forward_segments`): stages 1 and 2 run on all t frames, stage 3 -- the
+        reconstruction and the upsampling tail -- only on frames a .. b - 1.  The sink sees those frames alone, `first_frame` still
+        counted from the start of `lrs`; without a sink the (n, b - a, 3, s h, s w) tensor is returned.  Stage 3 is then always
+        launched under `ops.route_batch(t n)`, one chunk or not: b - a frames on their own could take another kernel than the t
+        frames do, and the result is frames a .. b - 1 of the run without `emit`, bit for bit.  emit=None: today's path."""
         FS.check_cache(cache)
         if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
             raise ValueError("forward_long: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
@@ -454,6 +460,10 @@ class EAVSRP(nn.Module):
         chunks = [(a, min(a + fc, t)) for a in range(0, t, fc)]
         single = len(chunks) == 1
         pin = (lambda rows: None) if single else (lambda rows: rows)      # one chunk IS the whole batch: nothing to pin
+        if emit is not None:
+            ea, eb = (int(v) for v in emit)
+            if not 0 <= ea < eb <= t:
+                raise ValueError(f"forward_long: emit {emit!r}: frames (a, b) with 0 <= a < b <= {t}")
         store = FS.make_store(cache, n, t, device)
 
         # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
@@ -489,27 +499,57 @@ class EAVSRP(nn.Module):
         # -- stage 3, per chunk: reconstruction + upsampling tail
         keys = ["spatial"] + branches + ["lr"]
         out = None
+        if emit is None:
+            tail, pin_tail, base, single_tail = chunks, pin, 0, single
+        else:      # the chunks' parts inside [ea, eb); always pinned: fewer rows than t n must not choose another kernel
+            tail = [(max(a, ea), min(b, eb)) for a, b in chunks if max(a, ea) < min(b, eb)]
+            pin_tail, base, single_tail = (lambda rows: rows), ea, len(tail) == 1
         for key in keys:
-            store.prefetch_range(key, *chunks[0])
-        for ci, (a, b) in enumerate(chunks):
+            store.prefetch_range(key, *tail[0])
+        for ci, (a, b) in enumerate(tail):
             tensors = [store.get_range(key, a, b) for key in keys]
-            if ci + 1 < len(chunks):      # (host cache: the next chunk's copies overlap this chunk's kernels)
+            if ci + 1 < len(tail):      # (host cache: the next chunk's copies overlap this chunk's kernels)
                 for key in keys:
-                    store.prefetch_range(key, *chunks[ci + 1])
-            with ops.route_batch(pin(t * n)):
+                    store.prefetch_range(key, *tail[ci + 1])
+            with ops.route_batch(pin_tail(t * n)):
                 sr = self._upsample_tm(tensors[:-1], tensors[-1])
             del tensors
             sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
             if sink is not None:
                 sink(a, sr.contiguous())
-            elif single:
+            elif single_tail:
                 out = sr.contiguous()
             else:
                 if out is None:
-                    out = sr.new_empty((n, t) + tuple(sr.shape[2:]))
-                out[:, a:b] = sr
+                    out = sr.new_empty((n, tail[-1][1] - base) + tuple(sr.shape[2:]))
+                out[:, a - base:b - base] = sr
             del sr
         store.finish()
+        return out
+
+    def forward_segments(self, lrs, segments, frame_chunk=None, cache="device", sink=None):
+        """A clip of any length as a sequence of `forward_long` calls: for every (start, stop, emit_start, emit_stop) of
+        `segments` (`segments.plan_segments`) `forward_long(lrs[:, start:stop], emit=...)` runs and frames emit_start .. emit_stop - 1
+        of the clip are taken from it -- each frame exactly what `forward_long` gives for it on its window, each emitted once, in
+        increasing order.  What is resident follows the longest window, not t.  `frame_chunk` / `cache` are `forward_long`'s;
+        `sink(first_frame, sr_chunk)` sees frame numbers of `lrs`.  Without a sink: the assembled (n, t, 3, s h, s w) tensor."""
+        from .segments import check_plan
+        if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
+            raise ValueError("forward_segments: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
+        n, t = int(lrs.shape[0]), int(lrs.shape[1])
+        plan = check_plan(t, segments)
+        out = None
+        for start, stop, ea, eb in plan:
+            part_sink = None if sink is None else (lambda first, sr, start=start: sink(start + first, sr))
+            sr = self.forward_long(lrs[:, start:stop], frame_chunk=frame_chunk, cache=cache, sink=part_sink,
+                                   emit=(ea - start, eb - start))
+            if sink is None:
+                if len(plan) == 1:
+                    return sr
+                if out is None:
+                    out = sr.new_empty((n, t) + tuple(sr.shape[2:]))
+                out[:, ea:eb] = sr
+                del sr
         return out
 
     def _ingest(self, lrs, a, b, device, hwc):
@@ -645,6 +685,8 @@ def long_clip_options(opt=None):
         raise ValueError(f"opt.cpu_cache={cc!r}: True or False")
     png_encoder_option(opt)      # validated with the others; read where frames are written (harness.super_resolve)
     png_decoder_option(opt)      # likewise; read where frames are read (harness.super_resolve, at every call)
+    from .segments import segment_options
+    segment_options(opt)         # likewise: opt.max_frames / segment_overlap / scene_cuts, read by harness.super_resolve at every call
     return fc, cc
 
 

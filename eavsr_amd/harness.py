@@ -22,6 +22,8 @@ from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
 
+from .segments import DEFAULT_OVERLAP
+
 Tensor = torch.Tensor
 
 
@@ -652,9 +654,50 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     return out
 
 
+def scene_changes(frames, chunk: int = 64, device=None):
+    """`ops.frame_change` of a clip that need not be on the device: uint8 frames (t, C, h, w), C 1 or 3, or (t, h, w, 3), in host or
+    device memory -> (hist int32 (t, 64), sad int64 (t - 1,)) on the device, the same numbers as one call on the whole clip.  A
+    host-resident clip is uploaded `chunk` frames at a time into one buffer of chunk + 1 frames, each chunk behind the previous
+    chunk's last frame (the pair that straddles two chunks); a device-resident clip is read in place, chunk + 1 frames per call.
+    With a leading clip dimension, (n, t, ...), the statistics are per clip: (n, t, 64) and (n, t - 1).  `device`: where a host clip
+    goes (default: the current device)."""
+    from . import ops
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (4, 5):
+        raise ValueError("scene_changes: a uint8 (t, C, h, w) or (t, h, w, 3) tensor, optionally with a leading n")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"scene_changes: chunk {chunk!r}: a positive number of frames")
+    if frames.dim() == 5:
+        per_clip = [scene_changes(clip, chunk, device) for clip in frames]
+        return torch.stack([h for h, _ in per_clip], 0), torch.stack([s for _, s in per_clip], 0)
+    t = int(frames.shape[0])
+    if t < 1:
+        raise ValueError("scene_changes: at least one frame")
+    hwc = frames.shape[3] == 3 and frames.shape[1] != 3
+    if frames.is_cuda:
+        device = frames.device
+    else:
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    buf = None if frames.is_cuda else torch.empty((min(chunk, t) + 1,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=device)
+    hists, sads, held = [], [], 0      # held: frames of the previous chunk in buf[1:]
+    for a in range(0, t, chunk):
+        k = min(chunk, t - a)
+        if frames.is_cuda:
+            seq = frames[max(a - 1, 0):a + k]
+        else:
+            if a > 0:
+                buf[0].copy_(buf[held])      # the previous chunk's last frame, ahead of the upload that overwrites it
+            buf[1:1 + k].copy_(frames[a:a + k], non_blocking=True)
+            seq, held = (buf[0:1 + k] if a > 0 else buf[1:1 + k]), k
+        h, s = ops.frame_change(seq, hwc=hwc)
+        hists.append(h if a == 0 else h[1:])
+        sads.append(s)
+    return torch.cat(hists, 0), torch.cat(sads, 0)
+
+
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
-                  png_decoder: Optional[str] = None) -> Dict:
+                  png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
+                  cut_thresholds=None, min_scene: int = 2) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -675,8 +718,22 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     `names`: one name per frame (default: the paths' base names, else `000_00000.png`, ...); a name's first three characters are its
     scene in the report.  Returns 'frames', 'seconds' (device-synchronised on both sides), 'frames_per_s', 'peak_bytes'
     (`torch.cuda.max_memory_allocated` over the run), 'written', and with `hr` the 'frame_psnr' / 'frame_ssim' / 'frame_names' /
-    'report' (/ 'frame_lpips') of `evaluate(per_frame=True)`, in (n, t) order."""
+    'report' (/ 'frame_lpips') of `evaluate(per_frame=True)`, in (n, t) order.
+
+    Videos of any length, opt-in: `max_frames` bounds the frames one `forward_long` call sees -- a longer scene runs as
+    windows of max_frames frames that share `overlap` frames (`segments.plan_segments`), so what is resident no longer grows with
+    t; `cuts` keeps the recurrence from running across a scene change: "device" finds the cuts on the 8-bit frames (`scene_changes`
+    + `segments.find_cuts` with `cut_thresholds` = (hist_threshold, sad_threshold), default the untuned constants of `segments`;
+    one clip of uint8 frames only), a list names the scene starts.  Scenes shorter than `min_scene` join their predecessor.  Then
+    `EAVSRP.forward_segments` feeds the same sink: files, metrics and LPIPS are unchanged, every frame is what `forward_long` gives
+    for it on its window.  With max_frames and cuts both None -- and `opt.max_frames` / EAVSR_MAX_FRAMES, `opt.scene_cuts` /
+    EAVSR_SCENE_CUTS unset (`segments.segment_options`; they stand in for arguments left None, and then `opt.segment_overlap` /
+    EAVSR_SEGMENT_OVERLAP for `overlap`; a max_frames from the options without an overlap beside it takes
+    min(overlap, max_frames // 2), so that EAVSR_MAX_FRAMES=8 alone is not refused for the default overlap of 8) -- the one
+    `forward_long` call as before.  The result also carries 'segments' (the plan:
+    (start, stop, emit_start, emit_stop) per window) and 'scene_starts'."""
     from . import ops
+    from .segments import find_cuts, plan_segments, segment_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD
     if png_encoder is None:      # a model wrapper has read its options already; the bare network has none
         png_encoder = getattr(model, "png_encoder", None)
     if png_encoder is None:
@@ -729,6 +786,23 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         lpips = build_lpips(os.fspath(lpips), device=device)
     if lpips is not None and hr is None:
         raise ValueError("super_resolve: lpips needs hr")
+    opt_frames, opt_overlap, opt_cuts = segment_options(getattr(model, "opt", None))
+    if max_frames is None and opt_frames is not None:
+        # (a window bound that comes from the options alone must not be refused for the default overlap of 8)
+        max_frames, overlap = opt_frames, (min(overlap, opt_frames // 2) if opt_overlap is None else opt_overlap)
+    if cuts is None:
+        cuts = opt_cuts
+    if isinstance(cuts, str):
+        if cuts != "device":
+            raise ValueError(f"super_resolve: cuts={cuts!r}: None, 'device' or a list of scene starts")
+        if n != 1 or lrs.dtype != torch.uint8:
+            raise ValueError(f"super_resolve: cuts='device' reads one clip of 8-bit frames, got n={n}, {lrs.dtype}")
+    elif cuts is not None:
+        cuts = sorted(int(c) for c in cuts)
+    hist_thr, sad_thr = (DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD) if cut_thresholds is None else cut_thresholds
+    segmented = max_frames is not None or cuts is not None
+    if segmented:      # max_frames / overlap / min_scene / explicit starts are refused here, before anything is allocated or run
+        plan_segments(t, [] if cuts == "device" else (cuts or []), max_frames, overlap, min_scene)
     written: List[str] = []
     sse_parts, ssim_parts, lpips_parts, counts = [], [], [], []
     staging = _PngStaging() if (out_dir is not None and png_encoder == "device") else None
@@ -777,12 +851,25 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     torch.cuda.reset_peak_memory_stats(device)
     t0 = time.time()
     with torch.no_grad():
-        net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        if not segmented:
+            starts, plan = [], [(0, t, 0, t)]
+            net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        else:
+            if cuts == "device":
+                hwc = lrs.shape[4] == 3 and lrs.shape[2] != 3
+                stat_hist, stat_sad = scene_changes(lrs[0], device=device)
+                pixels = int(lrs.shape[2] * lrs.shape[3]) if hwc else int(lrs.shape[3] * lrs.shape[4])
+                starts = find_cuts(stat_hist, stat_sad, pixels, hist_thr, sad_thr)
+            else:
+                starts = list(cuts or [])
+            plan = plan_segments(t, starts, max_frames, overlap, min_scene)
+            net.forward_segments(lrs, plan, frame_chunk=frame_chunk, cache=cache, sink=sink)
     write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
-           "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written}
+           "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
+           "segments": plan, "scene_starts": starts}
     if hr is not None:
         sse = torch.cat(sse_parts, 1).reshape(-1).tolist()      # (n, t) order, as evaluate
         frame_ssim = torch.cat(ssim_parts, 1).reshape(-1).tolist()

@@ -1564,6 +1564,39 @@ def u8_to_f32(frames: Tensor, hwc: Optional[bool] = None) -> Tensor:
     return out
 
 
+def frame_change(frames: Tensor, hwc: Optional[bool] = None):
+    """Scene-cut statistics of uint8 frames (F, C, h, w) planes, C 1 or 3, or (F, h, w, 3) interleaved (`hwc` as `u8_to_f32`), F >= 1,
+    in one launch (csrc/scene.hip) -> (hist int32 (F, 64), sad int64 (F - 1,)) on the device.  With the luma
+    Y = (77 R + 150 G + 29 B + 128) >> 8 (the sample itself for C = 1): hist[f][Y >> 2] counts frame f's pixels, sad[f] is the sum
+    of |Y_f - Y_{f+1}|.  Integers throughout: exact, and two calls agree bit for bit.  Any base alignment is taken."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frame_change: expected a tensor, got {type(frames)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"frame_change: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise ValueError(f"frame_change: a uint8 (F, C, h, w) or (F, h, w, 3) tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if hwc is None:
+        hwc = frames.shape[3] == 3 and frames.shape[1] != 3
+    if hwc and frames.shape[3] != 3:
+        raise ValueError(f"frame_change: an interleaved source is (F, h, w, 3), got {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    if hwc:
+        f, h, w, c = (int(v) for v in x.shape)
+    else:
+        f, c, h, w = (int(v) for v in x.shape)
+    if f < 1 or c not in (1, 3) or min(h, w) < 1:
+        raise ValueError(f"frame_change: F >= 1 frames of 1 or 3 channels and h, w >= 1, got {tuple(frames.shape)}")
+    if h * w >= 2 ** 31:
+        raise ValueError(f"frame_change: frames of {h * w} pixels, fewer than 2^31 (a histogram bin is 32 bits)")
+    hist = torch.zeros((f, 64), device=x.device, dtype=torch.int32)      # the kernel adds: zeroed on the launch's stream
+    sad = torch.zeros((f - 1,), device=x.device, dtype=torch.int64)
+    st = _stream(x)
+    _launch("frame_change", 0.0, float(x.numel()), x,
+            lambda: lib().eavsr_frame_change_u8(_p(x), _p(hist), _p(sad) if f > 1 else None, f, c, h, w, 1 if hwc else 0, st),
+            "frame_change")
+    return hist, sad
+
+
 def gather_pairs(lr_store: Tensor, hr_store: Optional[Tensor], frames: Tensor, desc: Tensor, patch, scale: int, out=None,
                  may_transpose: bool = True):
     """One launch builds a batch from device-resident 8-bit frames (csrc/batch.hip): the reference's training item -- window, crop,

@@ -1,0 +1,160 @@
+"""Videos of any length: where a scene is cut, and which windows of it `EAVSRP.forward_segments` runs.
+
+Pure host logic, no device: `find_cuts` turns the statistics of `ops.frame_change` into scene starts, `plan_segments` turns scene
+starts and a bound on a window's length into (start, stop, emit_start, emit_stop) windows, `segment_options` reads the opt-in
+settings the way `eavsrp_model.long_clip_options` reads its own.
+
+The thresholds below are SETTINGS, not measurements: nobody has validated them on real footage (no real clips and no trained
+weights exist in this project).  A cut is a hard cut between two consecutive frames; fades and dissolves change neither
+statistic enough between any two frames and are not detected.
+"""
+from __future__ import annotations
+
+import os
+from typing import List, Optional, Sequence, Tuple
+
+# a new scene starts where BOTH hold between two consecutive frames: half the L1 distance of the 64-bin luma histograms, as a
+# fraction of the pixels (0 = the same distribution, 1 = disjoint), and the mean absolute luma difference in 8-bit levels
+DEFAULT_HIST_THRESHOLD = 0.35
+DEFAULT_SAD_THRESHOLD = 12.0
+# frames two neighbouring windows share (harness.super_resolve's default): a setting, not a measured optimum
+DEFAULT_OVERLAP = 8
+# the shortest clip `EAVSRP.forward_long` / `_propagate_long` take is ONE frame (no frame pair: SPyNet is skipped, every branch runs
+# its first step only), so that is min_scene's lower bound; the default of 2 keeps a frame from being restored without a neighbour
+MIN_SCENE_FLOOR = 1
+
+Segment = Tuple[int, int, int, int]
+
+
+def find_cuts(hist, sad, pixels: int, hist_threshold: float = DEFAULT_HIST_THRESHOLD,
+              sad_threshold: float = DEFAULT_SAD_THRESHOLD) -> List[int]:
+    """Scene starts (sorted frame indices > 0) from `ops.frame_change`'s statistics of one clip: hist (F, 64) and sad (F - 1,) --
+    tensors, arrays or nested lists of integers -- and the pixels per frame.  A scene starts at f + 1 iff both
+        sum_b |hist[f][b] - hist[f + 1][b]| / (2 pixels) >= hist_threshold    and    sad[f] / pixels >= sad_threshold.
+    Two criteria because translating content has a large SAD under an unchanged histogram, a brightness change the opposite.
+    Evaluated in Python integers / float64 on the host: F - 1 comparisons."""
+    hist = hist.tolist() if hasattr(hist, "tolist") else [list(r) for r in hist]
+    sad = sad.tolist() if hasattr(sad, "tolist") else list(sad)
+    pixels = int(pixels)
+    if pixels < 1:
+        raise ValueError(f"find_cuts: pixels {pixels!r}: at least 1")
+    if len(hist) != len(sad) + 1:
+        raise ValueError(f"find_cuts: {len(hist)} histograms and {len(sad)} differences: F and F - 1")
+    cuts = []
+    for f in range(len(sad)):
+        d = sum(abs(int(a) - int(b)) for a, b in zip(hist[f], hist[f + 1]))
+        if d / (2.0 * pixels) >= hist_threshold and int(sad[f]) / float(pixels) >= sad_threshold:
+            cuts.append(f + 1)
+    return cuts
+
+
+def keep_starts(t: int, starts: Sequence[int], min_scene: int = 2) -> List[int]:
+    """The scene starts that survive the merge of short scenes: walking `starts` in increasing order, a start is kept only if it lies
+    at least `min_scene` after the last kept one (0 is implicit) and at most at t - min_scene; a scene that would be shorter joins
+    its predecessor."""
+    t, min_scene = int(t), int(min_scene)
+    if t < 1:
+        raise ValueError(f"plan_segments: t {t!r}: at least one frame")
+    if min_scene < MIN_SCENE_FLOOR:
+        raise ValueError(f"plan_segments: min_scene {min_scene!r}: at least {MIN_SCENE_FLOOR} (the shortest clip forward_long takes)")
+    starts = sorted(int(s) for s in starts)
+    for s in starts:
+        if not 0 < s < t:
+            raise ValueError(f"plan_segments: scene start {s} outside (0, {t})")
+    kept, last = [], 0
+    for s in starts:
+        if s - last >= min_scene and s <= t - min_scene:
+            kept.append(s)
+            last = s
+    return kept
+
+
+def plan_segments(t: int, starts: Sequence[int], max_frames: Optional[int] = None, overlap: int = 0,
+                  min_scene: int = 2) -> List[Segment]:
+    """(start, stop, emit_start, emit_stop) windows of a clip of t frames with scenes starting at `starts`: `forward_long` runs on
+    frames [start, stop) and frames [emit_start, emit_stop) of its result are kept.  The emit ranges partition [0, t) in order.
+
+    Scenes shorter than `min_scene` are merged first (`keep_starts`).  A scene [s, e) no longer than `max_frames` (or any scene when
+    max_frames is None) is one window that emits itself.  A longer one is cut into windows of exactly max_frames frames that start
+    at s + k (max_frames - overlap) while s + k (max_frames - overlap) + max_frames < e, and a last window [e - max_frames, e) --
+    shifted back to full length, not left short.  Two consecutive windows [a0, a1), [b0, b1) share [b0, a1): the first emits up to
+    m = (b0 + a1) // 2, the second from m, so every emitted frame lies at least overlap // 2 frames inside any window end that
+    is not a scene end."""
+    kept = keep_starts(t, starts, min_scene)
+    t = int(t)
+    if max_frames is not None:
+        max_frames = int(max_frames)
+        if max_frames < 1:
+            raise ValueError(f"plan_segments: max_frames {max_frames!r}: at least 1, or None")
+    overlap = int(overlap)
+    if overlap < 0:
+        raise ValueError(f"plan_segments: overlap {overlap!r}: not negative")
+    if max_frames is not None and overlap >= max_frames:
+        raise ValueError(f"plan_segments: overlap {overlap} must be smaller than max_frames {max_frames}")
+    plan: List[Segment] = []
+    bounds = [0] + kept + [t]
+    for s, e in zip(bounds[:-1], bounds[1:]):
+        if max_frames is None or e - s <= max_frames:
+            plan.append((s, e, s, e))
+            continue
+        stride = max_frames - overlap
+        windows = []
+        a = s
+        while a + max_frames < e:
+            windows.append((a, a + max_frames))
+            a += stride
+        windows.append((e - max_frames, e))
+        emit_from = s
+        for k, (a0, a1) in enumerate(windows):
+            emit_to = e if k + 1 == len(windows) else (windows[k + 1][0] + a1) // 2
+            plan.append((a0, a1, emit_from, emit_to))
+            emit_from = emit_to
+    return plan
+
+
+def check_plan(t: int, segments: Sequence[Segment]) -> List[Segment]:
+    """a plan as `forward_segments` takes it: windows inside [0, t) whose emit ranges lie inside them and partition [0, t) in order"""
+    plan = [tuple(int(v) for v in seg) for seg in segments]
+    at = 0
+    for seg in plan:
+        if len(seg) != 4:
+            raise ValueError(f"segments: (start, stop, emit_start, emit_stop) tuples, got {seg!r}")
+        a, b, ea, eb = seg
+        if not (0 <= a <= ea < eb <= b <= t) or ea != at:
+            raise ValueError(f"segments: {seg!r} after frame {at} of {t}: emit ranges partition [0, t) in order, inside their windows")
+        at = eb
+    if at != t:
+        raise ValueError(f"segments: the plan emits {at} of {t} frames")
+    return plan
+
+
+def _count(opt, name: str, env_name: str, least: int, what: str) -> Optional[int]:
+    value = getattr(opt, name, None)
+    if value is None:
+        env = os.environ.get(env_name, "")
+        if env == "":
+            return None
+        if not env.isdigit() or int(env) < least:
+            raise ValueError(f"{env_name}={env!r}: {what}")
+        return int(env)
+    if isinstance(value, bool) or not isinstance(value, int) or value < least:
+        raise ValueError(f"opt.{name}={value!r}: {what}, or None")
+    return value
+
+
+def segment_options(opt=None):
+    """(max_frames, overlap, cuts) of the opt-in segmented path, each None where nothing sets it (`harness.super_resolve` then keeps
+    its own default -- with all three None today's one `forward_long` call): `opt.max_frames` (frames per window), `opt.segment_overlap`
+    (frames two windows share), `opt.scene_cuts` ("device": detect cuts on the 8-bit frames), each falling back to the environment
+    where the options do not carry it -- EAVSR_MAX_FRAMES=<positive integer>, EAVSR_SEGMENT_OVERLAP=<integer >= 0>,
+    EAVSR_SCENE_CUTS=device.  None is among the reference's options."""
+    mf = _count(opt, "max_frames", "EAVSR_MAX_FRAMES", 1, "a positive number of frames")
+    ov = _count(opt, "segment_overlap", "EAVSR_SEGMENT_OVERLAP", 0, "a number of frames, 0 or more")
+    sc = getattr(opt, "scene_cuts", None)
+    if sc is None:
+        sc = os.environ.get("EAVSR_SCENE_CUTS", "") or None
+        if sc not in (None, "device"):
+            raise ValueError(f"EAVSR_SCENE_CUTS={sc!r}: device (or unset)")
+    elif sc != "device":
+        raise ValueError(f"opt.scene_cuts={sc!r}: 'device' or None")
+    return mf, ov, sc

@@ -818,6 +818,16 @@ int eavsr_deflate_huffman_u8(const uint8_t* in, uint8_t* out, int64_t* offsets, 
  * NULL pointer: -1; C not 1, 3 or 4, Cout outside 1 .. C, H or W < 1, W C > 2^31 - 2: -2; the scratch allocation failed: -3.
  * F = 0: nothing is launched. */
 int eavsr_png_unfilter_u8(const uint8_t* rows, uint8_t* out, int32_t F, int32_t H, int32_t W, int32_t C, int32_t Cout, void* stream);
+/* ---- scene-cut statistics of 8-bit frames (added to ABI 32, nothing above changes) ----------------------------------------------------
+ * csrc/scene.hip, one launch.  in: uint8, (F, C, H, W) planes (hwc = 0, C 1 or 3) or (F, H, W, 3) interleaved (hwc = 1, C must be 3),
+ * any alignment.  Per pixel the luma Y = (77 R + 150 G + 29 B + 128) >> 8 (C = 3) or the sample itself (C = 1); all integers, so the
+ * results are exact and two calls agree bit for bit.
+ *   hist (F, 64) int32:  hist[f][Y >> 2] += 1 for every pixel of frame f.
+ *   sad (F - 1) int64:   sad[f] += sum over the pixels of |Y_f - Y_{f+1}|; may be NULL when F = 1.
+ * Both are ADDED to with integer atomics: the caller zeroes them on `stream` ahead of the call.  hist 4-byte, sad 8-byte aligned.
+ * NULL pointer: -1; F < 1, C not 1 or 3, an interleaved source with C != 3, H W >= 2^31 (a bin is 32 bits), misaligned outputs: -2. */
+int eavsr_frame_change_u8(const uint8_t* in, int32_t* hist, int64_t* sad, int32_t F, int32_t C, int32_t H, int32_t W, int32_t hwc,
+                          void* stream);
 /* ---- f4: LPIPS (AlexNet), the report's third column (added to ABI 32, nothing above changes) ---------------------------------------
  * replaces `lpips.LPIPS(net='alex')` as psnr_total.py:27-35 calls it on the stored 8-bit frames.  Pinned to the published definition
  * (lpips 0.1, eval mode, spatial=False, normalize=False), not to the package, which is not available to this project's tests.
