@@ -195,6 +195,8 @@ SIGNATURES = {
     "eavsr_frame_metrics_f32": (C.c_int, [vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "eavsr_rgb8_f32": (C.c_int, [vp, f32, i32, i32, i32, i32, vp, vp]),
     "eavsr_u8_to_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    # padded ingest: frames of any size (csrc/ingest_pad.hip; addition to ABI 32)
+    "eavsr_ingest_pad": (C.c_int, [vp, vp] + [i32] * 8 + [vp]),
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
     # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)

@@ -409,7 +409,7 @@ class EAVSRP(nn.Module):
         return self.conv_last(hr, residual=skip)                                     # :359-360
 
     # -- long clips ------------------------------------------------------------------------
-    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None):
+    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None):
         """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
 
         The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
@@ -434,8 +434,17 @@ class EAVSRP(nn.Module):
         reconstruction and the upsampling tail -- only on frames a .. b - 1.  The sink sees those frames alone, `first_frame` still
         counted from the start of `lrs`; without a sink the (n, b - a, 3, s h, s w) tensor is returned.  Stage 3 is then always
         launched under `ops.route_batch(t n)`, one chunk or not: b - a frames on their own could take another kernel than the t
-        frames do, and the result is frames a .. b - 1 of the run without `emit`, bit for bit.  emit=None: today's path."""
+        frames do, and the result is frames a .. b - 1 of the run without `emit`, bit for bit.  emit=None: today's path.
+
+        pad="reflect" / "edge" (DESIGN 7i): frames of ANY size.  Where (H, W) = `segments.padded_size(h, w)` differs from (h, w) the
+        ingest pads every frame at the bottom and right while it converts it (`ops.ingest_pad`, one launch per chunk, all three
+        kinds of source; a host-resident uint8 clip still crosses the link as its unpadded bytes), everything downstream runs on
+        H x W frames, and every SR chunk is cropped to (s h, s w) before the sink sees it or it is stored: the result is
+        `forward_long(<the clip padded by hand>)[..., :s h, :s w]`, bit for bit.  Where the size needs no padding the launches are
+        those of pad=None.  pad=None: today's path, the assert below and `ops.pyramid`'s ValueError for other sizes included."""
+        from .segments import check_pad, padded_size
         FS.check_cache(cache)
+        check_pad(pad, "forward_long: pad")
         if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
             raise ValueError("forward_long: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
         if torch.is_grad_enabled():
@@ -451,7 +460,10 @@ class EAVSRP(nn.Module):
         hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
         n, t = int(lrs.shape[0]), int(lrs.shape[1])
         c, h, w = (3, int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[2:])
-        assert h >= 64 and w >= 64, (
+        size = None      # (H, W) of the padded frames, where `pad` is set and the size needs it
+        if pad is not None and padded_size(h, w) != (h, w):
+            size = padded_size(h, w)
+        assert size is not None or (h >= 64 and w >= 64), (
             'The height and width of inputs should be at least 64, '
             f'but got {h} and {w}.')
         if frame_chunk is not None and int(frame_chunk) < 1:
@@ -469,7 +481,7 @@ class EAVSRP(nn.Module):
         # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
         last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
         for a, b in chunks:
-            lr_c = self._ingest(lrs, a, b, device, hwc)
+            lr_c = self._ingest(lrs, a, b, device, hwc, pad, size)
             store.put_range("lr", a, lr_c)
             seq = lr_c if last is None else torch.cat([last, lr_c], 0)
             m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
@@ -515,6 +527,8 @@ class EAVSRP(nn.Module):
                 sr = self._upsample_tm(tensors[:-1], tensors[-1])
             del tensors
             sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
+            if size is not None:      # the crop: a view here, one copy of the chunk's output where it is made contiguous / stored below
+                sr = sr[..., :self.scale * h, :self.scale * w]
             if sink is not None:
                 sink(a, sr.contiguous())
             elif single_tail:
@@ -532,8 +546,16 @@ class EAVSRP(nn.Module):
         `segments` (`segments.plan_segments`) `forward_long(lrs[:, start:stop], emit=...)` runs and frames emit_start .. emit_stop - 1
         of the clip are taken from it -- each frame exactly what `forward_long` gives for it on its window, each emitted once, in
         increasing order.  What is resident follows the longest window, not t.  `frame_chunk` / `cache` are `forward_long`'s;
-        `sink(first_frame, sr_chunk)` sees frame numbers of `lrs`.  Without a sink: the assembled (n, t, 3, s h, s w) tensor."""
-        from .segments import check_plan
+        `sink(first_frame, sr_chunk)` sees frame numbers of `lrs`.  Without a sink: the assembled (n, t, 3, s h, s w) tensor.
+        Frames of any size: `forward_segments_padded`."""
+        return self.forward_segments_padded(lrs, segments, None, frame_chunk=frame_chunk, cache=cache, sink=sink)
+
+    def forward_segments_padded(self, lrs, segments, pad, frame_chunk=None, cache="device", sink=None):
+        """`forward_segments` for frames of any size: `pad` is `forward_long`'s -- "reflect" / "edge": every window is
+        padded on the device while it is converted and its SR frames are cropped; None: `forward_segments` itself.  A method of its
+        own: `forward_segments` keeps the parameter list it was published with."""
+        from .segments import check_pad, check_plan
+        check_pad(pad, "forward_segments_padded: pad")
         if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
             raise ValueError("forward_segments: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
         n, t = int(lrs.shape[0]), int(lrs.shape[1])
@@ -542,7 +564,7 @@ class EAVSRP(nn.Module):
         for start, stop, ea, eb in plan:
             part_sink = None if sink is None else (lambda first, sr, start=start: sink(start + first, sr))
             sr = self.forward_long(lrs[:, start:stop], frame_chunk=frame_chunk, cache=cache, sink=part_sink,
-                                   emit=(ea - start, eb - start))
+                                   emit=(ea - start, eb - start), pad=pad)
             if sink is None:
                 if len(plan) == 1:
                     return sr
@@ -552,14 +574,18 @@ class EAVSRP(nn.Module):
                 del sr
         return out
 
-    def _ingest(self, lrs, a, b, device, hwc):
-        """frames a .. b of the clip as frame-major fp32 ((b - a) n, 3, h, w) on the device"""
+    def _ingest(self, lrs, a, b, device, hwc, pad=None, size=None):
+        """frames a .. b of the clip as frame-major fp32 ((b - a) n, 3, h, w) on the device; with `size` = (H, W): padded to it at
+        the bottom and right (`ops.ingest_pad`, mode `pad`) in the launch that converts them"""
         part = lrs[:, a:b]
         if part.dtype != torch.uint8:
-            return part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
+            part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
+            return part if size is None else ops.ingest_pad(part, size[0], size[1], mode=pad, hwc=False)
         if not part.is_cuda:
-            part = part.to(device, non_blocking=True)      # bytes cross the link
+            part = part.to(device, non_blocking=True)      # bytes cross the link (unpadded)
         part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
+        if size is not None:
+            return ops.ingest_pad(part, size[0], size[1], mode=pad, hwc=hwc)
         return ops.u8_to_f32(part, hwc=hwc)
 
     def _propagate_long(self, store, module_name, others, n, t, hoist=False):
@@ -687,6 +713,8 @@ def long_clip_options(opt=None):
     png_decoder_option(opt)      # likewise; read where frames are read (harness.super_resolve, at every call)
     from .segments import segment_options
     segment_options(opt)         # likewise: opt.max_frames / segment_overlap / scene_cuts, read by harness.super_resolve at every call
+    from .segments import pad_option
+    pad_option(opt)              # likewise: opt.pad_frames, read by EAVSRPModel.forward and harness.super_resolve
     return fc, cc
 
 
@@ -736,6 +764,9 @@ class EAVSRPModel:
         # opt.frame_chunk / opt.cpu_cache (not among the reference's options): the opt-in long-clip inference path (EAVSRP.forward_long)
         self.frame_chunk, self.cpu_cache = long_clip_options(opt)
         self.png_encoder = png_encoder_option(opt)
+        # opt.pad_frames (not among the reference's options): frames of any size outside training (EAVSRP.forward_long(pad=...))
+        from .segments import pad_option
+        self.pad_frames = pad_option(opt)
         # opt.train_precision (not among the reference's options): the opt-in bf16 training mode (networks.set_train_precision)
         if getattr(opt, "train_precision", None) is not None:
             N.set_train_precision(opt.train_precision)
@@ -829,10 +860,11 @@ class EAVSRPModel:
                 self.data_sr_seq = self.data_sr_seq * self.mask
             return
         start = time.time()
-        if not self.isTrain and (self.frame_chunk is not None or self.cpu_cache):
+        long_path = not self.isTrain and (self.frame_chunk is not None or self.cpu_cache)
+        if long_path or (not self.isTrain and self.pad_frames is not None):      # frames of any size go through forward_long too
             with torch.no_grad():
                 self.data_sr_seq = self.netEAVSRP.forward_long(self.data_lr_seq, frame_chunk=self.frame_chunk,
-                                                               cache="host" if self.cpu_cache else "device")
+                                                               cache="host" if self.cpu_cache else "device", pad=self.pad_frames)
         else:
             self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
         self.data_sr = self.data_sr_seq[:, self.idx]

@@ -697,7 +697,7 @@ def scene_changes(frames, chunk: int = 64, device=None):
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
-                  cut_thresholds=None, min_scene: int = 2) -> Dict:
+                  cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -731,9 +731,18 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     EAVSR_SEGMENT_OVERLAP for `overlap`; a max_frames from the options without an overlap beside it takes
     min(overlap, max_frames // 2), so that EAVSR_MAX_FRAMES=8 alone is not refused for the default overlap of 8) -- the one
     `forward_long` call as before.  The result also carries 'segments' (the plan:
-    (start, stop, emit_start, emit_stop) per window) and 'scene_starts'."""
+    (start, stop, emit_start, emit_stop) per window) and 'scene_starts'.
+
+    Frames of any size, opt-in: `pad` = "reflect" / "edge" is `forward_long`'s -- frames whose sides are below 64 or no
+    multiple of 4 are padded at the bottom and right while the device converts them and every SR chunk is cropped before the sink
+    sees it, so `hr` is expected, and the files are written, at (s h, s w); the scene-cut statistics read the unpadded bytes.
+    None: `opt.pad_frames` of a model wrapper, else EAVSR_PAD_FRAMES=reflect|edge, else off -- such sizes are refused as before."""
     from . import ops
-    from .segments import find_cuts, plan_segments, segment_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD
+    from .segments import (check_pad, find_cuts, pad_option, plan_segments, segment_options, DEFAULT_HIST_THRESHOLD,
+                           DEFAULT_SAD_THRESHOLD)
+    if pad is None:
+        pad = pad_option(getattr(model, "opt", None))
+    check_pad(pad, "super_resolve: pad")
     if png_encoder is None:      # a model wrapper has read its options already; the bare network has none
         png_encoder = getattr(model, "png_encoder", None)
     if png_encoder is None:
@@ -853,7 +862,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     with torch.no_grad():
         if not segmented:
             starts, plan = [], [(0, t, 0, t)]
-            net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
         else:
             if cuts == "device":
                 hwc = lrs.shape[4] == 3 and lrs.shape[2] != 3
@@ -863,7 +872,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
             else:
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
-            net.forward_segments(lrs, plan, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            net.forward_segments_padded(lrs, plan, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
     write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0

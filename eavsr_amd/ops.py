@@ -1564,6 +1564,51 @@ def u8_to_f32(frames: Tensor, hwc: Optional[bool] = None) -> Tensor:
     return out
 
 
+def ingest_pad(frames: Tensor, H: int, W: int, mode: str = "reflect", hwc: Optional[bool] = None) -> Tensor:
+    """Frames of any size -> fp32 (F, C, H, W), H >= h and W >= w, padded at the bottom and right in one launch (csrc/ingest_pad.hip,
+    DESIGN 7i): out[f, c, y, x] = src[f, c, ry(y), rx(x)] with `segments.pad_index` -- mode "reflect" is np.pad(mode="reflect") for
+    every pad width, "edge" repeats the last row / column.  `frames`: uint8 (F, C, h, w) planes or (F, h, w, 3) interleaved (`hwc` as
+    `u8_to_f32`), every sample float(v) / 255.0f as `u8_to_f32` gives it, at any base alignment; or fp32 (F, C, h, w), copied bit
+    for bit.  F == 0: an empty tensor, nothing is launched.  H == h and W == w: `u8_to_f32`'s result (a copy for fp32)."""
+    from .segments import PAD_MODES
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"ingest_pad: expected a tensor, got {type(frames)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"ingest_pad: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4:
+        raise ValueError(f"ingest_pad: a uint8 (F, C, h, w) / (F, h, w, 3) or fp32 (F, C, h, w) tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if mode not in PAD_MODES:
+        raise ValueError(f"ingest_pad: mode {mode!r}: one of {PAD_MODES}")
+    u8 = frames.dtype == torch.uint8
+    if hwc is None:
+        hwc = u8 and frames.shape[3] == 3 and frames.shape[1] != 3
+    if hwc and (not u8 or frames.shape[3] != 3):
+        raise ValueError(f"ingest_pad: an interleaved source is uint8 (F, h, w, 3), got {frames.dtype} {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    if hwc:
+        f, h, w, c = (int(v) for v in x.shape)
+    else:
+        f, c, h, w = (int(v) for v in x.shape)
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (H, W)):
+        raise ValueError(f"ingest_pad: H, W {H!r}, {W!r}: integers")
+    if f > 0 and (c < 1 or h < 1 or w < 1):
+        raise ValueError(f"ingest_pad: empty frames {tuple(x.shape)}")
+    if H < h or W < w:
+        raise ValueError(f"ingest_pad: the output {H} x {W} is smaller than the frames {h} x {w} (padding only)")
+    if f > 65535 or c > 65535:
+        raise ValueError(f"ingest_pad: F={f}, C={c}: at most 65535 each (grid dimensions)")
+    out = torch.empty((f, c, H, W), device=x.device, dtype=torch.float32)
+    if f == 0:
+        return out
+    if out.data_ptr() % 16:
+        raise ValueError("ingest_pad: the output is not 16-byte aligned")
+    st = _stream(x)
+    kind = 1 if hwc else (0 if u8 else 2)
+    _launch("ingest_pad", 0.0, float(x.numel() * x.element_size() + 4 * out.numel()), x,
+            lambda: lib().eavsr_ingest_pad(_p(x), _p(out), f, c, h, w, H, W, kind, PAD_MODES.index(mode), st), "ingest_pad")
+    return out
+
+
 def frame_change(frames: Tensor, hwc: Optional[bool] = None):
     """Scene-cut statistics of uint8 frames (F, C, h, w) planes, C 1 or 3, or (F, h, w, 3) interleaved (`hwc` as `u8_to_f32`), F >= 1,
     in one launch (csrc/scene.hip) -> (hist int32 (F, 64), sad int64 (F - 1,)) on the device.  With the luma

@@ -2,7 +2,8 @@
 
 Pure host logic, no device: `find_cuts` turns the statistics of `ops.frame_change` into scene starts, `plan_segments` turns scene
 starts and a bound on a window's length into (start, stop, emit_start, emit_stop) windows, `segment_options` reads the opt-in
-settings the way `eavsrp_model.long_clip_options` reads its own.
+settings the way `eavsrp_model.long_clip_options` reads its own.  And frames of any size: `padded_size`, `pad_index` and
+`pad_option` at the end of the file.
 
 The thresholds below are SETTINGS, not measurements: nobody has validated them on real footage (no real clips and no trained
 weights exist in this project).  A cut is a hard cut between two consecutive frames; fades and dissolves change neither
@@ -158,3 +159,53 @@ def segment_options(opt=None):
     elif sc != "device":
         raise ValueError(f"opt.scene_cuts={sc!r}: 'device' or None")
     return mf, ov, sc
+
+
+# -- frames of any size: what `ops.ingest_pad` pads to, and which source sample a padded sample repeats ------------------
+PAD_MODES = ("reflect", "edge")      # the order is the C entry point's `mode` argument
+MIN_SIDE = 64                        # `EAVSRP.forward` asserts h, w >= 64 (SPyNet's six-level pyramid)
+SIDE_MULTIPLE = 4                    # `ops.pyramid` halves the features twice
+
+
+def padded_size(h: int, w: int) -> Tuple[int, int]:
+    """(H, W) the network takes for frames of h x w: each side rounded up to a multiple of 4, and to 64 where it is smaller"""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"padded_size: frames of {h} x {w}")
+    up = lambda v: max(MIN_SIDE, SIDE_MULTIPLE * ((v + SIDE_MULTIPLE - 1) // SIDE_MULTIPLE))
+    return up(h), up(w)
+
+
+def pad_index(i: int, s: int, mode: str = "reflect") -> int:
+    """The source index, in [0, s), that index i >= 0 of a padded axis repeats (`ops.ingest_pad`, csrc/ingest_pad.hip `src_index`).
+    "reflect": the triangle wave m = i mod 2 (s - 1), r = m if m < s else 2 (s - 1) - m, and 0 for s = 1 -- np.pad(mode="reflect")
+    for every pad width, pads several times the axis included.  "edge": min(i, s - 1)."""
+    i, s = int(i), int(s)
+    if i < 0 or s < 1:
+        raise ValueError(f"pad_index: index {i} of an axis of {s}")
+    if mode not in PAD_MODES:
+        raise ValueError(f"pad_index: mode {mode!r}: one of {PAD_MODES}")
+    if i < s:
+        return i
+    if mode == "edge" or s == 1:
+        return s - 1
+    period = 2 * (s - 1)
+    m = i % period
+    return m if m < s else period - m
+
+
+def check_pad(pad, what: str = "pad") -> Optional[str]:
+    """None, "reflect" or "edge"; anything else is a ValueError that names `what`"""
+    if pad is not None and pad not in PAD_MODES:
+        raise ValueError(f"{what}={pad!r}: 'reflect', 'edge' or None")
+    return pad
+
+
+def pad_option(opt=None) -> Optional[str]:
+    """`opt.pad_frames` ("reflect" / "edge": frames of any size are padded on the device and the output is cropped), falling back to
+    the environment where the options do not carry it (EAVSR_PAD_FRAMES=reflect|edge), None -- off -- where neither does.  Not
+    among the reference's options."""
+    pad = getattr(opt, "pad_frames", None)
+    if pad is not None:
+        return check_pad(pad, "opt.pad_frames")
+    return check_pad(os.environ.get("EAVSR_PAD_FRAMES", "") or None, "EAVSR_PAD_FRAMES")

@@ -746,6 +746,17 @@ int eavsr_rgb8_f32(const float* sr, float scale, int32_t F, int32_t C, int32_t H
  * (hwc = 1, C must be 3) -> out fp32 (F, C, H, W), every sample float(v) / 255.0f as an IEEE division.  `in` may have any
  * alignment; out must be 16-byte aligned (-2 otherwise).  NULL pointer: -1; F > 65535, bad dims or layout: -2. */
 int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t H, int32_t W, int32_t hwc, void* stream);
+/* ---- padded ingest: frames of any size (csrc/ingest_pad.hip; added to ABI 32, nothing above changes) ------------------------------------
+ * out fp32 (F, C, H, W), H >= h, W >= w, padded at the bottom and right only, one launch:
+ *     out[f, c, y, x] = conv(in[f, c, ry(y), rx(x)])
+ * mode 0 (reflect): r(i) = (m < s ? m : 2 (s - 1) - m), m = i mod 2 (s - 1); r = 0 for s = 1 -- np.pad(mode="reflect") for every pad
+ * width.  mode 1 (edge): r(i) = min(i, s - 1).
+ * kind 0: in uint8 (F, C, h, w) planes; kind 1: in uint8 (F, h, w, 3) interleaved (C must be 3); both: conv(v) = float(v) / 255.0f,
+ * an IEEE division as eavsr_u8_to_f32, `in` at any byte alignment.  kind 2: in fp32 (F, C, h, w) planes, conv copies the 32 bits.
+ * W % 4 == 0: 16-byte stores; any other W: one sample per lane.  out must be 16-byte aligned.
+ * NULL pointer: -1; H < h, W < w, bad kind / mode / dims, F > 65535, C > 65535, a misaligned out: -2.  F == 0: 0, nothing is launched. */
+int eavsr_ingest_pad(const void* in, float* out, int32_t F, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, int32_t kind,
+                     int32_t mode, void* stream);
 /* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
  * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
  * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
