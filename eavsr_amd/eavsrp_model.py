@@ -409,7 +409,7 @@ class EAVSRP(nn.Module):
         return self.conv_last(hr, residual=skip)                                     # :359-360
 
     # -- long clips ------------------------------------------------------------------------
-    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None):
+    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None):
         """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
 
         The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
@@ -441,7 +441,13 @@ class EAVSRP(nn.Module):
         kinds of source; a host-resident uint8 clip still crosses the link as its unpadded bytes), everything downstream runs on
         H x W frames, and every SR chunk is cropped to (s h, s w) before the sink sees it or it is stored: the result is
         `forward_long(<the clip padded by hand>)[..., :s h, :s w]`, bit for bit.  Where the size needs no padding the launches are
-        those of pad=None.  pad=None: today's path, the assert below and `ops.pyramid`'s ValueError for other sizes included."""
+        those of pad=None.  pad=None: today's path, the assert below and `ops.pyramid`'s ValueError for other sizes included.
+
+        window=(y0, y1, x0, x1) (`forward_tiled`): the clip is the window [y0, y1) x [x0, x1) of `lrs`' frames -- h, w are
+        the window's size from here on, and the ingest reads the window in place (`ops.ingest_window`, one launch per chunk, all three
+        kinds of source, padding to `padded_size` with `pad` in the same launch where the window's size needs it).  Everything else,
+        the crop included, is unchanged: the result is `forward_long(lrs[..., y0:y1, x0:x1].contiguous(), ...)`, bit for bit.
+        window=None: today's launches."""
         from .segments import check_pad, padded_size
         FS.check_cache(cache)
         check_pad(pad, "forward_long: pad")
@@ -450,6 +456,16 @@ class EAVSRP(nn.Module):
         if torch.is_grad_enabled():
             raise RuntimeError("forward_long is inference only: call it under torch.no_grad() (training runs `forward`)")
         u8 = lrs.dtype == torch.uint8
+        hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
+        n, t = int(lrs.shape[0]), int(lrs.shape[1])
+        c, h, w = (3, int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[2:])
+        if window is not None:
+            if len(window) != 4 or any(isinstance(v, bool) or not isinstance(v, int) for v in window):
+                raise ValueError(f"forward_long: window {window!r}: integers (y0, y1, x0, x1)")
+            y0, y1, x0, x1 = window = tuple(window)
+            if not (0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
+                raise ValueError(f"forward_long: window {window!r} does not lie inside frames of {h} x {w}")
+            h, w = y1 - y0, x1 - x0
         if not u8 and not lrs.is_cuda:
             raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path); for a CPU reference use "
                                "the original repository with --gpu_ids -1")
@@ -457,9 +473,6 @@ class EAVSRP(nn.Module):
         if device.type != "cuda":
             raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path): a uint8 clip in host memory needs the "
                                "network on the GPU")
-        hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
-        n, t = int(lrs.shape[0]), int(lrs.shape[1])
-        c, h, w = (3, int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[2:])
         size = None      # (H, W) of the padded frames, where `pad` is set and the size needs it
         if pad is not None and padded_size(h, w) != (h, w):
             size = padded_size(h, w)
@@ -481,7 +494,7 @@ class EAVSRP(nn.Module):
         # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
         last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
         for a, b in chunks:
-            lr_c = self._ingest(lrs, a, b, device, hwc, pad, size)
+            lr_c = self._ingest(lrs, a, b, device, hwc, pad, size, window)
             store.put_range("lr", a, lr_c)
             seq = lr_c if last is None else torch.cat([last, lr_c], 0)
             m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
@@ -529,8 +542,8 @@ class EAVSRP(nn.Module):
             sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
             if size is not None:      # the crop: a view here, one copy of the chunk's output where it is made contiguous / stored below
                 sr = sr[..., :self.scale * h, :self.scale * w]
-            if sink is not None:
-                sink(a, sr.contiguous())
+            if sink is not None:      # (`forward_tiled`'s own sink blends the view as it stands: `ops.tile_blend` reads strides)
+                sink(a, sr if getattr(sink, "takes_views", False) else sr.contiguous())
             elif single_tail:
                 out = sr.contiguous()
             else:
@@ -574,10 +587,97 @@ class EAVSRP(nn.Module):
                 del sr
         return out
 
-    def _ingest(self, lrs, a, b, device, hwc, pad=None, size=None):
+    def forward_tiled(self, lrs, tile, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device", sink=None):
+        """Frames of any resolution, inference only: the network runs on overlapped spatial tiles and the SR tiles are
+        blended into the frame with a feathered partition of unity, so what is resident follows the tile's area, not the frame's.
+
+        `tile` (an int or (rows, columns), LR pixels) and `overlap` give the plan (`segments.plan_tiles`: windows of one size in
+        row-major order); `lrs`, `frame_chunk`, `cache`, `pad` and `sink` are `forward_long`'s, `segments` is `forward_segments`'
+        plan (None: the whole clip as one window of frames).  Per segment a host-resident 8-bit window of frames is uploaded once,
+        as bytes, and every tile reads it there; an fp32 accumulator (n, emitted frames, 3, s h, s w) is zeroed; for every tile in
+        plan order `forward_long(window=..., emit=..., pad=pad)` runs with a sink that adds each SR chunk, as the view it is, to the
+        accumulator (`ops.tile_blend` with the rows of `segments.tile_weights`); the accumulator is then handed to
+        `sink(first_frame, chunk)` in `frame_chunk` pieces, or assembled and returned where there is no sink.  One accumulator
+        serves all segments (a sink that keeps its chunks gets copies while another segment is still to come).
+
+        Contract: the result is that blend -- tile order, weights, (wy wx) sr then the sum, each rounded to fp32 -- of `forward_long`
+        on each hand-cropped window, bit for bit.  It is NOT the whole-frame result: flow, DCN offsets and the 120 residual blocks
+        of a tile see the tile alone, and near a seam two such views are averaged.
+
+        Where one tile covers the frame the call IS `forward_long` / `forward_segments_padded`: no accumulator, no blend."""
+        from .segments import check_pad, check_plan, check_tile, plan_tiles, tile_axis, tile_weights
+        FS.check_cache(cache)
+        check_pad(pad, "forward_tiled: pad")
+        if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
+            raise ValueError("forward_tiled: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_tiled is inference only: call it under torch.no_grad() (training runs `forward`)")
+        u8 = lrs.dtype == torch.uint8
+        hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
+        n, t = int(lrs.shape[0]), int(lrs.shape[1])
+        h, w = (int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[3:])
+        sides = check_tile(tile, "forward_tiled: tile")
+        if sides is None:
+            raise ValueError("forward_tiled: tile=None (the untiled call is `forward_long`)")
+        tiles = plan_tiles(h, w, sides, overlap)      # refuses a bad tile / overlap before anything runs
+        if frame_chunk is not None and int(frame_chunk) < 1:
+            raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
+        plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
+        if len(tiles) == 1:
+            if segments is None:
+                return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
+            return self.forward_segments_padded(lrs, plan, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        if not u8 and not lrs.is_cuda:
+            raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path); for a CPU reference use "
+                               "the original repository with --gpu_ids -1")
+        device = lrs.device if lrs.is_cuda else next(self.parameters()).device
+        if device.type != "cuda":
+            raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path): a uint8 clip in host memory needs the "
+                               "network on the GPU")
+        s = self.scale
+        rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
+        wy = torch.from_numpy(tile_weights(h, rows, s)).to(device)      # (rows of tiles, s th): row i serves every tile of row i
+        wx = torch.from_numpy(tile_weights(w, cols, s)).to(device)
+        longest = max(eb - ea for _, _, ea, eb in plan)
+        per_frame = 3 * s * h * s * w
+        store = torch.empty(n * longest * per_frame, device=device, dtype=torch.float32)
+        out = None
+        for si, (start, stop, ea, eb) in enumerate(plan):
+            part = lrs[:, start:stop]
+            if not part.is_cuda:
+                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile reads it on the device
+            k = eb - ea
+            acc = store[:n * k * per_frame].view(n, k, 3, s * h, s * w)
+            acc.zero_()
+            for ti, (y0, y1, x0, x1) in enumerate(tiles):
+                blend = _TileBlend(acc, ea - start, s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)])
+                self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=(ea - start, eb - start), pad=pad,
+                                  window=(y0, y1, x0, x1))
+            if sink is not None:
+                fc = k if frame_chunk is None else min(int(frame_chunk), k)
+                for a in range(0, k, fc):
+                    chunk = acc[:, a:a + fc]
+                    sink(ea + a, chunk.clone() if si + 1 < len(plan) else chunk.contiguous())
+            elif len(plan) == 1:
+                return acc
+            else:
+                if out is None:
+                    out = acc.new_empty((n, t) + tuple(acc.shape[2:]))
+                out[:, ea:eb] = acc
+        return out
+
+    def _ingest(self, lrs, a, b, device, hwc, pad=None, size=None, window=None):
         """frames a .. b of the clip as frame-major fp32 ((b - a) n, 3, h, w) on the device; with `size` = (H, W): padded to it at
-        the bottom and right (`ops.ingest_pad`, mode `pad`) in the launch that converts them"""
+        the bottom and right (`ops.ingest_pad`, mode `pad`) in the launch that converts them; with `window` = (y0, y1, x0, x1): that
+        window of them, read in place by the launch that converts (and pads) it (`ops.ingest_window`)"""
         part = lrs[:, a:b]
+        if window is not None:
+            if part.dtype == torch.uint8 and not part.is_cuda:
+                part = part.to(device, non_blocking=True)      # whole frames cross the link as bytes (`forward_tiled` uploads once instead)
+            part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
+            y0, y1, x0, x1 = window
+            H, W = (y1 - y0, x1 - x0) if size is None else size
+            return ops.ingest_window(part, y0, x0, y1 - y0, x1 - x0, H, W, mode=pad or "reflect", hwc=hwc)
         if part.dtype != torch.uint8:
             part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
             return part if size is None else ops.ingest_pad(part, size[0], size[1], mode=pad, hwc=False)
@@ -643,6 +743,24 @@ class EAVSRP(nn.Module):
             store.put(module_name, idx, feat_prop)
             hist = (hist + [feat_prop])[-2:]
             store.done(i)
+
+
+class _TileBlend:
+    """`forward_tiled`'s sink: adds every SR chunk of one tile, as the view `forward_long` holds, to the accumulator"""
+    takes_views = True
+
+    def __init__(self, acc, first, Y0, X0, wy, wx):
+        self.acc, self.first, self.Y0, self.X0, self.wy, self.wx = acc, first, Y0, X0, wy, wx
+
+    def __call__(self, first_frame, sr):
+        a = first_frame - self.first      # the chunk's first frame among the emitted ones
+        b = a + int(sr.shape[1])
+        n = int(self.acc.shape[0])
+        if n == 1 or (a == 0 and b == int(self.acc.shape[1])):
+            ops.tile_blend(self.acc[:, a:b], sr, self.Y0, self.X0, self.wy, self.wx)
+        else:      # frames a .. b of several clips are not one contiguous block: clip by clip
+            for i in range(n):
+                ops.tile_blend(self.acc[i:i + 1, a:b], sr[i:i + 1], self.Y0, self.X0, self.wy, self.wx)
 
 
 class EAVSRPx2(EAVSRP):
@@ -715,6 +833,8 @@ def long_clip_options(opt=None):
     segment_options(opt)         # likewise: opt.max_frames / segment_overlap / scene_cuts, read by harness.super_resolve at every call
     from .segments import pad_option
     pad_option(opt)              # likewise: opt.pad_frames, read by EAVSRPModel.forward and harness.super_resolve
+    from .segments import tile_options
+    tile_options(opt)            # likewise: opt.tile / tile_overlap, read by EAVSRPModel.forward and harness.super_resolve
     return fc, cc
 
 
@@ -767,6 +887,11 @@ class EAVSRPModel:
         # opt.pad_frames (not among the reference's options): frames of any size outside training (EAVSRP.forward_long(pad=...))
         from .segments import pad_option
         self.pad_frames = pad_option(opt)
+        # opt.tile / opt.tile_overlap (not among the reference's options): frames of any resolution outside training (EAVSRP.forward_tiled)
+        from .segments import tile_options, DEFAULT_TILE_OVERLAP
+        self.tile, self.tile_overlap = tile_options(opt)
+        if self.tile_overlap is None:
+            self.tile_overlap = DEFAULT_TILE_OVERLAP
         # opt.train_precision (not among the reference's options): the opt-in bf16 training mode (networks.set_train_precision)
         if getattr(opt, "train_precision", None) is not None:
             N.set_train_precision(opt.train_precision)
@@ -861,7 +986,12 @@ class EAVSRPModel:
             return
         start = time.time()
         long_path = not self.isTrain and (self.frame_chunk is not None or self.cpu_cache)
-        if long_path or (not self.isTrain and self.pad_frames is not None):      # frames of any size go through forward_long too
+        if not self.isTrain and self.tile is not None:      # frames of any resolution: overlapped tiles, blended
+            with torch.no_grad():
+                self.data_sr_seq = self.netEAVSRP.forward_tiled(self.data_lr_seq, self.tile, overlap=self.tile_overlap,
+                                                                pad=self.pad_frames, frame_chunk=self.frame_chunk,
+                                                                cache="host" if self.cpu_cache else "device")
+        elif long_path or (not self.isTrain and self.pad_frames is not None):      # frames of any size go through forward_long too
             with torch.no_grad():
                 self.data_sr_seq = self.netEAVSRP.forward_long(self.data_lr_seq, frame_chunk=self.frame_chunk,
                                                                cache="host" if self.cpu_cache else "device", pad=self.pad_frames)

@@ -697,7 +697,8 @@ def scene_changes(frames, chunk: int = 64, device=None):
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
-                  cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None) -> Dict:
+                  cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
+                  tile_overlap: Optional[int] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -736,13 +737,28 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     Frames of any size, opt-in: `pad` = "reflect" / "edge" is `forward_long`'s -- frames whose sides are below 64 or no
     multiple of 4 are padded at the bottom and right while the device converts them and every SR chunk is cropped before the sink
     sees it, so `hr` is expected, and the files are written, at (s h, s w); the scene-cut statistics read the unpadded bytes.
-    None: `opt.pad_frames` of a model wrapper, else EAVSR_PAD_FRAMES=reflect|edge, else off -- such sizes are refused as before."""
+    None: `opt.pad_frames` of a model wrapper, else EAVSR_PAD_FRAMES=reflect|edge, else off -- such sizes are refused as before.
+
+    Frames of any resolution, opt-in: `tile` (LR pixels: an int, (rows, columns) or "288x512") runs the network on
+    overlapped spatial tiles that share `tile_overlap` LR pixels and blends their SR frames (`EAVSRP.forward_tiled`), so memory
+    follows the tile's area instead of the frame's; the same sink is fed, and it composes with `max_frames` / `cuts` / `pad`.  The
+    output is the blend of per-tile results, not the whole-frame result.  An argument left None: `opt.tile` / `opt.tile_overlap`
+    of a model wrapper, else EAVSR_TILE / EAVSR_TILE_OVERLAP (`segments.tile_options`), else no tiling / 32 pixels (a setting, not
+    a measured optimum).  The result carries 'tiles': the plan's (y0, y1, x0, x1) windows (one window, the frame: not tiled)."""
     from . import ops
-    from .segments import (check_pad, find_cuts, pad_option, plan_segments, segment_options, DEFAULT_HIST_THRESHOLD,
-                           DEFAULT_SAD_THRESHOLD)
+    from .segments import (check_pad, check_tile, find_cuts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
+                           tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP)
     if pad is None:
         pad = pad_option(getattr(model, "opt", None))
     check_pad(pad, "super_resolve: pad")
+    opt_tile, opt_tile_overlap = tile_options(getattr(model, "opt", None))
+    tile = parse_tile(tile, "super_resolve: tile") if isinstance(tile, str) else check_tile(tile, "super_resolve: tile")
+    if tile is None:
+        tile = opt_tile
+    if tile_overlap is None:
+        tile_overlap = DEFAULT_TILE_OVERLAP if opt_tile_overlap is None else opt_tile_overlap
+    if tile is not None:      # a bad tile / overlap is refused here, before a file is read or anything is allocated
+        plan_tiles(tile[0], tile[1], tile, tile_overlap)
     if png_encoder is None:      # a model wrapper has read its options already; the bare network has none
         png_encoder = getattr(model, "png_encoder", None)
     if png_encoder is None:
@@ -812,6 +828,9 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     segmented = max_frames is not None or cuts is not None
     if segmented:      # max_frames / overlap / min_scene / explicit starts are refused here, before anything is allocated or run
         plan_segments(t, [] if cuts == "device" else (cuts or []), max_frames, overlap, min_scene)
+    frame_h, frame_w = (int(v) for v in (lrs.shape[2:4] if (lrs.dtype == torch.uint8 and lrs.shape[4] == 3 and lrs.shape[2] != 3)
+                                         else lrs.shape[3:5]))
+    tiles = [(0, frame_h, 0, frame_w)] if tile is None else plan_tiles(frame_h, frame_w, tile, tile_overlap)
     written: List[str] = []
     sse_parts, ssim_parts, lpips_parts, counts = [], [], [], []
     staging = _PngStaging() if (out_dir is not None and png_encoder == "device") else None
@@ -862,7 +881,10 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     with torch.no_grad():
         if not segmented:
             starts, plan = [], [(0, t, 0, t)]
-            net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
+            if len(tiles) > 1:
+                net.forward_tiled(lrs, tile, overlap=tile_overlap, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            else:
+                net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
         else:
             if cuts == "device":
                 hwc = lrs.shape[4] == 3 and lrs.shape[2] != 3
@@ -872,13 +894,17 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
             else:
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
-            net.forward_segments_padded(lrs, plan, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            if len(tiles) > 1:
+                net.forward_tiled(lrs, tile, overlap=tile_overlap, segments=plan, pad=pad, frame_chunk=frame_chunk, cache=cache,
+                                  sink=sink)
+            else:
+                net.forward_segments_padded(lrs, plan, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
     write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
            "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
-           "segments": plan, "scene_starts": starts}
+           "segments": plan, "scene_starts": starts, "tiles": tiles}
     if hr is not None:
         sse = torch.cat(sse_parts, 1).reshape(-1).tolist()      # (n, t) order, as evaluate
         frame_ssim = torch.cat(ssim_parts, 1).reshape(-1).tolist()

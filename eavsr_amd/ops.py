@@ -1609,6 +1609,101 @@ def ingest_pad(frames: Tensor, H: int, W: int, mode: str = "reflect", hwc: Optio
     return out
 
 
+def ingest_window(frames: Tensor, y0: int, x0: int, wh: int, ww: int, H: Optional[int] = None, W: Optional[int] = None,
+                  mode: str = "reflect", hwc: Optional[bool] = None) -> Tensor:
+    """`ingest_pad` reading the window [y0, y0 + wh) x [x0, x0 + ww) of the frames (csrc/tile.hip) -> fp32 (F, C, H, W),
+    H >= wh and W >= ww (default: the window's size): out[f, c, y, x] = conv(src[f, c, y0 + ry(y), x0 + rx(x)]) with
+    `segments.pad_index` taken relative to the window (r(i) = pad_index(i, wh or ww, mode)).  `frames`, `mode`, `hwc` and conv are
+    `ingest_pad`'s: uint8 planes or interleaved at any base alignment, or fp32 planes copied bit for bit.  The window is read in
+    place, with the frames' own pitch: no copy of the slice is made.  F == 0: an empty tensor, nothing is launched.  The whole
+    frame as the window: `ingest_pad`'s result."""
+    from .segments import PAD_MODES
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"ingest_window: expected a tensor, got {type(frames)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"ingest_window: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4:
+        raise ValueError(f"ingest_window: a uint8 (F, C, h, w) / (F, h, w, 3) or fp32 (F, C, h, w) tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if mode not in PAD_MODES:
+        raise ValueError(f"ingest_window: mode {mode!r}: one of {PAD_MODES}")
+    u8 = frames.dtype == torch.uint8
+    if hwc is None:
+        hwc = u8 and frames.shape[3] == 3 and frames.shape[1] != 3
+    if hwc and (not u8 or frames.shape[3] != 3):
+        raise ValueError(f"ingest_window: an interleaved source is uint8 (F, h, w, 3), got {frames.dtype} {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    if hwc:
+        f, h, w, c = (int(v) for v in x.shape)
+    else:
+        f, c, h, w = (int(v) for v in x.shape)
+    H, W = (wh if H is None else H), (ww if W is None else W)
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (y0, x0, wh, ww, H, W)):
+        raise ValueError(f"ingest_window: y0, x0, wh, ww, H, W {(y0, x0, wh, ww, H, W)!r}: integers")
+    if f > 0 and (c < 1 or h < 1 or w < 1):
+        raise ValueError(f"ingest_window: empty frames {tuple(x.shape)}")
+    if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > max(h, 1) or x0 + ww > max(w, 1):
+        raise ValueError(f"ingest_window: the window [{y0}, {y0 + wh}) x [{x0}, {x0 + ww}) does not lie inside frames of {h} x {w}")
+    if H < wh or W < ww:
+        raise ValueError(f"ingest_window: the output {H} x {W} is smaller than the window {wh} x {ww} (padding only)")
+    if f > 65535 or c > 65535:
+        raise ValueError(f"ingest_window: F={f}, C={c}: at most 65535 each (grid dimensions)")
+    out = torch.empty((f, c, H, W), device=x.device, dtype=torch.float32)
+    if f == 0:
+        return out
+    if out.data_ptr() % 16:
+        raise ValueError("ingest_window: the output is not 16-byte aligned")
+    st = _stream(x)
+    kind = 1 if hwc else (0 if u8 else 2)
+    _launch("ingest_window", 0.0, float(f * c * wh * ww * x.element_size() + 4 * out.numel()), x,
+            lambda: lib().eavsr_ingest_window(_p(x), _p(out), f, c, h, w, y0, x0, wh, ww, H, W, kind, PAD_MODES.index(mode), st),
+            "ingest_window")
+    return out
+
+
+def tile_blend(acc: Tensor, sr: Tensor, Y0: int, X0: int, wy: Tensor, wx: Tensor) -> Tensor:
+    """acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * sr[n, f, c, y, x], in place, one launch (csrc/tile.hip): three
+    separately rounded fp32 operations in that order, never a fused multiply-add -- bit for bit what numpy computes.  `acc`: a
+    contiguous fp32 (n, F, C, SH, SW); `sr`: fp32 (n, F, C, th, tw) with any non-negative strides on n, f, c and rows and unit stride
+    along x (the transposed, cropped view `forward_long` holds is taken as it is, not copied); `wy` (th,), `wx` (tw,): contiguous fp32
+    rows of `segments.tile_weights` on the device.  Plain stores: tiles that overlap are blended one after another on one stream.
+    Returns `acc`."""
+    for name, t in (("acc", acc), ("sr", sr), ("wy", wy), ("wx", wx)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"tile_blend: {name}: expected a tensor, got {type(t)}")
+        if not t.is_cuda:
+            raise RuntimeError(f"tile_blend: {name} is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+        if t.dtype != torch.float32 or t.device != acc.device:
+            raise ValueError(f"tile_blend: {name}: fp32 on {acc.device}, got {t.dtype} on {t.device}")
+    if acc.dim() != 5 or sr.dim() != 5 or not acc.is_contiguous():
+        raise ValueError(f"tile_blend: acc is a contiguous (n, F, C, SH, SW) tensor and sr (n, F, C, th, tw), got {tuple(acc.shape)} "
+                         f"(contiguous: {acc.is_contiguous()}) and {tuple(sr.shape)}")
+    n, f, c, SH, SW = (int(v) for v in acc.shape)
+    th, tw = int(sr.shape[3]), int(sr.shape[4])
+    if tuple(sr.shape[:3]) != (n, f, c):
+        raise ValueError(f"tile_blend: sr holds {tuple(sr.shape[:3])} (n, F, C) planes, acc {(n, f, c)}")
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (Y0, X0)):
+        raise ValueError(f"tile_blend: Y0, X0 {Y0!r}, {X0!r}: integers")
+    if n * f > 0 and (c < 1 or th < 1 or tw < 1):
+        raise ValueError(f"tile_blend: an empty tile {tuple(sr.shape)}")
+    if Y0 < 0 or X0 < 0 or Y0 + th > SH or X0 + tw > SW:
+        raise ValueError(f"tile_blend: the tile [{Y0}, {Y0 + th}) x [{X0}, {X0 + tw}) does not lie inside frames of {SH} x {SW}")
+    if tuple(wy.shape) != (th,) or tuple(wx.shape) != (tw,) or not wy.is_contiguous() or not wx.is_contiguous():
+        raise ValueError(f"tile_blend: wy, wx are contiguous ({th},) and ({tw},) tensors, got {tuple(wy.shape)} and {tuple(wx.shape)}")
+    sn, sf, sc, sy, sx = (int(v) for v in sr.stride())
+    sn, sf, sc = (0 if d == 1 else v for d, v in zip((n, f, c), (sn, sf, sc)))      # the stride of a dimension of 1 is never used
+    if (tw > 1 and sx != 1) or min(sn, sf, sc, sy) < 0 or (th > 1 and sy < tw):
+        raise ValueError(f"tile_blend: sr has unit stride along x and non-negative strides elsewhere, got {tuple(sr.stride())}")
+    if n * f > 65535 or c > 65535:
+        raise ValueError(f"tile_blend: n F={n * f}, C={c}: at most 65535 each (grid dimensions)")
+    if n * f == 0:
+        return acc
+    st = _stream(acc)
+    _launch("tile_blend", 3.0 * sr.numel(), 12.0 * sr.numel(), acc,
+            lambda: lib().eavsr_tile_blend_f32(_p(acc), _p(sr), _p(wy), _p(wx), n, f, c, SH, SW, th, tw, Y0, X0, sn, sf, sc, max(sy, tw), st),
+            "tile_blend")
+    return acc
+
+
 def frame_change(frames: Tensor, hwc: Optional[bool] = None):
     """Scene-cut statistics of uint8 frames (F, C, h, w) planes, C 1 or 3, or (F, h, w, 3) interleaved (`hwc` as `u8_to_f32`), F >= 1,
     in one launch (csrc/scene.hip) -> (hist int32 (F, 64), sad int64 (F - 1,)) on the device.  With the luma

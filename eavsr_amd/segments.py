@@ -209,3 +209,113 @@ def pad_option(opt=None) -> Optional[str]:
     if pad is not None:
         return check_pad(pad, "opt.pad_frames")
     return check_pad(os.environ.get("EAVSR_PAD_FRAMES", "") or None, "EAVSR_PAD_FRAMES")
+
+
+# -- frames of any resolution: which spatial windows `EAVSRP.forward_tiled` runs, and how their SR tiles are blended -----
+DEFAULT_TILE_OVERLAP = 32            # LR pixels two neighbouring tiles share: a setting, not a measured optimum
+
+Tile = Tuple[int, int, int, int]
+
+
+def check_tile(tile, what: str = "tile") -> Optional[Tuple[int, int]]:
+    """None, or (th, tw) from an int (a square tile) or a pair: every side a multiple of 4 and at least 64 -- the model's own limit
+    for the frames it takes (`padded_size`); anything else is a ValueError that names `what`"""
+    if tile is None:
+        return None
+    sides = (tile, tile) if isinstance(tile, int) else tuple(tile) if isinstance(tile, (tuple, list)) else None
+    if sides is None or len(sides) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in sides):
+        raise ValueError(f"{what}={tile!r}: a number of LR pixels or (rows, columns), or None")
+    for v in sides:
+        if v < MIN_SIDE or v % SIDE_MULTIPLE:
+            raise ValueError(f"{what}={tile!r}: a tile side is a multiple of {SIDE_MULTIPLE} and at least {MIN_SIDE} (what the network takes)")
+    return sides
+
+
+def tile_axis(size: int, tile: int, overlap: int) -> List[Tuple[int, int]]:
+    """[a, b) windows of one axis of `size` samples, `plan_segments`' rule in space: an axis no longer than `tile` is one window, the
+    whole axis; a longer one gets windows of exactly `tile` samples that start at k (tile - overlap) while start + tile < size, and a
+    last window [size - tile, size) -- shifted back to full length, not left short"""
+    size, tile, overlap = int(size), int(tile), int(overlap)
+    if size < 1:
+        raise ValueError(f"plan_tiles: an axis of {size} samples")
+    if overlap < 0:
+        raise ValueError(f"plan_tiles: overlap {overlap!r}: not negative")
+    if overlap > tile // 2:
+        raise ValueError(f"plan_tiles: overlap {overlap} must be at most half the tile side {tile}")
+    if size <= tile:
+        return [(0, size)]
+    windows, a = [], 0
+    while a + tile < size:
+        windows.append((a, a + tile))
+        a += tile - overlap
+    windows.append((size - tile, size))
+    return windows
+
+
+def plan_tiles(h: int, w: int, tile, overlap: int = DEFAULT_TILE_OVERLAP) -> List[Tile]:
+    """(y0, y1, x0, x1) LR windows of frames of h x w in row-major order, `tile_axis` on either axis: all windows of a plan have the
+    same size -- min(tile, size) per axis -- so every tile takes the same kernel routes.  Refused with a ValueError before anything
+    runs: a tile side that is no multiple of 4 or below 64, overlap < 0, overlap > tile // 2 on either axis."""
+    sides = check_tile(tile, "plan_tiles: tile")
+    if sides is None:
+        raise ValueError("plan_tiles: tile=None")
+    if isinstance(overlap, bool) or not isinstance(overlap, int):
+        raise ValueError(f"plan_tiles: overlap {overlap!r}: a number of LR pixels")
+    for side in sides:      # both axes are checked, also where the frame is smaller than the tile
+        tile_axis(1, side, overlap)
+    rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
+    return [(y0, y1, x0, x1) for y0, y1 in rows for x0, x1 in cols]
+
+
+def tile_weights(size: int, windows_1d: Sequence[Tuple[int, int]], scale: int):
+    """float32 numpy (k, scale * tile_len): one row of SR-resolution blending weights per window [a, b) of one axis of `size` LR
+    samples (`tile_axis`; all of one length).  For SR sample X in [s a, s b) the raw weight is min(dl, dr) with
+    dl = X - s a + 0.5 if a > 0 else inf, dr = s b - X - 0.5 if b < size else inf -- the distance to the nearest window edge that is
+    not a frame edge -- and 1 where both are inf; the weight is the raw weight over the sum of the raw weights of all windows that
+    cover X: a partition of unity, a linear ramp across the overlap of two neighbours, exactly 1.0 where one window covers X.
+    Computed in float64 and rounded once."""
+    import numpy as np
+    size, s = int(size), int(scale)
+    windows = [(int(a), int(b)) for a, b in windows_1d]
+    if s < 1 or not windows or any(not 0 <= a < b <= size for a, b in windows) or len({b - a for a, b in windows}) != 1:
+        raise ValueError(f"tile_weights: windows {windows!r} of one length inside [0, {size}), scale {scale!r}")
+    total = np.zeros(s * size, np.float64)
+    raws = []
+    for a, b in windows:
+        X = np.arange(s * a, s * b, dtype=np.float64)
+        dl = X - s * a + 0.5 if a > 0 else np.full(X.shape, np.inf)
+        dr = s * b - X - 0.5 if b < size else np.full(X.shape, np.inf)
+        raw = np.minimum(dl, dr)
+        raw[np.isinf(raw)] = 1.0
+        total[s * a:s * b] += raw
+        raws.append(raw)
+    if not (total > 0).all():
+        raise ValueError(f"tile_weights: windows {windows!r} do not cover [0, {size})")
+    return np.stack([raw / total[s * a:s * b] for raw, (a, b) in zip(raws, windows)], 0).astype(np.float32)
+
+
+def parse_tile(text: str, what: str) -> Tuple[int, int]:
+    """"512" or "288x512" (rows x columns) -> (th, tw), checked as `check_tile`"""
+    parts = text.split("x")
+    if len(parts) not in (1, 2) or not all(p.isdigit() for p in parts):
+        raise ValueError(f"{what}={text!r}: LR pixels as '512' or '288x512' (rows x columns)")
+    sides = [int(p) for p in parts]
+    return check_tile(sides[0] if len(sides) == 1 else tuple(sides), what)
+
+
+def tile_options(opt=None):
+    """(tile, overlap) of the opt-in tiled path, each None where nothing sets it: `opt.tile` -- an int, (rows, columns) or
+    the text form "512" / "288x512" -- and `opt.tile_overlap` (LR pixels two tiles share; `harness.super_resolve` and the model
+    wrapper take DEFAULT_TILE_OVERLAP = 32 where it is None: a setting, not a measured optimum), each falling back to the environment
+    where the options do not carry it: EAVSR_TILE=512|288x512, EAVSR_TILE_OVERLAP=<integer >= 0>.  tile is returned as (th, tw).
+    Neither is among the reference's options."""
+    tile = getattr(opt, "tile", None)
+    if tile is None:
+        env = os.environ.get("EAVSR_TILE", "")
+        tile = parse_tile(env, "EAVSR_TILE") if env != "" else None
+    elif isinstance(tile, str):
+        tile = parse_tile(tile, "opt.tile")
+    else:
+        tile = check_tile(tile, "opt.tile")
+    ov = _count(opt, "tile_overlap", "EAVSR_TILE_OVERLAP", 0, "a number of LR pixels, 0 or more")
+    return tile, ov

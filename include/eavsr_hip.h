@@ -757,6 +757,26 @@ int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t
  * NULL pointer: -1; H < h, W < w, bad kind / mode / dims, F > 65535, C > 65535, a misaligned out: -2.  F == 0: 0, nothing is launched. */
 int eavsr_ingest_pad(const void* in, float* out, int32_t F, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, int32_t kind,
                      int32_t mode, void* stream);
+/* ---- spatial tiling: frames of any resolution (csrc/tile.hip; added to ABI 32, nothing above changes) -----------------------------------
+ * eavsr_ingest_window is eavsr_ingest_pad reading the window [y0, y0 + wh) x [x0, x0 + ww) of frames of h x w, addressed with the
+ * frames' own pitch (no copy of the slice):
+ *     out[f, c, y, x] = conv(in[f, c, y0 + r(y, wh), x0 + r(x, ww)]),   out fp32 (F, C, H, W), H >= wh, W >= ww
+ * kind, mode, conv, r and the alignment rules are eavsr_ingest_pad's, r taken relative to the window.  y0 = x0 = 0, wh = h, ww = w
+ * gives eavsr_ingest_pad's result.  NULL pointer: -1; a window that leaves the frame, H < wh, W < ww, bad kind / mode / dims,
+ * F > 65535, C > 65535, a misaligned out: -2.  F == 0: 0, nothing is launched.
+ *
+ * eavsr_tile_blend_f32 accumulates one weighted tile:
+ *     acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * sr[n, f, c, y, x],   0 <= y < th, 0 <= x < tw
+ * as three separately rounded fp32 operations in that order (never contracted into a fused multiply-add).  acc: contiguous fp32
+ * (N, F, C, SH, SW).  sr: fp32 with the element strides sn, sf, sc, sy (rows) >= 0 and unit stride along x.  wy: th weights, wx: tw.
+ * Every pointer 4-byte aligned; wider accesses are used where a row's address allows them.  Plain stores: calls that overlap in acc
+ * must be ordered on one stream.  NULL pointer: -1; a tile that leaves the frame, sy < tw, a negative stride, N F > 65535,
+ * C > 65535: -2.  N == 0 or F == 0: 0, nothing is launched. */
+int eavsr_ingest_window(const void* in, float* out, int32_t F, int32_t C, int32_t h, int32_t w, int32_t y0, int32_t x0, int32_t wh,
+                        int32_t ww, int32_t H, int32_t W, int32_t kind, int32_t mode, void* stream);
+int eavsr_tile_blend_f32(float* acc, const float* sr, const float* wy, const float* wx, int32_t N, int32_t F, int32_t C, int32_t SH,
+                         int32_t SW, int32_t th, int32_t tw, int32_t Y0, int32_t X0, int64_t sn, int64_t sf, int64_t sc, int64_t sy,
+                         void* stream);
 /* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
  * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
  * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
