@@ -195,10 +195,10 @@ SIGNATURES = {
     "eavsr_frame_metrics_f32": (C.c_int, [vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "eavsr_rgb8_f32": (C.c_int, [vp, f32, i32, i32, i32, i32, vp, vp]),
     "eavsr_u8_to_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
-    # padded ingest: frames of any size (csrc/ingest_pad.hip; addition to ABI 32)
+    # padded ingest of frames of any size, and of a window of them: one kernel family (csrc/ingest_pad.hip; additions to ABI 32)
     "eavsr_ingest_pad": (C.c_int, [vp, vp] + [i32] * 8 + [vp]),
-    # spatial tiling: window ingest and weighted accumulation of SR tiles (csrc/tile.hip; addition to ABI 32)
     "eavsr_ingest_window": (C.c_int, [vp, vp] + [i32] * 12 + [vp]),
+    # spatial tiling: weighted accumulation of SR tiles (csrc/tile.hip; addition to ABI 32)
     "eavsr_tile_blend_f32": (C.c_int, [vp] * 4 + [i32] * 9 + [i64] * 4 + [vp]),
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),

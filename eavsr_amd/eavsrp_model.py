@@ -64,6 +64,19 @@ def _frame_major(frames) -> Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
+def _clip_geometry(lrs, who: str):
+    """(u8, hwc, n, t, h, w) of a clip handed to the inference path `who`: (n, t, 3, h, w), or 8-bit frames interleaved as
+    (n, t, h, w, 3); anything else, and a call with gradients enabled, is refused under the caller's name"""
+    if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
+        raise ValueError(f"{who}: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{who} is inference only: call it under torch.no_grad() (training runs `forward`)")
+    u8 = lrs.dtype == torch.uint8
+    hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
+    h, w = (int(v) for v in (lrs.shape[2:4] if hwc else lrs.shape[3:]))
+    return u8, hwc, int(lrs.shape[0]), int(lrs.shape[1]), h, w
+
+
 class ResidualBlocksWithInputConv(nn.Module):
     """conv3x3(in -> out) + LeakyReLU(0.1) -> RCAGroup(nb=num_blocks).  `feat` may be a tensor or a
     list of tensors standing for their channel concatenation (the cat at eavsrp_model.py:322,353 is
@@ -451,14 +464,7 @@ class EAVSRP(nn.Module):
         from .segments import check_pad, padded_size
         FS.check_cache(cache)
         check_pad(pad, "forward_long: pad")
-        if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
-            raise ValueError("forward_long: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
-        if torch.is_grad_enabled():
-            raise RuntimeError("forward_long is inference only: call it under torch.no_grad() (training runs `forward`)")
-        u8 = lrs.dtype == torch.uint8
-        hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
-        n, t = int(lrs.shape[0]), int(lrs.shape[1])
-        c, h, w = (3, int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[2:])
+        u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_long")
         if window is not None:
             if len(window) != 4 or any(isinstance(v, bool) or not isinstance(v, int) for v in window):
                 raise ValueError(f"forward_long: window {window!r}: integers (y0, y1, x0, x1)")
@@ -466,13 +472,7 @@ class EAVSRP(nn.Module):
             if not (0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
                 raise ValueError(f"forward_long: window {window!r} does not lie inside frames of {h} x {w}")
             h, w = y1 - y0, x1 - x0
-        if not u8 and not lrs.is_cuda:
-            raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path); for a CPU reference use "
-                               "the original repository with --gpu_ids -1")
-        device = lrs.device if lrs.is_cuda else next(self.parameters()).device
-        if device.type != "cuda":
-            raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path): a uint8 clip in host memory needs the "
-                               "network on the GPU")
+        device = self._clip_device(lrs)
         size = None      # (H, W) of the padded frames, where `pad` is set and the size needs it
         if pad is not None and padded_size(h, w) != (h, w):
             size = padded_size(h, w)
@@ -569,22 +569,31 @@ class EAVSRP(nn.Module):
         own: `forward_segments` keeps the parameter list it was published with."""
         from .segments import check_pad, check_plan
         check_pad(pad, "forward_segments_padded: pad")
-        if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
-            raise ValueError("forward_segments: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
+        _, _, _, t, _, _ = _clip_geometry(lrs, "forward_segments")
+
+        def segment(part, emit, part_sink, last):
+            return self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=part_sink, emit=emit, pad=pad)
+        return self._over_plan(lrs, check_plan(t, segments), sink, segment)
+
+    def _over_plan(self, lrs, plan, sink, segment):
+        """The loop of `forward_segments_padded` and `forward_tiled` over a checked segment plan: for every (start, stop, ea, eb)
+        `segment(lrs[:, start:stop], emit, part_sink, last)` produces frames ea .. eb - 1 of the clip, emit = (ea - start, eb - start)
+        counted inside the window as `forward_long` counts them.  With a sink, `part_sink` is the sink with its frame number moved
+        from the window's to the clip's, the segment feeds it and nothing is returned; without one the segment returns its
+        (n, eb - ea, ...) frames, which are the result where the plan is one segment and are assembled into (n, t, ...) otherwise.
+        `last`: no segment follows (what a segment hands a sink may then be a view of storage it would reuse)."""
         n, t = int(lrs.shape[0]), int(lrs.shape[1])
-        plan = check_plan(t, segments)
         out = None
-        for start, stop, ea, eb in plan:
+        for si, (start, stop, ea, eb) in enumerate(plan):
             part_sink = None if sink is None else (lambda first, sr, start=start: sink(start + first, sr))
-            sr = self.forward_long(lrs[:, start:stop], frame_chunk=frame_chunk, cache=cache, sink=part_sink,
-                                   emit=(ea - start, eb - start), pad=pad)
+            sr = segment(lrs[:, start:stop], (ea - start, eb - start), part_sink, si + 1 == len(plan))
             if sink is None:
                 if len(plan) == 1:
                     return sr
                 if out is None:
                     out = sr.new_empty((n, t) + tuple(sr.shape[2:]))
                 out[:, ea:eb] = sr
-                del sr
+            del sr
         return out
 
     def forward_tiled(self, lrs, tile, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device", sink=None):
@@ -608,14 +617,7 @@ class EAVSRP(nn.Module):
         from .segments import check_pad, check_plan, check_tile, plan_tiles, tile_axis, tile_weights
         FS.check_cache(cache)
         check_pad(pad, "forward_tiled: pad")
-        if not isinstance(lrs, torch.Tensor) or lrs.dim() != 5:
-            raise ValueError("forward_tiled: lrs is an (n, t, 3, h, w) tensor (uint8: also (n, t, h, w, 3))")
-        if torch.is_grad_enabled():
-            raise RuntimeError("forward_tiled is inference only: call it under torch.no_grad() (training runs `forward`)")
-        u8 = lrs.dtype == torch.uint8
-        hwc = u8 and lrs.shape[4] == 3 and lrs.shape[2] != 3
-        n, t = int(lrs.shape[0]), int(lrs.shape[1])
-        h, w = (int(lrs.shape[2]), int(lrs.shape[3])) if hwc else (int(v) for v in lrs.shape[3:])
+        u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_tiled")
         sides = check_tile(tile, "forward_tiled: tile")
         if sides is None:
             raise ValueError("forward_tiled: tile=None (the untiled call is `forward_long`)")
@@ -623,70 +625,76 @@ class EAVSRP(nn.Module):
         if frame_chunk is not None and int(frame_chunk) < 1:
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
-        if len(tiles) == 1:
-            if segments is None:
-                return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
-            return self.forward_segments_padded(lrs, plan, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
-        if not u8 and not lrs.is_cuda:
+        if len(tiles) == 1:      # the untiled call: `forward_video` decides between `forward_long` and the segment plan
+            return self.forward_video(lrs, segments=segments, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        device = self._clip_device(lrs)
+        s = self.scale
+        rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
+        wy = torch.from_numpy(tile_weights(h, rows, s)).to(device)      # (rows of tiles, s th): row i serves every tile of row i
+        wx = torch.from_numpy(tile_weights(w, cols, s)).to(device)
+        per_frame = 3 * s * h * s * w
+        store = torch.empty(n * max(eb - ea for _, _, ea, eb in plan) * per_frame, device=device, dtype=torch.float32)
+
+        def segment(part, emit, part_sink, last):
+            if not part.is_cuda:
+                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile reads it on the device
+            k = emit[1] - emit[0]
+            acc = store[:n * k * per_frame].view(n, k, 3, s * h, s * w)
+            acc.zero_()
+            for ti, (y0, y1, x0, x1) in enumerate(tiles):
+                blend = _TileBlend(acc, emit[0], s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)])
+                self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=(y0, y1, x0, x1))
+            if part_sink is not None:
+                fc = k if frame_chunk is None else min(int(frame_chunk), k)
+                for a in range(0, k, fc):
+                    chunk = acc[:, a:a + fc]
+                    part_sink(emit[0] + a, chunk.contiguous() if last else chunk.clone())
+            return acc
+        return self._over_plan(lrs, plan, sink, segment)
+
+    def forward_video(self, lrs, segments=None, tile=None, tile_overlap=32, pad=None, frame_chunk=None, cache="device", sink=None):
+        """The one dispatch between the inference paths (`harness.super_resolve`, `EAVSRPModel.forward`): `forward_tiled` where
+        `tile` (None: untiled) cuts the frames into more than one tile, else `forward_segments_padded` where there is a segment
+        plan (`segments`, as `forward_segments` takes it), else `forward_long`.  `pad`, `frame_chunk`, `cache` and `sink` are
+        handed on; so is the result."""
+        from .segments import check_tile, plan_tiles
+        sides = check_tile(tile, "forward_video: tile")
+        if sides is not None:
+            h, w = _clip_geometry(lrs, "forward_video")[4:]
+            if len(plan_tiles(h, w, sides, tile_overlap)) > 1:
+                return self.forward_tiled(lrs, tile, overlap=tile_overlap, segments=segments, pad=pad, frame_chunk=frame_chunk,
+                                          cache=cache, sink=sink)
+        if segments is not None:
+            return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
+
+    def _clip_device(self, lrs):
+        """the device a clip runs on: its own, or the network's for 8-bit frames in host memory; anything but a GPU is refused"""
+        if lrs.dtype != torch.uint8 and not lrs.is_cuda:
             raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path); for a CPU reference use "
                                "the original repository with --gpu_ids -1")
         device = lrs.device if lrs.is_cuda else next(self.parameters()).device
         if device.type != "cuda":
             raise RuntimeError("eavsr_amd.EAVSRP runs on the GPU only (no CPU path): a uint8 clip in host memory needs the "
                                "network on the GPU")
-        s = self.scale
-        rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
-        wy = torch.from_numpy(tile_weights(h, rows, s)).to(device)      # (rows of tiles, s th): row i serves every tile of row i
-        wx = torch.from_numpy(tile_weights(w, cols, s)).to(device)
-        longest = max(eb - ea for _, _, ea, eb in plan)
-        per_frame = 3 * s * h * s * w
-        store = torch.empty(n * longest * per_frame, device=device, dtype=torch.float32)
-        out = None
-        for si, (start, stop, ea, eb) in enumerate(plan):
-            part = lrs[:, start:stop]
-            if not part.is_cuda:
-                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile reads it on the device
-            k = eb - ea
-            acc = store[:n * k * per_frame].view(n, k, 3, s * h, s * w)
-            acc.zero_()
-            for ti, (y0, y1, x0, x1) in enumerate(tiles):
-                blend = _TileBlend(acc, ea - start, s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)])
-                self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=(ea - start, eb - start), pad=pad,
-                                  window=(y0, y1, x0, x1))
-            if sink is not None:
-                fc = k if frame_chunk is None else min(int(frame_chunk), k)
-                for a in range(0, k, fc):
-                    chunk = acc[:, a:a + fc]
-                    sink(ea + a, chunk.clone() if si + 1 < len(plan) else chunk.contiguous())
-            elif len(plan) == 1:
-                return acc
-            else:
-                if out is None:
-                    out = acc.new_empty((n, t) + tuple(acc.shape[2:]))
-                out[:, ea:eb] = acc
-        return out
+        return device
 
     def _ingest(self, lrs, a, b, device, hwc, pad=None, size=None, window=None):
         """frames a .. b of the clip as frame-major fp32 ((b - a) n, 3, h, w) on the device; with `size` = (H, W): padded to it at
         the bottom and right (`ops.ingest_pad`, mode `pad`) in the launch that converts them; with `window` = (y0, y1, x0, x1): that
         window of them, read in place by the launch that converts (and pads) it (`ops.ingest_window`)"""
         part = lrs[:, a:b]
+        u8 = part.dtype == torch.uint8
+        if u8 and not part.is_cuda:
+            part = part.to(device, non_blocking=True)      # bytes cross the link, whole and unpadded (`forward_tiled` uploads once instead)
+        part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
         if window is not None:
-            if part.dtype == torch.uint8 and not part.is_cuda:
-                part = part.to(device, non_blocking=True)      # whole frames cross the link as bytes (`forward_tiled` uploads once instead)
-            part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
             y0, y1, x0, x1 = window
             H, W = (y1 - y0, x1 - x0) if size is None else size
             return ops.ingest_window(part, y0, x0, y1 - y0, x1 - x0, H, W, mode=pad or "reflect", hwc=hwc)
-        if part.dtype != torch.uint8:
-            part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
-            return part if size is None else ops.ingest_pad(part, size[0], size[1], mode=pad, hwc=False)
-        if not part.is_cuda:
-            part = part.to(device, non_blocking=True)      # bytes cross the link (unpadded)
-        part = part.transpose(0, 1).reshape((b - a) * part.shape[0], *part.shape[2:])
         if size is not None:
             return ops.ingest_pad(part, size[0], size[1], mode=pad, hwc=hwc)
-        return ops.u8_to_f32(part, hwc=hwc)
+        return ops.u8_to_f32(part, hwc=hwc) if u8 else part
 
     def _propagate_long(self, store, module_name, others, n, t, hoist=False):
         """`propagate` (eavsrp_model.py:242-329) on a frame store, inference only: the same launches per time step; what a step
@@ -809,24 +817,16 @@ def long_clip_options(opt=None):
     """(frame_chunk, cpu_cache) of the opt-in long-clip path: `opt.frame_chunk` (frames per chunk of the batched stages; None / 0 =
     off) and `opt.cpu_cache` (per-frame tensors in pinned host memory), each falling back to the environment where the options do
     not carry it -- EAVSR_FRAME_CHUNK=<positive integer>, EAVSR_CPU_CACHE=0|1.  Neither is among the reference's options."""
-    fc = getattr(opt, "frame_chunk", None)
-    if fc is None:
-        env = os.environ.get("EAVSR_FRAME_CHUNK", "")
-        if env != "":
-            if not env.isdigit() or int(env) < 1:
-                raise ValueError(f"EAVSR_FRAME_CHUNK={env!r}: a positive number of frames")
-            fc = int(env)
-    elif isinstance(fc, bool) or not isinstance(fc, int) or fc < 0:
-        raise ValueError(f"opt.frame_chunk={fc!r}: a positive number of frames, or None")
-    fc = fc or None
-    cc = getattr(opt, "cpu_cache", None)
-    if cc is None:
-        env = os.environ.get("EAVSR_CPU_CACHE", "0")
-        if env not in ("0", "1"):
-            raise ValueError(f"EAVSR_CPU_CACHE={env!r}: 0 or 1")
-        cc = env == "1"
-    elif not isinstance(cc, bool):
-        raise ValueError(f"opt.cpu_cache={cc!r}: True or False")
+    from .segments import digits, one_of, read_option, whole_number
+
+    def flag(value, who):
+        if not isinstance(value, bool):
+            raise ValueError(f"{who}={value!r}: True or False")
+        return value
+    fc = read_option(opt, "frame_chunk", "EAVSR_FRAME_CHUNK", whole_number(0, "a positive number of frames, or None"),
+                     digits(1, "a positive number of frames")) or None
+    cc = read_option(opt, "cpu_cache", "EAVSR_CPU_CACHE", flag, lambda text, who: one_of(("0", "1"), "0 or 1")(text, who) == "1",
+                     default=False, empty_is_unset=False)      # (the one variable that, set, may not be empty)
     png_encoder_option(opt)      # validated with the others; read where frames are written (harness.super_resolve)
     png_decoder_option(opt)      # likewise; read where frames are read (harness.super_resolve, at every call)
     from .segments import segment_options
@@ -842,28 +842,18 @@ def png_encoder_option(opt=None) -> str:
     """"host" or "device": who encodes the PNG files `harness.super_resolve` writes -- `opt.png_encoder`, falling back to the
     environment where the options do not carry it (EAVSR_PNG_ENCODER=host|device), "host" where neither does.  Not among the
     reference's options."""
-    pe = getattr(opt, "png_encoder", None)
-    if pe is None:
-        pe = os.environ.get("EAVSR_PNG_ENCODER", "") or "host"
-        if pe not in ("host", "device"):
-            raise ValueError(f"EAVSR_PNG_ENCODER={pe!r}: host or device")
-    elif pe not in ("host", "device"):
-        raise ValueError(f"opt.png_encoder={pe!r}: 'host' or 'device'")
-    return pe
+    from .segments import one_of, read_option
+    return read_option(opt, "png_encoder", "EAVSR_PNG_ENCODER", one_of(("host", "device"), "'host' or 'device'"),
+                       one_of(("host", "device"), "host or device"), default="host")
 
 
 def png_decoder_option(opt=None) -> str:
     """"host" or "device": who undoes the scanline filters of the PNG files `harness.super_resolve` reads -- `opt.png_decoder`,
     falling back to the environment where the options do not carry it (EAVSR_PNG_DECODER=host|device), "host" where neither does.
     Not among the reference's options."""
-    pd = getattr(opt, "png_decoder", None)
-    if pd is None:
-        pd = os.environ.get("EAVSR_PNG_DECODER", "") or "host"
-        if pd not in ("host", "device"):
-            raise ValueError(f"EAVSR_PNG_DECODER={pd!r}: host or device")
-    elif pd not in ("host", "device"):
-        raise ValueError(f"opt.png_decoder={pd!r}: 'host' or 'device'")
-    return pd
+    from .segments import one_of, read_option
+    return read_option(opt, "png_decoder", "EAVSR_PNG_DECODER", one_of(("host", "device"), "'host' or 'device'"),
+                       one_of(("host", "device"), "host or device"), default="host")
 
 
 class EAVSRPModel:
@@ -986,15 +976,15 @@ class EAVSRPModel:
             return
         start = time.time()
         long_path = not self.isTrain and (self.frame_chunk is not None or self.cpu_cache)
-        if not self.isTrain and self.tile is not None:      # frames of any resolution: overlapped tiles, blended
+        cache = "host" if self.cpu_cache else "device"
+        if not self.isTrain and (self.tile is not None or self.pad_frames is not None):
+            # frames of any resolution (overlapped tiles, blended: DESIGN 7j) or of any size
             with torch.no_grad():
-                self.data_sr_seq = self.netEAVSRP.forward_tiled(self.data_lr_seq, self.tile, overlap=self.tile_overlap,
-                                                                pad=self.pad_frames, frame_chunk=self.frame_chunk,
-                                                                cache="host" if self.cpu_cache else "device")
-        elif long_path or (not self.isTrain and self.pad_frames is not None):      # frames of any size go through forward_long too
+                self.data_sr_seq = self.netEAVSRP.forward_video(self.data_lr_seq, tile=self.tile, tile_overlap=self.tile_overlap,
+                                                                pad=self.pad_frames, frame_chunk=self.frame_chunk, cache=cache)
+        elif long_path:
             with torch.no_grad():
-                self.data_sr_seq = self.netEAVSRP.forward_long(self.data_lr_seq, frame_chunk=self.frame_chunk,
-                                                               cache="host" if self.cpu_cache else "device", pad=self.pad_frames)
+                self.data_sr_seq = self.netEAVSRP.forward_long(self.data_lr_seq, frame_chunk=self.frame_chunk, cache=cache)
         else:
             self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
         self.data_sr = self.data_sr_seq[:, self.idx]

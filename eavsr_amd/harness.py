@@ -881,10 +881,6 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     with torch.no_grad():
         if not segmented:
             starts, plan = [], [(0, t, 0, t)]
-            if len(tiles) > 1:
-                net.forward_tiled(lrs, tile, overlap=tile_overlap, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
-            else:
-                net.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
         else:
             if cuts == "device":
                 hwc = lrs.shape[4] == 3 and lrs.shape[2] != 3
@@ -894,11 +890,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
             else:
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
-            if len(tiles) > 1:
-                net.forward_tiled(lrs, tile, overlap=tile_overlap, segments=plan, pad=pad, frame_chunk=frame_chunk, cache=cache,
-                                  sink=sink)
-            else:
-                net.forward_segments_padded(lrs, plan, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
+                          frame_chunk=frame_chunk, cache=cache, sink=sink)
     write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0

@@ -1564,100 +1564,83 @@ def u8_to_f32(frames: Tensor, hwc: Optional[bool] = None) -> Tensor:
     return out
 
 
+def _ingest_frames(who: str, frames: Tensor, window, H, W, mode: str, hwc: Optional[bool]) -> Tensor:
+    """The body of `ingest_pad` (window None: the whole frame) and `ingest_window` (window = (y0, x0, wh, ww)): the checks under the
+    caller's name, the allocation and the one launch of csrc/ingest_pad.hip's kernels."""
+    from .segments import PAD_MODES
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"{who}: expected a tensor, got {type(frames)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"{who}: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4:
+        raise ValueError(f"{who}: a uint8 (F, C, h, w) / (F, h, w, 3) or fp32 (F, C, h, w) tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if mode not in PAD_MODES:
+        raise ValueError(f"{who}: mode {mode!r}: one of {PAD_MODES}")
+    u8 = frames.dtype == torch.uint8
+    if hwc is None:
+        hwc = u8 and frames.shape[3] == 3 and frames.shape[1] != 3
+    if hwc and (not u8 or frames.shape[3] != 3):
+        raise ValueError(f"{who}: an interleaved source is uint8 (F, h, w, 3), got {frames.dtype} {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    if hwc:
+        f, h, w, c = (int(v) for v in x.shape)
+    else:
+        f, c, h, w = (int(v) for v in x.shape)
+    if window is None:
+        given, named = (H, W), f"H, W {H!r}, {W!r}"
+    else:
+        H, W = (window[2] if H is None else H), (window[3] if W is None else W)
+        given = (*window, H, W)
+        named = f"y0, x0, wh, ww, H, W {given!r}"
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in given):
+        raise ValueError(f"{who}: {named}: integers")
+    if f > 0 and (c < 1 or h < 1 or w < 1):
+        raise ValueError(f"{who}: empty frames {tuple(x.shape)}")
+    if window is None:
+        y0, x0, wh, ww = 0, 0, h, w
+        if H < h or W < w:
+            raise ValueError(f"{who}: the output {H} x {W} is smaller than the frames {h} x {w} (padding only)")
+    else:
+        y0, x0, wh, ww = window
+        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > max(h, 1) or x0 + ww > max(w, 1):
+            raise ValueError(f"{who}: the window [{y0}, {y0 + wh}) x [{x0}, {x0 + ww}) does not lie inside frames of {h} x {w}")
+        if H < wh or W < ww:
+            raise ValueError(f"{who}: the output {H} x {W} is smaller than the window {wh} x {ww} (padding only)")
+    if f > 65535 or c > 65535:
+        raise ValueError(f"{who}: F={f}, C={c}: at most 65535 each (grid dimensions)")
+    out = torch.empty((f, c, H, W), device=x.device, dtype=torch.float32)
+    if f == 0:
+        return out
+    if out.data_ptr() % 16:
+        raise ValueError(f"{who}: the output is not 16-byte aligned")
+    st = _stream(x)
+    kind, m = 1 if hwc else (0 if u8 else 2), PAD_MODES.index(mode)
+    if window is None:
+        fn = lambda: lib().eavsr_ingest_pad(_p(x), _p(out), f, c, h, w, H, W, kind, m, st)
+    else:
+        fn = lambda: lib().eavsr_ingest_window(_p(x), _p(out), f, c, h, w, y0, x0, wh, ww, H, W, kind, m, st)
+    _launch(who, 0.0, float(f * c * wh * ww * x.element_size() + 4 * out.numel()), x, fn, who)
+    return out
+
+
 def ingest_pad(frames: Tensor, H: int, W: int, mode: str = "reflect", hwc: Optional[bool] = None) -> Tensor:
     """Frames of any size -> fp32 (F, C, H, W), H >= h and W >= w, padded at the bottom and right in one launch (csrc/ingest_pad.hip,
     DESIGN 7i): out[f, c, y, x] = src[f, c, ry(y), rx(x)] with `segments.pad_index` -- mode "reflect" is np.pad(mode="reflect") for
     every pad width, "edge" repeats the last row / column.  `frames`: uint8 (F, C, h, w) planes or (F, h, w, 3) interleaved (`hwc` as
     `u8_to_f32`), every sample float(v) / 255.0f as `u8_to_f32` gives it, at any base alignment; or fp32 (F, C, h, w), copied bit
     for bit.  F == 0: an empty tensor, nothing is launched.  H == h and W == w: `u8_to_f32`'s result (a copy for fp32)."""
-    from .segments import PAD_MODES
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError(f"ingest_pad: expected a tensor, got {type(frames)}")
-    if not frames.is_cuda:
-        raise RuntimeError(f"ingest_pad: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
-    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4:
-        raise ValueError(f"ingest_pad: a uint8 (F, C, h, w) / (F, h, w, 3) or fp32 (F, C, h, w) tensor, got {frames.dtype} {tuple(frames.shape)}")
-    if mode not in PAD_MODES:
-        raise ValueError(f"ingest_pad: mode {mode!r}: one of {PAD_MODES}")
-    u8 = frames.dtype == torch.uint8
-    if hwc is None:
-        hwc = u8 and frames.shape[3] == 3 and frames.shape[1] != 3
-    if hwc and (not u8 or frames.shape[3] != 3):
-        raise ValueError(f"ingest_pad: an interleaved source is uint8 (F, h, w, 3), got {frames.dtype} {tuple(frames.shape)}")
-    x = frames if frames.is_contiguous() else frames.contiguous()
-    if hwc:
-        f, h, w, c = (int(v) for v in x.shape)
-    else:
-        f, c, h, w = (int(v) for v in x.shape)
-    if any(isinstance(v, bool) or not isinstance(v, int) for v in (H, W)):
-        raise ValueError(f"ingest_pad: H, W {H!r}, {W!r}: integers")
-    if f > 0 and (c < 1 or h < 1 or w < 1):
-        raise ValueError(f"ingest_pad: empty frames {tuple(x.shape)}")
-    if H < h or W < w:
-        raise ValueError(f"ingest_pad: the output {H} x {W} is smaller than the frames {h} x {w} (padding only)")
-    if f > 65535 or c > 65535:
-        raise ValueError(f"ingest_pad: F={f}, C={c}: at most 65535 each (grid dimensions)")
-    out = torch.empty((f, c, H, W), device=x.device, dtype=torch.float32)
-    if f == 0:
-        return out
-    if out.data_ptr() % 16:
-        raise ValueError("ingest_pad: the output is not 16-byte aligned")
-    st = _stream(x)
-    kind = 1 if hwc else (0 if u8 else 2)
-    _launch("ingest_pad", 0.0, float(x.numel() * x.element_size() + 4 * out.numel()), x,
-            lambda: lib().eavsr_ingest_pad(_p(x), _p(out), f, c, h, w, H, W, kind, PAD_MODES.index(mode), st), "ingest_pad")
-    return out
+    return _ingest_frames("ingest_pad", frames, None, H, W, mode, hwc)
 
 
 def ingest_window(frames: Tensor, y0: int, x0: int, wh: int, ww: int, H: Optional[int] = None, W: Optional[int] = None,
                   mode: str = "reflect", hwc: Optional[bool] = None) -> Tensor:
-    """`ingest_pad` reading the window [y0, y0 + wh) x [x0, x0 + ww) of the frames (csrc/tile.hip) -> fp32 (F, C, H, W),
-    H >= wh and W >= ww (default: the window's size): out[f, c, y, x] = conv(src[f, c, y0 + ry(y), x0 + rx(x)]) with
-    `segments.pad_index` taken relative to the window (r(i) = pad_index(i, wh or ww, mode)).  `frames`, `mode`, `hwc` and conv are
+    """`ingest_pad` reading the window [y0, y0 + wh) x [x0, x0 + ww) of the frames (the same kernels, csrc/ingest_pad.hip)
+    -> fp32 (F, C, H, W), H >= wh and W >= ww (default: the window's size): out[f, c, y, x] = conv(src[f, c, y0 + ry(y), x0 + rx(x)])
+    with `segments.pad_index` taken relative to the window (r(i) = pad_index(i, wh or ww, mode)).  `frames`, `mode`, `hwc` and conv are
     `ingest_pad`'s: uint8 planes or interleaved at any base alignment, or fp32 planes copied bit for bit.  The window is read in
     place, with the frames' own pitch: no copy of the slice is made.  F == 0: an empty tensor, nothing is launched.  The whole
     frame as the window: `ingest_pad`'s result."""
-    from .segments import PAD_MODES
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError(f"ingest_window: expected a tensor, got {type(frames)}")
-    if not frames.is_cuda:
-        raise RuntimeError(f"ingest_window: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
-    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4:
-        raise ValueError(f"ingest_window: a uint8 (F, C, h, w) / (F, h, w, 3) or fp32 (F, C, h, w) tensor, got {frames.dtype} {tuple(frames.shape)}")
-    if mode not in PAD_MODES:
-        raise ValueError(f"ingest_window: mode {mode!r}: one of {PAD_MODES}")
-    u8 = frames.dtype == torch.uint8
-    if hwc is None:
-        hwc = u8 and frames.shape[3] == 3 and frames.shape[1] != 3
-    if hwc and (not u8 or frames.shape[3] != 3):
-        raise ValueError(f"ingest_window: an interleaved source is uint8 (F, h, w, 3), got {frames.dtype} {tuple(frames.shape)}")
-    x = frames if frames.is_contiguous() else frames.contiguous()
-    if hwc:
-        f, h, w, c = (int(v) for v in x.shape)
-    else:
-        f, c, h, w = (int(v) for v in x.shape)
-    H, W = (wh if H is None else H), (ww if W is None else W)
-    if any(isinstance(v, bool) or not isinstance(v, int) for v in (y0, x0, wh, ww, H, W)):
-        raise ValueError(f"ingest_window: y0, x0, wh, ww, H, W {(y0, x0, wh, ww, H, W)!r}: integers")
-    if f > 0 and (c < 1 or h < 1 or w < 1):
-        raise ValueError(f"ingest_window: empty frames {tuple(x.shape)}")
-    if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > max(h, 1) or x0 + ww > max(w, 1):
-        raise ValueError(f"ingest_window: the window [{y0}, {y0 + wh}) x [{x0}, {x0 + ww}) does not lie inside frames of {h} x {w}")
-    if H < wh or W < ww:
-        raise ValueError(f"ingest_window: the output {H} x {W} is smaller than the window {wh} x {ww} (padding only)")
-    if f > 65535 or c > 65535:
-        raise ValueError(f"ingest_window: F={f}, C={c}: at most 65535 each (grid dimensions)")
-    out = torch.empty((f, c, H, W), device=x.device, dtype=torch.float32)
-    if f == 0:
-        return out
-    if out.data_ptr() % 16:
-        raise ValueError("ingest_window: the output is not 16-byte aligned")
-    st = _stream(x)
-    kind = 1 if hwc else (0 if u8 else 2)
-    _launch("ingest_window", 0.0, float(f * c * wh * ww * x.element_size() + 4 * out.numel()), x,
-            lambda: lib().eavsr_ingest_window(_p(x), _p(out), f, c, h, w, y0, x0, wh, ww, H, W, kind, PAD_MODES.index(mode), st),
-            "ingest_window")
-    return out
+    return _ingest_frames("ingest_window", frames, (y0, x0, wh, ww), H, W, mode, hwc)
 
 
 def tile_blend(acc: Tensor, sr: Tensor, Y0: int, X0: int, wy: Tensor, wx: Tensor) -> Tensor:

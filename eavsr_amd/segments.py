@@ -129,18 +129,49 @@ def check_plan(t: int, segments: Sequence[Segment]) -> List[Segment]:
     return plan
 
 
-def _count(opt, name: str, env_name: str, least: int, what: str) -> Optional[int]:
+def read_option(opt, name: str, env_name: str, from_opt, from_env, default=None, empty_is_unset: bool = True):
+    """One opt-in setting, as every reader of this package finds it: `opt.<name>` where the options carry it (anything but None),
+    else the environment variable `env_name` where it is set (and not empty, unless `empty_is_unset` is False), else `default`.
+    `from_opt(value, "opt.<name>")` / `from_env(text, env_name)` return the setting or raise the ValueError that refuses it, which
+    opens with `<who>=<value>: `; a bad environment is therefore not read where the options decide."""
     value = getattr(opt, name, None)
-    if value is None:
-        env = os.environ.get(env_name, "")
-        if env == "":
-            return None
-        if not env.isdigit() or int(env) < least:
-            raise ValueError(f"{env_name}={env!r}: {what}")
-        return int(env)
-    if isinstance(value, bool) or not isinstance(value, int) or value < least:
-        raise ValueError(f"opt.{name}={value!r}: {what}, or None")
-    return value
+    if value is not None:
+        return from_opt(value, f"opt.{name}")
+    env = os.environ.get(env_name)
+    if env is None or (env == "" and empty_is_unset):
+        return default
+    return from_env(env, env_name)
+
+
+def one_of(choices, what: str):
+    """a `read_option` check: the value itself where it is among `choices`, else `<who>=<value>: <what>`"""
+    def check(value, who):
+        if value not in choices:
+            raise ValueError(f"{who}={value!r}: {what}")
+        return value
+    return check
+
+
+def whole_number(least: int, what: str):
+    """a `read_option` check for `opt.<name>`: an int (no bool) >= least"""
+    def check(value, who):
+        if isinstance(value, bool) or not isinstance(value, int) or value < least:
+            raise ValueError(f"{who}={value!r}: {what}")
+        return value
+    return check
+
+
+def digits(least: int, what: str):
+    """a `read_option` check for an environment variable: decimal digits, as an int >= least"""
+    def check(text, who):
+        if not text.isdigit() or int(text) < least:
+            raise ValueError(f"{who}={text!r}: {what}")
+        return int(text)
+    return check
+
+
+def _count(opt, name: str, env_name: str, least: int, what: str) -> Optional[int]:
+    return read_option(opt, name, env_name, whole_number(least, what + ", or None"), digits(least, what))
 
 
 def segment_options(opt=None):
@@ -151,13 +182,7 @@ def segment_options(opt=None):
     EAVSR_SCENE_CUTS=device.  None is among the reference's options."""
     mf = _count(opt, "max_frames", "EAVSR_MAX_FRAMES", 1, "a positive number of frames")
     ov = _count(opt, "segment_overlap", "EAVSR_SEGMENT_OVERLAP", 0, "a number of frames, 0 or more")
-    sc = getattr(opt, "scene_cuts", None)
-    if sc is None:
-        sc = os.environ.get("EAVSR_SCENE_CUTS", "") or None
-        if sc not in (None, "device"):
-            raise ValueError(f"EAVSR_SCENE_CUTS={sc!r}: device (or unset)")
-    elif sc != "device":
-        raise ValueError(f"opt.scene_cuts={sc!r}: 'device' or None")
+    sc = read_option(opt, "scene_cuts", "EAVSR_SCENE_CUTS", one_of(("device",), "'device' or None"), one_of(("device",), "device (or unset)"))
     return mf, ov, sc
 
 
@@ -205,10 +230,7 @@ def pad_option(opt=None) -> Optional[str]:
     """`opt.pad_frames` ("reflect" / "edge": frames of any size are padded on the device and the output is cropped), falling back to
     the environment where the options do not carry it (EAVSR_PAD_FRAMES=reflect|edge), None -- off -- where neither does.  Not
     among the reference's options."""
-    pad = getattr(opt, "pad_frames", None)
-    if pad is not None:
-        return check_pad(pad, "opt.pad_frames")
-    return check_pad(os.environ.get("EAVSR_PAD_FRAMES", "") or None, "EAVSR_PAD_FRAMES")
+    return read_option(opt, "pad_frames", "EAVSR_PAD_FRAMES", check_pad, check_pad)
 
 
 # -- frames of any resolution (DESIGN 7j): which spatial windows `EAVSRP.forward_tiled` runs, and how their SR tiles are blended -----
@@ -309,13 +331,6 @@ def tile_options(opt=None):
     wrapper take DEFAULT_TILE_OVERLAP = 32 where it is None: a setting, not a measured optimum), each falling back to the environment
     where the options do not carry it: EAVSR_TILE=512|288x512, EAVSR_TILE_OVERLAP=<integer >= 0>.  tile is returned as (th, tw).
     Neither is among the reference's options."""
-    tile = getattr(opt, "tile", None)
-    if tile is None:
-        env = os.environ.get("EAVSR_TILE", "")
-        tile = parse_tile(env, "EAVSR_TILE") if env != "" else None
-    elif isinstance(tile, str):
-        tile = parse_tile(tile, "opt.tile")
-    else:
-        tile = check_tile(tile, "opt.tile")
+    tile = read_option(opt, "tile", "EAVSR_TILE", lambda v, who: parse_tile(v, who) if isinstance(v, str) else check_tile(v, who), parse_tile)
     ov = _count(opt, "tile_overlap", "EAVSR_TILE_OVERLAP", 0, "a number of LR pixels, 0 or more")
     return tile, ov

@@ -757,12 +757,12 @@ int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t
  * NULL pointer: -1; H < h, W < w, bad kind / mode / dims, F > 65535, C > 65535, a misaligned out: -2.  F == 0: 0, nothing is launched. */
 int eavsr_ingest_pad(const void* in, float* out, int32_t F, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, int32_t kind,
                      int32_t mode, void* stream);
-/* ---- spatial tiling: frames of any resolution (csrc/tile.hip; added to ABI 32, nothing above changes) -----------------------------------
- * eavsr_ingest_window is eavsr_ingest_pad reading the window [y0, y0 + wh) x [x0, x0 + ww) of frames of h x w, addressed with the
- * frames' own pitch (no copy of the slice):
+/* ---- spatial tiling: frames of any resolution (csrc/ingest_pad.hip, csrc/tile.hip; added to ABI 32, nothing above changes) ------------
+ * eavsr_ingest_window is eavsr_ingest_pad, the same kernels, reading the window [y0, y0 + wh) x [x0, x0 + ww) of frames of h x w,
+ * addressed with the frames' own pitch (no copy of the slice):
  *     out[f, c, y, x] = conv(in[f, c, y0 + r(y, wh), x0 + r(x, ww)]),   out fp32 (F, C, H, W), H >= wh, W >= ww
  * kind, mode, conv, r and the alignment rules are eavsr_ingest_pad's, r taken relative to the window.  y0 = x0 = 0, wh = h, ww = w
- * gives eavsr_ingest_pad's result.  NULL pointer: -1; a window that leaves the frame, H < wh, W < ww, bad kind / mode / dims,
+ * is eavsr_ingest_pad.  NULL pointer: -1; a window that leaves the frame, H < wh, W < ww, bad kind / mode / dims,
  * F > 65535, C > 65535, a misaligned out: -2.  F == 0: 0, nothing is launched.
  *
  * eavsr_tile_blend_f32 accumulates one weighted tile:

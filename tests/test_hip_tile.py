@@ -107,6 +107,37 @@ def test_a_window_that_spans_a_short_axis_is_padded_and_slicing_then_ingest_pad_
     assert np.array_equal(_bits(got).numpy(), R.window_oracle(x, 5, 2, 40, 64, 40, 64, "reflect", hwc=hwc).view(np.int32))
 
 
+# (h, w, H, W) of F = 2, C = 3 frames: the smallest shapes that reach every path of the one kernel family behind both ops
+_ONE_KERNEL_SHAPES = [
+    (5, 7, 8, 12),        # vector stores; the reflected quads straddle the last column
+    (5, 7, 7, 9),         # W % 4 != 0: one sample per lane
+    (3, 5, 16, 20),       # padding several times the size: the reflect period wraps
+    (4, 264, 4, 264),     # nothing to pad; more than one pass of 64 lanes x 4 samples
+    (1, 1, 4, 4),         # s == 1
+]
+
+
+@pytest.mark.parametrize("mode", ["reflect", "edge"])
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_ingest_pad_is_ingest_window_of_the_whole_frame_bit_for_bit(ops, cuda, layout, mode):
+    """`ops.ingest_pad(x, H, W)` and `ops.ingest_window(x, 0, 0, h, w, H, W)` give the same bits, and both are tests/pad_ref.py's
+    np.pad statement (so they cannot be wrong together): at an aligned base and at one sliced 1 byte (fp32: 1 sample, which takes
+    the 16-byte alignment away; an fp32 source is 4-byte aligned by contract) past it"""
+    from tests import pad_ref
+    hwc = layout == "u8_interleaved"
+    for h, w, Hh, Ww in _ONE_KERNEL_SHAPES:
+        x = _source(layout, 2, 3, h, w, seed=h * 1000 + w)
+        want = pad_ref.pad_oracle(x, Hh, Ww, mode, hwc=hwc).view(np.int32)
+        for off in (0, 1):
+            src = _at_offset(x, off, cuda)
+            assert src.data_ptr() % 2 == off or src.dtype == torch.float32
+            padded = ops.ingest_pad(src, Hh, Ww, mode=mode, hwc=hwc)
+            windowed = ops.ingest_window(src, 0, 0, h, w, Hh, Ww, mode=mode, hwc=hwc)
+            assert tuple(padded.shape) == tuple(windowed.shape) == (2, 3, Hh, Ww)
+            assert torch.equal(_bits(padded), _bits(windowed)), (layout, mode, h, w, Hh, Ww, off)
+            assert np.array_equal(_bits(padded).numpy(), want), (layout, mode, h, w, Hh, Ww, off)
+
+
 def test_ingest_window_refusals_launch_nothing(ops, cuda):
     from eavsr_amd import _native as N
     u8 = torch.zeros(2, 3, 20, 30, dtype=torch.uint8, device=cuda)

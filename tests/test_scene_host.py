@@ -200,3 +200,97 @@ def test_oracle_on_a_hand_computed_case():
     grey = np.array([[[[0, 3, 4, 255]]], [[[255, 3, 0, 255]]]], np.uint8)
     hist, sad = R.frame_change(grey)
     assert hist[0].tolist()[:2] == [2, 1] and hist[0, 63] == 1 and sad.tolist() == [259]
+
+
+# ------------------------------------------------------------------------------------------------------------- every option reader
+_ENV_NAMES = ("EAVSR_FRAME_CHUNK", "EAVSR_CPU_CACHE", "EAVSR_PNG_ENCODER", "EAVSR_PNG_DECODER", "EAVSR_MAX_FRAMES",
+              "EAVSR_SEGMENT_OVERLAP", "EAVSR_SCENE_CUTS", "EAVSR_PAD_FRAMES", "EAVSR_TILE", "EAVSR_TILE_OVERLAP")
+
+
+def _readers():
+    from eavsr_amd import eavsrp_model as M
+    return {"long": M.long_clip_options, "enc": M.png_encoder_option, "dec": M.png_decoder_option, "seg": S.segment_options,
+            "pad": S.pad_option, "tile": S.tile_options}
+
+
+# (reader, opt fields, environment, what it returns -- or the ValueError's text): written down from the readers as they stood before
+# they shared `segments.read_option`; opt.<name> where it is not None, else the variable where it is set and not empty, else the default
+_OPTION_TABLE = [
+    ("long", {}, {}, (None, False)),
+    ("long", {"frame_chunk": 3, "cpu_cache": True}, {"EAVSR_FRAME_CHUNK": "x", "EAVSR_CPU_CACHE": "x"}, (3, True)),
+    ("long", {"frame_chunk": 0, "cpu_cache": False}, {"EAVSR_FRAME_CHUNK": "5", "EAVSR_CPU_CACHE": "1"}, (None, False)),
+    ("long", {"frame_chunk": None, "cpu_cache": None}, {"EAVSR_FRAME_CHUNK": "5", "EAVSR_CPU_CACHE": "1"}, (5, True)),
+    ("long", {}, {"EAVSR_FRAME_CHUNK": "", "EAVSR_CPU_CACHE": "0"}, (None, False)),
+    ("long", {}, {"EAVSR_FRAME_CHUNK": "0"}, "EAVSR_FRAME_CHUNK='0': a positive number of frames"),
+    ("long", {}, {"EAVSR_FRAME_CHUNK": "-2"}, "EAVSR_FRAME_CHUNK='-2': a positive number of frames"),
+    ("long", {}, {"EAVSR_FRAME_CHUNK": "2.0"}, "EAVSR_FRAME_CHUNK='2.0': a positive number of frames"),
+    ("long", {"frame_chunk": -1}, {}, "opt.frame_chunk=-1: a positive number of frames, or None"),
+    ("long", {"frame_chunk": True}, {}, "opt.frame_chunk=True: a positive number of frames, or None"),
+    ("long", {"frame_chunk": "4"}, {}, "opt.frame_chunk='4': a positive number of frames, or None"),
+    ("long", {}, {"EAVSR_CPU_CACHE": "yes"}, "EAVSR_CPU_CACHE='yes': 0 or 1"),
+    ("long", {}, {"EAVSR_CPU_CACHE": ""}, "EAVSR_CPU_CACHE='': 0 or 1"),      # the one variable that may not be empty
+    ("long", {"cpu_cache": 1}, {}, "opt.cpu_cache=1: True or False"),
+    ("long", {"cpu_cache": "1"}, {}, "opt.cpu_cache='1': True or False"),
+    ("long", {}, {"EAVSR_PNG_ENCODER": "gpu"}, "EAVSR_PNG_ENCODER='gpu': host or device"),      # validated with the others
+    ("long", {"png_decoder": "gpu"}, {}, "opt.png_decoder='gpu': 'host' or 'device'"),
+    ("long", {}, {"EAVSR_MAX_FRAMES": "0"}, "EAVSR_MAX_FRAMES='0': a positive number of frames"),
+    ("enc", {}, {}, "host"),
+    ("enc", {}, {"EAVSR_PNG_ENCODER": ""}, "host"),
+    ("enc", {}, {"EAVSR_PNG_ENCODER": "device"}, "device"),
+    ("enc", {"png_encoder": "host"}, {"EAVSR_PNG_ENCODER": "device"}, "host"),
+    ("enc", {"png_encoder": "device"}, {"EAVSR_PNG_ENCODER": "gpu"}, "device"),
+    ("enc", {"png_encoder": None}, {"EAVSR_PNG_ENCODER": "gpu"}, "EAVSR_PNG_ENCODER='gpu': host or device"),
+    ("enc", {"png_encoder": "Device"}, {}, "opt.png_encoder='Device': 'host' or 'device'"),
+    ("enc", {"png_encoder": True}, {}, "opt.png_encoder=True: 'host' or 'device'"),
+    ("dec", {}, {}, "host"),
+    ("dec", {}, {"EAVSR_PNG_DECODER": "device", "EAVSR_PNG_ENCODER": "gpu"}, "device"),
+    ("dec", {"png_decoder": "host"}, {"EAVSR_PNG_DECODER": "device"}, "host"),
+    ("dec", {}, {"EAVSR_PNG_DECODER": "0"}, "EAVSR_PNG_DECODER='0': host or device"),
+    ("dec", {"png_decoder": ""}, {}, "opt.png_decoder='': 'host' or 'device'"),
+    ("seg", {}, {}, (None, None, None)),
+    ("seg", {"max_frames": 40, "segment_overlap": 0, "scene_cuts": "device"}, {}, (40, 0, "device")),
+    ("seg", {}, {"EAVSR_MAX_FRAMES": "30", "EAVSR_SEGMENT_OVERLAP": "4", "EAVSR_SCENE_CUTS": "device"}, (30, 4, "device")),
+    ("seg", {"max_frames": 12}, {"EAVSR_MAX_FRAMES": "x", "EAVSR_SEGMENT_OVERLAP": "", "EAVSR_SCENE_CUTS": ""}, (12, None, None)),
+    ("seg", {"max_frames": 0}, {}, "opt.max_frames=0: a positive number of frames, or None"),
+    ("seg", {"max_frames": 2.0}, {}, "opt.max_frames=2.0: a positive number of frames, or None"),
+    ("seg", {"segment_overlap": -1}, {}, "opt.segment_overlap=-1: a number of frames, 0 or more, or None"),
+    ("seg", {"segment_overlap": False}, {}, "opt.segment_overlap=False: a number of frames, 0 or more, or None"),
+    ("seg", {}, {"EAVSR_SEGMENT_OVERLAP": "-1"}, "EAVSR_SEGMENT_OVERLAP='-1': a number of frames, 0 or more"),
+    ("seg", {}, {"EAVSR_SCENE_CUTS": "host"}, "EAVSR_SCENE_CUTS='host': device (or unset)"),
+    ("seg", {"scene_cuts": "host"}, {}, "opt.scene_cuts='host': 'device' or None"),
+    ("seg", {"scene_cuts": [3]}, {}, "opt.scene_cuts=[3]: 'device' or None"),
+    ("pad", {}, {}, None),
+    ("pad", {}, {"EAVSR_PAD_FRAMES": "edge"}, "edge"),
+    ("pad", {"pad_frames": "reflect"}, {"EAVSR_PAD_FRAMES": "wrap"}, "reflect"),
+    ("pad", {}, {"EAVSR_PAD_FRAMES": "wrap"}, "EAVSR_PAD_FRAMES='wrap': 'reflect', 'edge' or None"),
+    ("pad", {"pad_frames": ""}, {}, "opt.pad_frames='': 'reflect', 'edge' or None"),
+    ("pad", {"pad_frames": 1}, {}, "opt.pad_frames=1: 'reflect', 'edge' or None"),
+    ("tile", {}, {}, (None, None)),
+    ("tile", {"tile": 128, "tile_overlap": 0}, {"EAVSR_TILE": "x", "EAVSR_TILE_OVERLAP": "x"}, ((128, 128), 0)),
+    ("tile", {"tile": "288x512"}, {"EAVSR_TILE_OVERLAP": "8"}, ((288, 512), 8)),
+    ("tile", {"tile": [64, 128]}, {}, ((64, 128), None)),
+    ("tile", {}, {"EAVSR_TILE": "512", "EAVSR_TILE_OVERLAP": ""}, ((512, 512), None)),
+    ("tile", {}, {"EAVSR_TILE": "64x"}, "EAVSR_TILE='64x': LR pixels as '512' or '288x512' (rows x columns)"),
+    ("tile", {}, {"EAVSR_TILE": "66"}, "EAVSR_TILE=66: a tile side is a multiple of 4 and at least 64 (what the network takes)"),
+    ("tile", {"tile": "a"}, {}, "opt.tile='a': LR pixels as '512' or '288x512' (rows x columns)"),
+    ("tile", {"tile": 64.0}, {}, "opt.tile=64.0: a number of LR pixels or (rows, columns), or None"),
+    ("tile", {"tile": (64, 32)}, {}, "opt.tile=(64, 32): a tile side is a multiple of 4 and at least 64 (what the network takes)"),
+    ("tile", {"tile_overlap": "8"}, {}, "opt.tile_overlap='8': a number of LR pixels, 0 or more, or None"),
+    ("tile", {}, {"EAVSR_TILE_OVERLAP": "1.5"}, "EAVSR_TILE_OVERLAP='1.5': a number of LR pixels, 0 or more"),
+]
+
+
+def test_every_option_reader_returns_what_it_returned_before_they_shared_one_helper(monkeypatch):
+    readers = _readers()
+    for reader, fields, env, want in _OPTION_TABLE:
+        for name in _ENV_NAMES:
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        for opt in ([Namespace(**fields)] if fields else [None, Namespace()]):
+            if isinstance(want, str) and ("=" in want):
+                with pytest.raises(ValueError) as e:
+                    readers[reader](opt)
+                assert str(e.value) == want, (reader, fields, env)
+            else:
+                assert readers[reader](opt) == want, (reader, fields, env)

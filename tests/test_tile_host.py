@@ -1,6 +1,7 @@
 """Spatial tiling, what needs no GPU: the plan by brute force, the blending weights against their scalar restatement
 (tests/tile_ref.py) and as a partition of unity, transcriptions of both kernels' address arithmetic against numpy slicing, the C
 ABI's entry points, the options, and the argument checks that come before any device work."""
+import inspect
 import os
 import re
 from argparse import Namespace
@@ -273,3 +274,48 @@ def test_arguments_are_refused_before_anything_runs(monkeypatch):
         ops.ingest_window(np.zeros((1, 3, 20, 20), np.uint8), 0, 0, 8, 8)
     with pytest.raises(TypeError):
         ops.tile_blend(np.zeros((1, 1, 1, 8, 8), np.float32), torch.zeros(1, 1, 1, 4, 4), 0, 0, torch.ones(4), torch.ones(4))
+
+
+# ------------------------------------------------------------------------------------------------------------- the dispatch
+def test_forward_video_chooses_one_of_the_four_paths():
+    """`EAVSRP.forward_video` with the four methods replaced by recorders: no tile and no plan -> forward_long; a plan -> the segment
+    path; more than one tile -> the tiled path (the plan handed on); a tile that covers the frame -> as if no tile were given"""
+    from eavsr_amd.eavsrp_model import EAVSRP
+    net = EAVSRP.__new__(EAVSRP)
+    calls = []
+    for name in ("forward_long", "forward_segments", "forward_segments_padded", "forward_tiled"):
+        net.__dict__[name] = lambda *a, _n=name, **k: calls.append((_n, a, k)) or _n
+    x = torch.zeros(1, 4, 3, 96, 112)
+    u8_hwc = torch.zeros(1, 4, 96, 112, 3, dtype=torch.uint8)
+    plan = [(0, 3, 0, 2), (1, 4, 2, 4)]
+    common = dict(frame_chunk=2, cache="host", sink=None)
+    with torch.no_grad():
+        for lrs in (x, u8_hwc):
+            calls.clear()
+            assert net.forward_video(lrs, pad="edge", **common) == "forward_long"
+            assert calls == [("forward_long", (lrs,), dict(common, pad="edge"))]
+            calls.clear()
+            assert net.forward_video(lrs, segments=plan, pad="edge", **common) == "forward_segments_padded"
+            assert calls == [("forward_segments_padded", (lrs, plan, "edge"), common)]
+            calls.clear()      # one segment is still a plan: its frames go through the segment path
+            assert net.forward_video(lrs, segments=[(0, 4, 0, 4)], **common) == "forward_segments_padded"
+            assert calls == [("forward_segments_padded", (lrs, [(0, 4, 0, 4)], None), common)]
+            for tile, segments in ((64, None), ((64, 112), plan), ((96, 64), None)):      # 2 x 2, 2 x 1 and 1 x 2 tiles
+                calls.clear()
+                assert net.forward_video(lrs, segments=segments, tile=tile, tile_overlap=16, pad="reflect", **common) == "forward_tiled"
+                assert calls == [("forward_tiled", (lrs, tile), dict(common, overlap=16, segments=segments, pad="reflect"))]
+            for tile in (128, (96, 112)):      # one tile
+                calls.clear()
+                assert net.forward_video(lrs, segments=plan, tile=tile, **common) == "forward_segments_padded"
+                assert calls == [("forward_segments_padded", (lrs, plan, None), common)]
+                calls.clear()
+                assert net.forward_video(lrs, tile=tile, **common) == "forward_long"
+                assert calls == [("forward_long", (lrs,), dict(common, pad=None))]
+        calls.clear()
+        for tile, overlap in ((66, 0), (64, 33), ((64, 32), 0)):      # refused here, before any of the four is called
+            with pytest.raises(ValueError, match="tile|overlap"):
+                net.forward_video(x, tile=tile, tile_overlap=overlap)
+        assert calls == []
+    sig = inspect.signature(EAVSRP.forward_video)
+    assert [(k, p.default) for k, p in list(sig.parameters.items())[2:]] == [
+        ("segments", None), ("tile", None), ("tile_overlap", 32), ("pad", None), ("frame_chunk", None), ("cache", "device"), ("sink", None)]

@@ -141,7 +141,7 @@ class Memory:
 
 
 def ingest_window_transcription(x, y0, x0, wh, ww, H, W, mode, kind, base=0, grid_x=None):
-    """csrc/tile.hip's ingest kernels on frames x (layout `kind`) at byte address `base` -> (out float32 (F, C, H, W), wide loads,
+    """csrc/ingest_pad.hip's kernels, given a window, on frames x (layout `kind`) at byte address `base` -> (out float32 (F, C, H, W), wide loads,
     narrow loads); the output is taken as 16-byte aligned, which the entry point requires"""
     x = np.ascontiguousarray(x)
     edge = mode == "edge"
