@@ -200,6 +200,9 @@ SIGNATURES = {
     "eavsr_ingest_window": (C.c_int, [vp, vp] + [i32] * 12 + [vp]),
     # spatial tiling: weighted accumulation of SR tiles (csrc/tile.hip; addition to ABI 32)
     "eavsr_tile_blend_f32": (C.c_int, [vp] * 4 + [i32] * 9 + [i64] * 4 + [vp]),
+    # self-ensemble inference: flips / transposes of LR frames, their inverses into the accumulator (csrc/ensemble.hip; additions to ABI 32)
+    "eavsr_dihedral_f32": (C.c_int, [vp, vp] + [i32] * 5 + [vp]),
+    "eavsr_blend_dihedral_f32": (C.c_int, [vp] * 4 + [i32] * 10 + [i64] * 4 + [vp]),
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
     # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)

@@ -422,7 +422,7 @@ class EAVSRP(nn.Module):
         return self.conv_last(hr, residual=skip)                                     # :359-360
 
     # -- long clips ------------------------------------------------------------------------
-    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None):
+    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None, transform=None):
         """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
 
         The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
@@ -460,8 +460,18 @@ class EAVSRP(nn.Module):
         the window's size from here on, and the ingest reads the window in place (`ops.ingest_window`, one launch per chunk, all three
         kinds of source, padding to `padded_size` with `pad` in the same launch where the window's size needs it).  Everything else,
         the crop included, is unchanged: the result is `forward_long(lrs[..., y0:y1, x0:x1].contiguous(), ...)`, bit for bit.
-        window=None: today's launches."""
-        from .segments import check_pad, padded_size
+        window=None: today's launches.
+
+        transform=k, 1 .. 7 (`forward_ensemble`): the network sees the clip under mode k of the eight flips / transposes
+        (bit 0 hflip, bit 1 vflip, bit 2 transpose, in that order).  Every ingested chunk -- window and padding as above, in their one
+        launch -- goes through `ops.dihedral(.., k)`, and at the tail the crop is `segments.valid_region`, where the transform has
+        moved the frame's samples to (a view, taken whether or not the size needed padding).  The sink, or the result, holds the
+        frames in the TRANSFORMED orientation: `forward_long(g_k(<the padded window>))[valid region]`, bit for bit.  transform=None
+        or 0: today's launches and today's crop."""
+        from .segments import check_pad, padded_size, valid_region
+        if transform is not None and (isinstance(transform, bool) or not isinstance(transform, int) or not 0 <= transform <= 7):
+            raise ValueError(f"forward_long: transform {transform!r}: a mode 0 .. 7, or None")
+        transform = transform or None
         FS.check_cache(cache)
         check_pad(pad, "forward_long: pad")
         u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_long")
@@ -495,6 +505,8 @@ class EAVSRP(nn.Module):
         last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
         for a, b in chunks:
             lr_c = self._ingest(lrs, a, b, device, hwc, pad, size, window)
+            if transform is not None:
+                lr_c = ops.dihedral(lr_c, transform)
             store.put_range("lr", a, lr_c)
             seq = lr_c if last is None else torch.cat([last, lr_c], 0)
             m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
@@ -540,7 +552,10 @@ class EAVSRP(nn.Module):
                 sr = self._upsample_tm(tensors[:-1], tensors[-1])
             del tensors
             sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
-            if size is not None:      # the crop: a view here, one copy of the chunk's output where it is made contiguous / stored below
+            if transform is not None:      # where mode k has moved the frame's samples to, inside its (transposed: s W x s H) SR frame
+                r0, r1, c0, c1 = valid_region(transform, h, w, *(size or (h, w)), self.scale)
+                sr = sr[..., r0:r1, c0:c1]
+            elif size is not None:      # the crop: a view here, one copy of the chunk's output where it is made contiguous / stored below
                 sr = sr[..., :self.scale * h, :self.scale * w]
             if sink is not None:      # (`forward_tiled`'s own sink blends the view as it stands: `ops.tile_blend` reads strides)
                 sink(a, sr if getattr(sink, "takes_views", False) else sr.contiguous())
@@ -668,6 +683,74 @@ class EAVSRP(nn.Module):
             return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
         return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
 
+    def forward_ensemble(self, lrs, ensemble=8, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device",
+                         sink=None):
+        """Geometric self-ensemble, inference only: the clip runs under each mode of `ensemble` -- the flips and
+        transposes of the frame, `segments.check_ensemble`: 2, 4 / "flips", 8 or an explicit sequence of modes -- and the results,
+        each turned back, are averaged.  A method of its own: `forward_video` keeps the parameter list it was published with;
+        `harness.super_resolve` and the model wrapper call this one where an ensemble is set.
+
+        `forward_tiled`'s loop with the mode loop inside the tile loop: per segment a host-resident 8-bit window of frames is
+        uploaded once; the fp32 accumulator (n, emitted frames, 3, s h, s w) is zeroed; for every tile in `plan_tiles` order (untiled:
+        the one window, the frame, with weights 1) and inside it for every mode k in increasing order,
+        `forward_long(window=..., emit=..., pad=pad, transform=k)` runs with a sink that adds inv_k of every SR chunk, as the view it
+        is, to the accumulator (`ops.blend_dihedral`): acc = acc + ((wy' wx) inv_k(sr)), three separately rounded fp32 operations,
+        wy' = fp32(wy / len(modes)) computed once on the host.  The accumulator then goes to `sink(first_frame, chunk)` in
+        `frame_chunk` pieces, or is returned assembled.  One accumulator serves all segments.
+
+        Contract: the result is that numpy blend of `forward_long` on each hand-cropped, hand-padded, hand-transformed clip, bit for
+        bit.  The network is NOT equivariant -- SPyNet, the DCN offsets and the residual blocks see the orientation -- so the modes
+        differ and this is their mean, not an equivariant network.  Nothing is claimed about quality: no trained weights exist
+        in this project, and the gain a published "+" row reports cannot be measured here.
+
+        A spec that is off, or the one mode 0, IS `forward_video(...)`: no accumulator, no blend."""
+        from .segments import (check_ensemble, check_pad, check_plan, check_tile, ensemble_weight, plan_tiles, tile_axis,
+                               tile_weights)
+        import numpy as np
+        modes = check_ensemble(ensemble, "forward_ensemble: ensemble")      # refused before anything runs
+        FS.check_cache(cache)
+        check_pad(pad, "forward_ensemble: pad")
+        u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_ensemble")
+        sides = check_tile(tile, "forward_ensemble: tile")
+        tiles = [(0, h, 0, w)] if sides is None else plan_tiles(h, w, sides, overlap)
+        if frame_chunk is not None and int(frame_chunk) < 1:
+            raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
+        plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
+        if modes is None or modes == (0,):
+            return self.forward_video(lrs, segments=segments, tile=tile, tile_overlap=overlap, pad=pad, frame_chunk=frame_chunk,
+                                      cache=cache, sink=sink)
+        device = self._clip_device(lrs)
+        s = self.scale
+        if len(tiles) == 1:      # the whole frame: `forward_long` without a window, every weight 1
+            cols, windows = [(0, w)], [None]
+            wy, wx = np.ones((1, s * h), np.float32), np.ones((1, s * w), np.float32)
+        else:
+            rows, cols, windows = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap), tiles
+            wy, wx = tile_weights(h, rows, s), tile_weights(w, cols, s)
+        wy = torch.from_numpy(wy * ensemble_weight(modes)).to(device)      # fp32 x fp32, rounded once: wy'
+        wx = torch.from_numpy(wx).to(device)
+        per_frame = 3 * s * h * s * w
+        store = torch.empty(n * max(eb - ea for _, _, ea, eb in plan) * per_frame, device=device, dtype=torch.float32)
+
+        def segment(part, emit, part_sink, last):
+            if not part.is_cuda:
+                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile and mode reads it on the device
+            k = emit[1] - emit[0]
+            acc = store[:n * k * per_frame].view(n, k, 3, s * h, s * w)
+            acc.zero_()
+            for ti, ((y0, _, x0, _), window) in enumerate(zip(tiles, windows)):
+                for mode in modes:
+                    blend = _EnsembleBlend(acc, emit[0], s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)], mode)
+                    self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=window,
+                                      transform=mode)
+            if part_sink is not None:
+                fc = k if frame_chunk is None else min(int(frame_chunk), k)
+                for a in range(0, k, fc):
+                    chunk = acc[:, a:a + fc]
+                    part_sink(emit[0] + a, chunk.contiguous() if last else chunk.clone())
+            return acc
+        return self._over_plan(lrs, plan, sink, segment)
+
     def _clip_device(self, lrs):
         """the device a clip runs on: its own, or the network's for 8-bit frames in host memory; anything but a GPU is refused"""
         if lrs.dtype != torch.uint8 and not lrs.is_cuda:
@@ -771,6 +854,24 @@ class _TileBlend:
                 ops.tile_blend(self.acc[i:i + 1, a:b], sr[i:i + 1], self.Y0, self.X0, self.wy, self.wx)
 
 
+class _EnsembleBlend(_TileBlend):
+    """`forward_ensemble`'s sink: `_TileBlend` for SR chunks that arrive under mode k -- inv_k on the load (`ops.blend_dihedral`)"""
+
+    def __init__(self, acc, first, Y0, X0, wy, wx, k):
+        super().__init__(acc, first, Y0, X0, wy, wx)
+        self.k = k
+
+    def __call__(self, first_frame, sr):
+        a = first_frame - self.first
+        b = a + int(sr.shape[1])
+        n = int(self.acc.shape[0])
+        if n == 1 or (a == 0 and b == int(self.acc.shape[1])):
+            ops.blend_dihedral(self.acc[:, a:b], sr, self.k, self.Y0, self.X0, self.wy, self.wx)
+        else:      # frames a .. b of several clips are not one contiguous block: clip by clip
+            for i in range(n):
+                ops.blend_dihedral(self.acc[i:i + 1, a:b], sr[i:i + 1], self.k, self.Y0, self.X0, self.wy, self.wx)
+
+
 class EAVSRPx2(EAVSRP):
     """eavsrpx2_model.py's network (class EAVSRP there): one pixel-shuffle stage, x2 bilinear skip."""
 
@@ -835,6 +936,8 @@ def long_clip_options(opt=None):
     pad_option(opt)              # likewise: opt.pad_frames, read by EAVSRPModel.forward and harness.super_resolve
     from .segments import tile_options
     tile_options(opt)            # likewise: opt.tile / tile_overlap, read by EAVSRPModel.forward and harness.super_resolve
+    from .segments import ensemble_options
+    ensemble_options(opt)        # likewise: opt.ensemble, read by EAVSRPModel.forward and harness.super_resolve
     return fc, cc
 
 
@@ -882,6 +985,11 @@ class EAVSRPModel:
         self.tile, self.tile_overlap = tile_options(opt)
         if self.tile_overlap is None:
             self.tile_overlap = DEFAULT_TILE_OVERLAP
+        # opt.ensemble (not among the reference's options): the self-ensemble outside training (EAVSRP.forward_ensemble); None: off
+        from .segments import ensemble_options
+        self.ensemble = ensemble_options(opt)
+        if self.ensemble == (0,):
+            self.ensemble = None
         # opt.train_precision (not among the reference's options): the opt-in bf16 training mode (networks.set_train_precision)
         if getattr(opt, "train_precision", None) is not None:
             N.set_train_precision(opt.train_precision)
@@ -977,7 +1085,13 @@ class EAVSRPModel:
         start = time.time()
         long_path = not self.isTrain and (self.frame_chunk is not None or self.cpu_cache)
         cache = "host" if self.cpu_cache else "device"
-        if not self.isTrain and (self.tile is not None or self.pad_frames is not None):
+        if not self.isTrain and self.ensemble is not None:
+            # the mean over flips / transposes of the frame, tiled and padded as below
+            with torch.no_grad():
+                self.data_sr_seq = self.netEAVSRP.forward_ensemble(self.data_lr_seq, ensemble=self.ensemble, tile=self.tile,
+                                                                   overlap=self.tile_overlap, pad=self.pad_frames,
+                                                                   frame_chunk=self.frame_chunk, cache=cache)
+        elif not self.isTrain and (self.tile is not None or self.pad_frames is not None):
             # frames of any resolution (overlapped tiles, blended: DESIGN 7j) or of any size
             with torch.no_grad():
                 self.data_sr_seq = self.netEAVSRP.forward_video(self.data_lr_seq, tile=self.tile, tile_overlap=self.tile_overlap,

@@ -698,7 +698,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
                   cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
-                  tile_overlap: Optional[int] = None) -> Dict:
+                  tile_overlap: Optional[int] = None, ensemble=None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -744,10 +744,25 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     follows the tile's area instead of the frame's; the same sink is fed, and it composes with `max_frames` / `cuts` / `pad`.  The
     output is the blend of per-tile results, not the whole-frame result.  An argument left None: `opt.tile` / `opt.tile_overlap`
     of a model wrapper, else EAVSR_TILE / EAVSR_TILE_OVERLAP (`segments.tile_options`), else no tiling / 32 pixels (a setting, not
-    a measured optimum).  The result carries 'tiles': the plan's (y0, y1, x0, x1) windows (one window, the frame: not tiled)."""
+    a measured optimum).  The result carries 'tiles': the plan's (y0, y1, x0, x1) windows (one window, the frame: not tiled).
+
+    Self-ensemble, opt-in: `ensemble` -- 2, 4 / "flips", 8, or a sequence of modes 0 .. 7 (bit 0 hflip, bit 1 vflip, bit 2
+    transpose; `segments.check_ensemble`) -- runs every window under each mode and feeds the sink their mean, turned back on the
+    device (`EAVSRP.forward_ensemble`); it composes with everything above, and the scene cuts read the untransformed bytes.  About
+    len(modes) times the work.  The network is not equivariant, so the modes differ; whether their mean is BETTER is not known
+    here (no trained weights exist in this project).  None: `opt.ensemble` of a model wrapper, else EAVSR_ENSEMBLE=8|4|2|flips|0,1,4
+    (`segments.ensemble_options`), else off.  The result carries 'ensemble': the tuple of modes that ran ((0,): off)."""
     from . import ops
     from .segments import (check_pad, check_tile, find_cuts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
-                           tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP)
+                           tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP,
+                           check_ensemble, ensemble_options, parse_ensemble)
+    if ensemble is None:      # a bad spec is refused here, before a file is read
+        modes = ensemble_options(getattr(model, "opt", None))
+    elif isinstance(ensemble, str):
+        modes = parse_ensemble(ensemble, "super_resolve: ensemble")
+    else:
+        modes = check_ensemble(ensemble, "super_resolve: ensemble")
+    modes = modes or (0,)
     if pad is None:
         pad = pad_option(getattr(model, "opt", None))
     check_pad(pad, "super_resolve: pad")
@@ -890,14 +905,18 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
             else:
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
-        net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
-                          frame_chunk=frame_chunk, cache=cache, sink=sink)
+        if modes == (0,):
+            net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
+                              frame_chunk=frame_chunk, cache=cache, sink=sink)
+        else:
+            net.forward_ensemble(lrs, ensemble=modes, tile=tile, overlap=tile_overlap, segments=plan if segmented else None, pad=pad,
+                                 frame_chunk=frame_chunk, cache=cache, sink=sink)
     write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
            "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
-           "segments": plan, "scene_starts": starts, "tiles": tiles}
+           "segments": plan, "scene_starts": starts, "tiles": tiles, "ensemble": modes}
     if hr is not None:
         sse = torch.cat(sse_parts, 1).reshape(-1).tolist()      # (n, t) order, as evaluate
         frame_ssim = torch.cat(ssim_parts, 1).reshape(-1).tolist()

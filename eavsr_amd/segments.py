@@ -334,3 +334,65 @@ def tile_options(opt=None):
     tile = read_option(opt, "tile", "EAVSR_TILE", lambda v, who: parse_tile(v, who) if isinstance(v, str) else check_tile(v, who), parse_tile)
     ov = _count(opt, "tile_overlap", "EAVSR_TILE_OVERLAP", 0, "a number of LR pixels, 0 or more")
     return tile, ov
+
+
+# -- self-ensemble inference: which of the eight flips / transposes `EAVSRP.forward_ensemble` averages ----------------------
+ENSEMBLE_MODES = 8                   # mode k: bit 0 hflip, bit 1 vflip, bit 2 transpose, in that order (the flags of `dataset.py`)
+ENSEMBLE_NAMED = {1: (0,), 2: (0, 1), 4: (0, 1, 2, 3), "flips": (0, 1, 2, 3), 8: tuple(range(8))}
+
+
+def check_ensemble(spec, what: str = "ensemble") -> Optional[Tuple[int, ...]]:
+    """The ensemble spec as a tuple of distinct modes in increasing order, or None (off): None and 1 are off; 2 is modes (0, 1); 4
+    and "flips" are (0, 1, 2, 3); 8 is all eight; a non-empty sequence of distinct modes 0 .. 7 is itself, sorted.  Anything else
+    is a ValueError that names `what`."""
+    if spec is None:
+        return None
+    if isinstance(spec, (int, str)) and not isinstance(spec, bool):
+        if spec in ENSEMBLE_NAMED:
+            return None if spec == 1 else ENSEMBLE_NAMED[spec]
+    elif isinstance(spec, (tuple, list)) and spec:
+        modes = tuple(spec)
+        if (all(isinstance(k, int) and not isinstance(k, bool) and 0 <= k < ENSEMBLE_MODES for k in modes)
+                and len(set(modes)) == len(modes)):
+            return tuple(sorted(modes))
+    raise ValueError(f"{what}={spec!r}: None, 1 (off), 2, 4, 'flips', 8, or distinct modes 0 .. 7 (bit 0 hflip, bit 1 vflip, "
+                     f"bit 2 transpose)")
+
+
+def parse_ensemble(text: str, what: str) -> Optional[Tuple[int, ...]]:
+    """"8", "4", "2", "1", "flips", or a list of modes as "0,1,4" -> `check_ensemble`'s tuple"""
+    if text == "flips":
+        return check_ensemble(text, what)
+    parts = text.split(",")
+    if not all(p.isdigit() for p in parts):
+        raise ValueError(f"{what}={text!r}: 1, 2, 4, 8, flips, or modes as '0,1,4'")
+    if len(parts) == 1:
+        value = int(parts[0])
+        return check_ensemble(value if value in ENSEMBLE_NAMED else (value,), what)
+    return check_ensemble(tuple(int(p) for p in parts), what)
+
+
+def ensemble_options(opt=None) -> Optional[Tuple[int, ...]]:
+    """The modes of the opt-in self-ensemble, None where nothing sets it or it is off: `opt.ensemble` -- anything
+    `check_ensemble` takes, or the text form -- falling back to the environment where the options do not carry it:
+    EAVSR_ENSEMBLE=8|4|2|1|flips|0,1,4.  Not among the reference's options."""
+    return read_option(opt, "ensemble", "EAVSR_ENSEMBLE",
+                       lambda v, who: parse_ensemble(v, who) if isinstance(v, str) else check_ensemble(v, who), parse_ensemble)
+
+
+def ensemble_weight(modes) -> "np.float32":
+    """np.float32(1) / np.float32(len(modes)): exact for 2, 4 and 8 modes"""
+    import numpy as np
+    return np.float32(1) / np.float32(len(modes))
+
+
+def valid_region(k: int, h: int, w: int, H: int, W: int, scale: int) -> Tuple[int, int, int, int]:
+    """(r0, r1, c0, c1): where the SR samples of the h x w frame lie inside the SR frame of mode k, when the frame was padded at the
+    bottom and right to H x W and THEN transformed -- g_k's image of [0, s h) x [0, s w).  A flip moves the padding to the top /
+    left; a transposed mode swaps the axes (its SR frame is s W x s H)."""
+    k, s = int(k), int(scale)
+    if not 0 <= k < ENSEMBLE_MODES or not (1 <= h <= H and 1 <= w <= W and s >= 1):
+        raise ValueError(f"valid_region: mode {k}, a {h} x {w} frame inside {H} x {W}, scale {s}")
+    ys = (s * (H - h), s * H) if k & 2 else (0, s * h)
+    xs = (s * (W - w), s * W) if k & 1 else (0, s * w)
+    return (*xs, *ys) if k & 4 else (*ys, *xs)

@@ -777,6 +777,26 @@ int eavsr_ingest_window(const void* in, float* out, int32_t F, int32_t C, int32_
 int eavsr_tile_blend_f32(float* acc, const float* sr, const float* wy, const float* wx, int32_t N, int32_t F, int32_t C, int32_t SH,
                          int32_t SW, int32_t th, int32_t tw, int32_t Y0, int32_t X0, int64_t sn, int64_t sf, int64_t sc, int64_t sy,
                          void* stream);
+/* ---- self-ensemble inference: flips and transposes in, their inverses out (csrc/ensemble.hip; added to ABI 32, nothing above changes) ----
+ * Mode k in 0 .. 7: bit 0 hflip, bit 1 vflip, bit 2 transpose, applied in that order on the last two axes (the flags of
+ * eavsr_gather_pairs_u8 below):
+ *     g_k(x)[i, j]   = x[vflip ? H-1-r : r][hflip ? W-1-q : q],   (r, q) = (j, i) if transposed, else (i, j)
+ *     inv_k(z)[y, x] = z[R][Q],   (R, Q) = (x', y') if transposed, else (y', x'),   y' = vflip ? th-1-y : y,   x' = hflip ? tw-1-x : x
+ * so inv_k(g_k(x)) = x.  A transposed mode turns H x W frames into W x H frames.
+ *
+ * eavsr_dihedral_f32: out = g_k(in), in fp32 (F, C, H, W) contiguous, out (F, C, H, W) or, transposed, (F, C, W, H); the 32 bits of
+ * every sample are copied.  in and out must not overlap.  NULL pointer: -1; k outside 0 .. 7, bad dims, F > 65535, C > 65535,
+ * a pointer that is not 4-byte aligned: -2.  F == 0: 0, nothing is launched.
+ *
+ * eavsr_blend_dihedral_f32 is eavsr_tile_blend_f32 with the inverse on the load:
+ *     acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * inv_k(sr)[n, f, c, y, x],   0 <= y < th, 0 <= x < tw
+ * the same three separately rounded fp32 operations, plain stores.  sr: (N, F, C, th, tw) or, transposed, (N, F, C, tw, th), with the
+ * element strides sn, sf, sc, sy (rows) >= 0 and unit stride along its rows; sy at least the length of a row.  k == 0 IS
+ * eavsr_tile_blend_f32.  Error codes as eavsr_tile_blend_f32; k outside 0 .. 7: -2. */
+int eavsr_dihedral_f32(const float* in, float* out, int32_t F, int32_t C, int32_t H, int32_t W, int32_t k, void* stream);
+int eavsr_blend_dihedral_f32(float* acc, const float* sr, const float* wy, const float* wx, int32_t N, int32_t F, int32_t C, int32_t SH,
+                             int32_t SW, int32_t th, int32_t tw, int32_t Y0, int32_t X0, int32_t k, int64_t sn, int64_t sf, int64_t sc,
+                             int64_t sy, void* stream);
 /* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
  * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
  * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
