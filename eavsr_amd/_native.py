@@ -194,6 +194,9 @@ SIGNATURES = {
     "eavsr_frame_metrics_partials": (i32, [i32, i32, i32, i32]),
     "eavsr_frame_metrics_f32": (C.c_int, [vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "eavsr_rgb8_f32": (C.c_int, [vp, f32, i32, i32, i32, i32, vp, vp]),
+    # temporal consistency of the report: warping error and tOF (csrc/temporal.hip; additions to ABI 32)
+    "eavsr_temporal_metrics_partials": (i32, [i32, i32, i32, i32]),
+    "eavsr_temporal_metrics_f32": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "eavsr_u8_to_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
     # padded ingest of frames of any size, and of a window of them: one kernel family (csrc/ingest_pad.hip; additions to ABI 32)
     "eavsr_ingest_pad": (C.c_int, [vp, vp] + [i32] * 8 + [vp]),

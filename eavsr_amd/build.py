@@ -31,8 +31,9 @@ FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-ffp-contract=fast", "-fno-slp-vectorize"]
 
 
-# per-source additions (none at present)
-PER_FILE_FLAGS = {}
+# per-source additions.  temporal.hip defines its metric operation by operation, every fp32 product and sum rounded on
+# its own: no contraction into fused multiply-adds anywhere in that file (the later flag wins over FLAGS' -ffp-contract=fast)
+PER_FILE_FLAGS = {"temporal.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

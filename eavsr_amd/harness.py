@@ -460,22 +460,183 @@ def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0, lpips=No
     return out
 
 
+# -- temporal consistency: warping error and tOF of consecutive frames -----------------------------------------------------
+TEMPORAL_FLOWS = ("hr", "sr")
+# padded image pixels one PWC-Net call may hold (its level buffers take about 200 bytes per image pixel): the pairs of a clip are
+# estimated this many at a time.  A pair's flow does not depend on the split (every pwc.hip kernel computes an output sample from
+# its own pair alone, in an order that does not look at the batch), so this bounds memory and nothing else.
+_FLOW_PIXELS = 1 << 22
+
+
+def check_temporal_flow(flow_from, what: str = "flow_from") -> Optional[str]:
+    if flow_from is not None and flow_from not in TEMPORAL_FLOWS:
+        raise ValueError(f"{what}={flow_from!r}: 'hr' (flows of the ground truth), 'sr' (flows of the output itself) or None")
+    return flow_from
+
+
+def temporal_option(opt=None):
+    """`opt.temporal` -- True, "hr" or "sr" (a flow source also switches the metric on); False is off -- else EAVSR_TEMPORAL=hr|sr,
+    else None: the temporal metrics are off and nothing is launched for them."""
+    from .segments import read_option, one_of
+    value = read_option(opt, "temporal", "EAVSR_TEMPORAL", one_of((True, False) + TEMPORAL_FLOWS, "True, 'hr', 'sr' or None"),
+                        one_of(TEMPORAL_FLOWS, "hr or sr (or unset)"))
+    return None if value is False else value
+
+
+def temporal_net(temporal, opt=None, device=None, who: str = "temporal"):
+    """The PWC-Net behind `temporal=`: a `pwc.PWCNET` as it is, a path read with `pwc.load_pwc_weights`, True: `opt.pwc_path`.
+    A missing file is a ValueError that names it -- raised before anything is launched."""
+    from . import pwc
+    if isinstance(temporal, pwc.PWCNET):
+        return temporal
+    if temporal is True:
+        path = getattr(opt, "pwc_path", None)
+        if path is None:
+            raise ValueError(f"{who}: temporal=True reads the PWC-Net weights from opt.pwc_path, and the options carry none "
+                             "(no PWC-Net weights ship with this project)")
+    elif isinstance(temporal, (str, os.PathLike)):
+        path = temporal
+    else:
+        raise ValueError(f"{who}: temporal={temporal!r}: a pwc.PWCNET, the path of its weights, or True (opt.pwc_path)")
+    path = os.fspath(path)
+    if not os.path.isfile(path):
+        raise ValueError(f"{who}: PWC-Net weights {path!r} not found (no PWC-Net weights ship with this project: name the file)")
+    net = pwc.load_pwc_weights(pwc.PWCNET(), path).to(device).eval()
+    for p in net.parameters():
+        p.requires_grad_(False)
+    return net
+
+
+def _check_flow_frames(frames, who: str):
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or int(frames.shape[0]) < 2:
+        raise ValueError(f"{who}: frames are an (F, 3, H, W) tensor with F >= 2, got "
+                         f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)}")
+    if int(frames.shape[1]) != 3:
+        raise ValueError(f"{who}: PWC-Net reads RGB frames: C = {int(frames.shape[1])}, only C = 3 is accepted")
+
+
+def _flows(frames: Tensor, net, scale: float, backward: bool):
+    """(fw, bw or None) of the F - 1 consecutive pairs of frames (F, 3, H, W): both directions of as many pairs as _FLOW_PIXELS
+    allows share one `pwc.estimate` call (rows [0, p): t -> t + 1, rows [p, 2p): t + 1 -> t)."""
+    from . import pwc
+    f, _, h, w = (int(v) for v in frames.shape)
+    x = frames.detach().to(torch.float32)
+    if float(scale) != 255.0:      # scale takes a sample to 0 .. 255 (ops.frame_metrics); PWC-Net reads [0, 1]
+        x = x * (float(scale) / 255.0)
+    hp, wp = -(-h // 64) * 64, -(-w // 64) * 64
+    per_call = max(1, _FLOW_PIXELS // ((4 if backward else 2) * hp * wp))
+    fw = torch.empty((f - 1, 2, h, w), device=x.device, dtype=torch.float32)
+    bw = torch.empty_like(fw) if backward else None
+    with torch.no_grad():
+        for a in range(0, f - 1, per_call):
+            p = min(per_call, f - 1 - a)
+            first, second = x[a:a + p], x[a + 1:a + 1 + p]
+            if backward:
+                flow = pwc.estimate(torch.cat([first, second], 0), torch.cat([second, first], 0), net)
+                fw[a:a + p].copy_(flow[:p])
+                bw[a:a + p].copy_(flow[p:])
+            else:
+                fw[a:a + p].copy_(pwc.estimate(first, second, net))
+    return fw, bw
+
+
+def pair_flows(frames: Tensor, net, scale: float = 255.0):
+    """The optical flow between consecutive frames, both ways, by the project's PWC-Net (`pwc.estimate`): frames (F, 3, H, W) on the
+    device (scale 255: samples in [0, 1]; scale 1: 0 .. 255) -> (fw, bw), each (F - 1, 2, H, W) in pixels, channel 0 = x; fw[t] is
+    the flow t -> t + 1, bw[t] the flow t + 1 -> t.  A pair's flow is the same bits whether it is estimated alone or with others."""
+    _check_flow_frames(frames, "pair_flows")
+    return _flows(frames, net, scale, True)
+
+
+def _temporal_device(sr: Tensor, hr: Optional[Tensor], net, scale: float, flow_from: str):
+    """(err, count, epe or None) of `ops.temporal_metrics` for one clip sr (F, C, H, W) [/ hr of the same shape], on the device"""
+    from . import ops
+    if flow_from == "hr":
+        fw, bw = _flows(hr, net, scale, True)
+        flow_b = _flows(sr, net, scale, False)[0]
+    else:
+        (fw, bw), flow_b = _flows(sr, net, scale, True), None
+    return ops.temporal_metrics(sr.detach(), fw, bw, scale, flow_b)
+
+
+def temporal_values(err, count, epe, c: int, h: int, w: int) -> Dict[str, List]:
+    """The sums of `ops.temporal_metrics` as the report's numbers, in float64 on the host: 'ewarp' = err / (C count) / 255^2 (`nan`
+    where no pixel is valid), 'valid' = count / (H W), 'tof' = epe / (H W) (None without epe)."""
+    err, count = [float(v) for v in err], [int(v) for v in count]
+    out = {"ewarp": [e / (c * n) / (255.0 * 255.0) if n else math.nan for e, n in zip(err, count)],
+           "valid": [n / (h * w) for n in count], "tof": None}
+    if epe is not None:
+        out["tof"] = [float(v) / (h * w) for v in epe]
+    return out
+
+
+def _resolve_flow_from(flow_from, has_hr: bool, who: str) -> str:
+    check_temporal_flow(flow_from, f"{who}: flow_from")
+    if flow_from is None:
+        return "hr" if has_hr else "sr"
+    if flow_from == "hr" and not has_hr:
+        raise ValueError(f"{who}: flow_from='hr' needs the HR frames (flow_from='sr' scores footage without ground truth)")
+    return flow_from
+
+
+def temporal_metrics(sr_seq: Tensor, hr_seq: Optional[Tensor], net, scale: float = 255.0, flow_from: Optional[str] = None) -> Dict:
+    """Temporal consistency of every pair of consecutive frames: sr_seq (n, t, 3, H, W) [hr_seq of the same shape, or
+    None] on the device, `net` a `pwc.PWCNET` -> {'ewarp', 'valid', 'tof'}, lists in (n, t - 1) order.
+    'ewarp': the warping error -- frame t + 1 warped back to frame t along the flow, mean squared difference of the 8-bit images over
+    the pixels that are neither occluded, nor on a motion boundary, nor out of frame, over 255^2 (`nan` where none is left);
+    'valid': the share of such pixels; 'tof': the mean endpoint distance between the SR pair's flow and the HR pair's.
+    flow_from="hr" (the default where hr_seq is given): the warp and its mask use the HR frames' flows, and tOF is reported;
+    "sr" (footage without ground truth): the SR frames' own flows, 'tof' is None.  The flows are PWC-Net's (`pair_flows`): the
+    values are this project's own and compare with nothing computed with another estimator."""
+    if not isinstance(sr_seq, torch.Tensor) or sr_seq.dim() != 5 or (hr_seq is not None and hr_seq.shape != sr_seq.shape):
+        raise ValueError("temporal_metrics: (n, t, 3, H, W) tensors of one shape, got "
+                         f"{tuple(sr_seq.shape)} / {None if hr_seq is None else tuple(hr_seq.shape)}")
+    flow_from = _resolve_flow_from(flow_from, hr_seq is not None, "temporal_metrics")
+    n, t, c, h, w = (int(v) for v in sr_seq.shape)
+    if t < 2:
+        raise ValueError(f"temporal_metrics: {t} frame(s): a pair needs two")
+    _check_flow_frames(sr_seq[0], "temporal_metrics")
+    out = {"ewarp": [], "valid": [], "tof": [] if flow_from == "hr" else None}
+    parts = [_temporal_device(sr_seq[b], hr_seq[b] if flow_from == "hr" else None, net, scale, flow_from) for b in range(n)]
+    for err, count, epe in parts:
+        vals = temporal_values(err.tolist(), count.tolist(), None if epe is None else epe.tolist(), c, h, w)
+        out["ewarp"] += vals["ewarp"]
+        out["valid"] += vals["valid"]
+        if epe is not None:
+            out["tof"] += vals["tof"]
+    return out
+
+
 def psnr_from_sse(sse: int, count: int, range: float = 255.0) -> float:
     """-10 log10(sse / count / range^2) in float64 (psnr_total.py:13-20 on the 8-bit image); `inf` when sse == 0"""
     return math.inf if sse == 0 else -10.0 * math.log10(sse / count / (range * range))
 
 
-def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[float], lpips: Optional[Sequence[float]] = None) -> Dict:
+TEMPORAL_COLUMNS = ("ewarp", "tof")
+
+
+def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[float], lpips: Optional[Sequence[float]] = None,
+                 temporal: Optional[Dict] = None) -> Dict:
     """The averaging of psnr_total.py:89-133 (host only): frames are grouped by the scene in the first three characters of their
     name, every scene's frames are averaged, then the scene means are averaged -- NOT the frames, so a short scene weighs as much
     as a long one.  Returns {'frames': [{'name', 'scene', 'psnr', 'ssim'}, ...] in the given order, 'scenes': {scene: {'psnr',
     'ssim', 'frames': count}} sorted by scene, 'final': {'psnr', 'ssim', 'scenes': count}}.
     With `lpips` (one value per frame: the third column of the reference's log, psnr_total.py:116-138) every frame, every scene and
-    'final' carry an 'lpips' field as well, averaged exactly as the other two; without it the report has no such field."""
+    'final' carry an 'lpips' field as well, averaged exactly as the other two; without it the report has no such field.
+    With `temporal` = {'ewarp': [...], 'tof': [...] or None} (one entry per frame: the pair (previous frame, this
+    frame), None for a frame that has no predecessor in its clip) every frame, scene and 'final' carry 'ewarp' and 'tof': a scene's
+    mean runs over its entries that are not None, the final mean over the scene means that are not None; None where there is none.
+    A pair without a valid pixel has the warping error `nan`: the frame keeps it, the means leave it out as they leave out None (one
+    fully masked pair does not turn a column into `nan`).  Without it the report has no such fields."""
     if not (len(names) == len(psnr) == len(ssim)):
         raise ValueError(f"scene_report: {len(names)} names, {len(psnr)} PSNR and {len(ssim)} SSIM values")
     if lpips is not None and len(lpips) != len(names):
         raise ValueError(f"scene_report: {len(names)} names and {len(lpips)} LPIPS values")
+    if temporal is not None:
+        temporal = {k: ([None] * len(names) if temporal.get(k) is None else list(temporal[k])) for k in TEMPORAL_COLUMNS}
+        for k, v in temporal.items():
+            if len(v) != len(names):
+                raise ValueError(f"scene_report: {len(names)} names and {len(v)} {k} entries")
     frames = [{"name": str(nm), "scene": str(nm)[:3], "psnr": float(p), "ssim": float(s)} for nm, p, s in zip(names, psnr, ssim)]
     cols = ["psnr", "ssim"]
     if lpips is not None:
@@ -488,6 +649,15 @@ def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[flo
         rows = [fr for fr in frames if fr["scene"] == scene]
         scenes[scene] = {**{k: mean([r[k] for r in rows]) for k in cols}, "frames": len(rows)}
     final = {**{k: mean([v[k] for v in scenes.values()]) for k in cols}, "scenes": len(scenes)}
+    if temporal is not None:
+        some = lambda v: sum(v) / len(v) if v else None
+        has = lambda v: v is not None and math.isfinite(v)
+        for k in TEMPORAL_COLUMNS:
+            for fr, v in zip(frames, temporal[k]):
+                fr[k] = None if v is None else float(v)
+            for scene, row in scenes.items():
+                row[k] = some([fr[k] for fr in frames if fr["scene"] == scene and has(fr[k])])
+            final[k] = some([row[k] for row in scenes.values() if row[k] is not None])
     return {"frames": frames, "scenes": scenes, "final": final}
 
 
@@ -495,9 +665,16 @@ def write_metrics_log(report: Dict, path: str) -> str:
     """A `scene_report` as a text file: per scene its frames and its mean, then the final line; PSNR to 2 decimals and SSIM to 4,
     the precision of the reference's log (psnr_total.py:116-138), in this project's own layout.  A report with LPIPS (see
     `scene_report`) gets `  lpips %.3f` at the end of every line, the reference's three decimals; one without it produces the
-    file it always produced."""
+    file it always produced.  A report with the temporal columns gets `  ewarp %.6f  tof %.4f` after that, `-` where a row has no
+    value (a frame without a predecessor; tOF without HR flows)."""
     lines = []
-    third = lambda row: "  lpips %.3f" % row["lpips"] if "lpips" in report["final"] else ""
+    cell = lambda fmt, v: "-" if v is None else fmt % v
+
+    def third(row):
+        text = "  lpips %.3f" % row["lpips"] if "lpips" in report["final"] else ""
+        if "ewarp" in report["final"]:
+            text += "  ewarp %s  tof %s" % (cell("%.6f", row["ewarp"]), cell("%.4f", row["tof"]))
+        return text
     for scene, mean in report["scenes"].items():
         lines.append(f"scene {scene}")
         for fr in report["frames"]:
@@ -557,7 +734,8 @@ def crop_center(img: Tensor, p: int) -> Tensor:
 
 
 def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssim_flag: bool = False,
-             save_root: Optional[str] = None, load_iter="0", full_res: bool = False, per_frame: bool = False, lpips=None) -> Dict:
+             save_root: Optional[str] = None, load_iter="0", full_res: bool = False, per_frame: bool = False, lpips=None,
+             temporal=None, temporal_flow: Optional[str] = None) -> Dict:
     """The timed loop of test_basic.py:56-83 for a model wrapper (EAVSRPModel / EAVSRPx2Model); with `save_root` the frames are
     written as the reference's `--save_imgs` does (test_basic.py:85-92, `save_visuals`); `calc_ssim_flag` adds psnr_total.py's SSIM
     per item (mean over the item's frames).
@@ -576,9 +754,27 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     `lpips` (with `per_frame=True` only; it raises otherwise): an `eavsr_amd.lpips.LPIPSAlex`, or the path of its weights (one file
     in the lpips package's state-dict layout, see `lpips.load_lpips_weights`), read once; the default is `model.opt.lpips_path`
     where the options have one.  The result then gains 'frame_lpips' and the report its 'lpips' column (psnr_total.py:27-35, every
-    frame pair on the same 8-bit images).  Items without HR frames are skipped, as they are for PSNR and SSIM."""
+    frame pair on the same 8-bit images).  Items without HR frames are skipped, as they are for PSNR and SSIM.
+
+    `temporal` (with `per_frame=True` only; it raises otherwise): a `pwc.PWCNET`, the path of its weights, or True
+    (`opt.pwc_path`); the default is `opt.temporal` / EAVSR_TEMPORAL (`temporal_option`).  Every pair of consecutive frames inside
+    an item, separately for each batch entry, is scored with `temporal_metrics` (`temporal_flow`: its `flow_from`): the result gains
+    'frame_ewarp' / 'frame_tof' / 'frame_valid' -- one entry per frame, None for an item's first frame -- and the report its
+    'ewarp' / 'tof' columns.  Unset, nothing is launched for it and the result is what it was."""
     if lpips is not None and not per_frame:
         raise ValueError("evaluate: lpips needs per_frame=True (LPIPS is part of the per-frame report)")
+    if temporal is False:
+        temporal = None
+    if temporal is not None and not per_frame:
+        raise ValueError("evaluate: temporal needs per_frame=True (the temporal metrics are part of the per-frame report)")
+    check_temporal_flow(temporal_flow, "evaluate: temporal_flow")
+    if temporal is None and per_frame:
+        temporal = temporal_option(getattr(model, "opt", None))
+        if temporal in TEMPORAL_FLOWS:
+            temporal, temporal_flow = True, (temporal if temporal_flow is None else temporal_flow)
+    if temporal is not None:
+        temporal = temporal_net(temporal, getattr(model, "opt", None), model.device, "evaluate")
+    frame_temporal = {"ewarp": [], "tof": [], "valid": []}
     if lpips is None and per_frame:
         lpips = getattr(getattr(model, "opt", None), "lpips_path", None)
     if isinstance(lpips, (str, os.PathLike)):
@@ -616,6 +812,12 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
                 frame_ssim += fs
                 if lpips is not None:
                     frame_lpips += lpips(sr.reshape(n * t, c, h, w), hr.reshape(n * t, c, h, w), 255.0).tolist()
+                if temporal is not None:
+                    vals = ({"ewarp": [], "valid": [], "tof": None} if t < 2 else
+                            temporal_metrics(model.data_sr_seq.detach(), hr, temporal, 255.0, temporal_flow))
+                    for k in frame_temporal:
+                        for b in range(n):
+                            frame_temporal[k] += [None] + ([None] * (t - 1) if vals[k] is None else vals[k][b * (t - 1):(b + 1) * (t - 1)])
                 frame_names += [_frame_name(data.get("fname"), i, b) for b in range(n) for i in range(t)]
                 if calc_psnr_flag:
                     psnr.append(psnr_from_sse(sum(sse), n * t * c * h * w))
@@ -648,10 +850,20 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     }
     if per_frame:
         out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
-                   report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips if lpips is not None else None))
+                   report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips if lpips is not None else None,
+                                       **({} if temporal is None else {"temporal": frame_temporal})))
         if lpips is not None:
             out["frame_lpips"] = frame_lpips
+        if temporal is not None:
+            out.update(frame_ewarp=frame_temporal["ewarp"], frame_tof=frame_temporal["tof"], frame_valid=frame_temporal["valid"])
     return out
+
+
+def explicit_cuts(cuts) -> List[int]:
+    """The scene starts of `super_resolve(cuts=[...])` as `segments.plan_segments` takes them: sorted integers without a 0 -- frame 0
+    starts a scene whether it is listed or not, so `cuts=[0]` is `cuts=[]` and `cuts=[0, 5]` is `cuts=[5]` (`plan_segments` itself
+    refuses a 0, and goes on refusing every other start outside (0, t))."""
+    return sorted(int(c) for c in cuts if int(c) != 0)
 
 
 def scene_changes(frames, chunk: int = 64, device=None):
@@ -698,7 +910,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
                   cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
-                  tile_overlap: Optional[int] = None, ensemble=None) -> Dict:
+                  tile_overlap: Optional[int] = None, ensemble=None, temporal=None, temporal_flow: Optional[str] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -751,9 +963,20 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     device (`EAVSRP.forward_ensemble`); it composes with everything above, and the scene cuts read the untransformed bytes.  About
     len(modes) times the work.  The network is not equivariant, so the modes differ; whether their mean is BETTER is not known
     here (no trained weights exist in this project).  None: `opt.ensemble` of a model wrapper, else EAVSR_ENSEMBLE=8|4|2|flips|0,1,4
-    (`segments.ensemble_options`), else off.  The result carries 'ensemble': the tuple of modes that ran ((0,): off)."""
+    (`segments.ensemble_options`), else off.  The result carries 'ensemble': the tuple of modes that ran ((0,): off).
+
+    Temporal consistency, opt-in: `temporal` -- a `pwc.PWCNET`, the path of its weights, or True (`opt.pwc_path`) -- scores
+    every pair of consecutive frames of every clip with `ops.temporal_metrics` on PWC-Net flows (`pair_flows`); `temporal_flow` is
+    `temporal_metrics`' `flow_from`: "hr" (the default with `hr`; tOF is reported) or "sr" (no ground truth needed).  The sink keeps
+    the last SR / HR frame of the previous chunk, so a pair that straddles two chunks, two windows or two emit ranges is scored once
+    and the numbers do not depend on `frame_chunk`; a pair across a scene start the forward honoured (`cuts`, after the merge of
+    short scenes; a 0 in an explicit list is the clip's own start and is dropped) is not scored.  The frames scored are the ones the
+    sink sees: cropped (`pad`), blended (`tile`), averaged (`ensemble`).  The result gains 'frame_ewarp' / 'frame_tof' /
+    'frame_valid', one entry per frame in (n, t) order and None for a frame without a scored predecessor, and the report (with `hr`)
+    its 'ewarp' / 'tof' columns.  None: `opt.temporal` of a model wrapper, else EAVSR_TEMPORAL=hr|sr (`temporal_option`; the weights
+    then come from `opt.pwc_path`), else off: no launch and no byte differs from a run without it."""
     from . import ops
-    from .segments import (check_pad, check_tile, find_cuts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
+    from .segments import (check_pad, check_tile, find_cuts, keep_starts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
                            tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP,
                            check_ensemble, ensemble_options, parse_ensemble)
     if ensemble is None:      # a bad spec is refused here, before a file is read
@@ -788,6 +1011,16 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     device = next(net.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("super_resolve: the network must be on the GPU (eavsr_amd has no CPU path)")
+    if temporal is False:
+        temporal = None
+    check_temporal_flow(temporal_flow, "super_resolve: temporal_flow")
+    if temporal is None:
+        temporal = temporal_option(getattr(model, "opt", None))
+        if temporal in TEMPORAL_FLOWS:
+            temporal, temporal_flow = True, (temporal if temporal_flow is None else temporal_flow)
+    if temporal is not None:      # refused here, before a file is read: a missing weights file, "hr" without HR frames
+        temporal_flow = _resolve_flow_from(temporal_flow, hr is not None, "super_resolve")
+        temporal = temporal_net(temporal, getattr(model, "opt", None), device, "super_resolve")
     paths = None
     if isinstance(frames, (list, tuple)):
         paths = [os.fspath(p) for p in frames]
@@ -813,6 +1046,10 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     if lrs.dtype != torch.uint8:
         lrs = lrs.to(device=device, dtype=torch.float32)
     n, t = int(lrs.shape[0]), int(lrs.shape[1])
+    if temporal is not None:      # refused before anything runs: the SR frames have the input's channels, and PWC-Net reads RGB
+        channels = int(lrs.shape[4] if (lrs.dtype == torch.uint8 and lrs.shape[4] == 3 and lrs.shape[2] != 3) else lrs.shape[2])
+        if channels != 3:
+            raise ValueError(f"super_resolve: temporal: PWC-Net reads RGB frames: C = {channels}, only C = 3 is accepted")
     if hr is not None:
         hr = as_clip(hr, "hr")
         if tuple(hr.shape[:2]) != (n, t):
@@ -838,7 +1075,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         if n != 1 or lrs.dtype != torch.uint8:
             raise ValueError(f"super_resolve: cuts='device' reads one clip of 8-bit frames, got n={n}, {lrs.dtype}")
     elif cuts is not None:
-        cuts = sorted(int(c) for c in cuts)
+        cuts = explicit_cuts(cuts)
     hist_thr, sad_thr = (DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD) if cut_thresholds is None else cut_thresholds
     segmented = max_frames is not None or cuts is not None
     if segmented:      # max_frames / overlap / min_scene / explicit starts are refused here, before anything is allocated or run
@@ -864,6 +1101,29 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         part = part.reshape((n * (b - a),) + tuple(part.shape[2:]))
         return ops.u8_to_f32(part) if part.dtype == torch.uint8 else part.to(torch.float32)
 
+    # temporal consistency: the last frame of the previous chunk is kept (a copy: a chunk may be a view of storage the forward
+    # reuses), so the pair that straddles two sink calls is scored with the later one
+    held = {"next": None, "sr": None, "hr": None}
+    scene_bounds: List[int] = []      # the scene starts the forward honours: no pair is scored across one
+    temporal_parts = []               # (clip frame of the first pair's second frame, [(err, count, epe) per clip]), on the device
+    temporal_shape = []
+
+    def score_pairs(first, sr, ref):
+        k = int(sr.shape[1])
+        temporal_shape[:] = [int(v) for v in sr.shape[2:]]
+
+        def score(at, seq_sr, seq_hr):      # frames [at - 1, at - 1 + len) of the clip: one run inside a scene
+            temporal_parts.append((at, [_temporal_device(seq_sr[b], None if seq_hr is None else seq_hr[b], temporal, 255.0,
+                                                         temporal_flow) for b in range(n)]))
+
+        if held["next"] == first and first not in scene_bounds:      # the pair that straddles two sink calls, on its own
+            score(first, torch.cat([held["sr"], sr[:, :1]], 1), None if ref is None else torch.cat([held["hr"], ref[:, :1]], 1))
+        bounds = [first] + [s for s in scene_bounds if first < s < first + k] + [first + k]
+        for lo, hi in zip(bounds[:-1], bounds[1:]):      # the chunk's own pairs, in place
+            if hi - lo >= 2:
+                score(lo + 1, sr[:, lo - first:hi - first], None if ref is None else ref[:, lo - first:hi - first])
+        held.update(next=first + k, sr=sr[:, -1:].clone(), hr=None if ref is None else ref[:, -1:].clone())
+
     def sink(first, sr):
         k = int(sr.shape[1])
         c, hh, ww = (int(v) for v in sr.shape[2:])
@@ -881,6 +1141,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                 lpips_parts.append(lpips(flat, ref, 255.0).view(n, k))
         elif out_dir is not None:
             rgb8 = ops.rgb8(flat, 255.0)
+        if temporal is not None:
+            score_pairs(first, sr, ref.view(n, k, c, hh, ww) if temporal_flow == "hr" else None)
         if staging is not None:
             job = staging.enqueue(rgb8[:k])      # clip 0, as save_visuals; nothing here waits for the device
             write_pending()                      # the previous chunk's files, while this chunk's encoder runs
@@ -905,6 +1167,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
             else:
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
+            scene_bounds[:] = keep_starts(t, starts, min_scene)
         if modes == (0,):
             net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
                               frame_chunk=frame_chunk, cache=cache, sink=sink)
@@ -917,6 +1180,17 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
            "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
            "segments": plan, "scene_starts": starts, "tiles": tiles, "ensemble": modes}
+    frame_temporal = None
+    if temporal is not None:
+        rows = {key: [[None] * t for _ in range(n)] for key in ("ewarp", "tof", "valid")}
+        for at, per_clip in temporal_parts:
+            for b, (err, count, epe) in enumerate(per_clip):
+                vals = temporal_values(err.tolist(), count.tolist(), None if epe is None else epe.tolist(), *temporal_shape)
+                for key, row in rows.items():
+                    if vals[key] is not None:
+                        row[b][at:at + len(vals[key])] = vals[key]
+        frame_temporal = {key: [v for row in rows[key] for v in row] for key in rows}      # (n, t) order
+        out.update(frame_ewarp=frame_temporal["ewarp"], frame_tof=frame_temporal["tof"], frame_valid=frame_temporal["valid"])
     if hr is not None:
         sse = torch.cat(sse_parts, 1).reshape(-1).tolist()      # (n, t) order, as evaluate
         frame_ssim = torch.cat(ssim_parts, 1).reshape(-1).tolist()
@@ -924,7 +1198,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         frame_names = [_frame_name(names, i, b) for b in range(n) for i in range(t)]
         frame_lpips = torch.cat(lpips_parts, 1).reshape(-1).tolist() if lpips is not None else None
         out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
-                   report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips))
+                   report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips,
+                                       **({} if frame_temporal is None else {"temporal": frame_temporal})))
         if lpips is not None:
             out["frame_lpips"] = frame_lpips
     return out

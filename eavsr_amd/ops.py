@@ -1526,6 +1526,40 @@ def frame_metrics(sr: Tensor, hr: Tensor, scale: float = 255.0, rgb8: bool = Fal
     return sse, ssim_sum / float(c * (h - 10) * (w - 10)), img
 
 
+def temporal_metrics(seq: Tensor, fw: Tensor, bw: Tensor, scale: float = 255.0, flow_b: Optional[Tensor] = None):
+    """Warping error and tOF of every pair of consecutive frames (DESIGN 7l; csrc/temporal.hip): seq (F, C, H, W), C 1 or 3, F >= 2;
+    fw, bw (F - 1, 2, H, W) the flows t -> t + 1 and t + 1 -> t in pixels (channel 0 = x); flow_b (optional, fw's shape) the flow
+    `fw` is compared with -> (err float64 (F - 1,), count int64 (F - 1,), epe float64 (F - 1,) or None), all on the device: per
+    pair the squared difference, summed over the `count` pixels that pass the occlusion / motion-boundary / in-frame test and the C
+    planes, between frame t and frame t + 1 warped back along fw, both quantised as `frame_metrics` quantises; and the endpoint
+    distance |flow_b - fw| summed over every pixel.  E_warp = err / (C count) / 255^2, tOF = epe / (H W) (`harness.temporal_metrics`).
+    Non-contiguous inputs are copied.  One fused launch and a fixed-order sum: two calls on the same input agree bit for bit."""
+    seq, fw, bw = _chk(seq, "seq"), _chk(fw, "fw"), _chk(bw, "bw")
+    if flow_b is not None:
+        flow_b = _chk(flow_b, "flow_b")
+    if seq.dim() != 4:
+        raise ValueError(f"temporal_metrics: seq is an (F, C, H, W) tensor, got {tuple(seq.shape)}")
+    f, c, h, w = (int(v) for v in seq.shape)
+    for name, flow in (("fw", fw), ("bw", bw), ("flow_b", flow_b)):
+        if flow is not None and tuple(flow.shape) != (f - 1, 2, h, w):
+            raise ValueError(f"temporal_metrics: {name} is {tuple(flow.shape)}, the {f} frames of {h} x {w} need {(f - 1, 2, h, w)}")
+        if flow is not None and flow.device != seq.device:
+            raise ValueError(f"temporal_metrics: {name} is on {flow.device}, seq on {seq.device}")
+    parts = lib().eavsr_temporal_metrics_partials(f, c, h, w)
+    if parts < 0:
+        N.check(parts, "temporal_metrics")
+    ws = torch.empty(((f - 1) * parts, 3), device=seq.device, dtype=torch.int64)      # 24 bytes per workgroup record
+    err = torch.empty(f - 1, device=seq.device, dtype=torch.float64)
+    count = torch.empty(f - 1, device=seq.device, dtype=torch.int64)
+    epe = torch.empty(f - 1, device=seq.device, dtype=torch.float64) if flow_b is not None else None
+    st = _stream(seq)
+    px = float(f - 1) * h * w
+    _launch("temporal_metrics", px * (60.0 + 30.0 * c), 4.0 * px * (4 + 2 * c + (2 if flow_b is not None else 0)), seq,
+            lambda: lib().eavsr_temporal_metrics_f32(_p(seq), _p(fw), _p(bw), _p(flow_b), float(scale), f, c, h, w, _p(ws), _p(err),
+                                                     _p(count), _p(epe), st), "temporal_metrics")
+    return err, count, epe
+
+
 def rgb8(sr: Tensor, scale: float = 255.0) -> Tensor:
     """sr (F, C, H, W), C 1 or 3 -> uint8 (F, H, W, C): rint(clamp(v * scale, 0, 255)) interleaved, the bytes of the frame's PNG
     scanlines (test_basic.py:85-92), without the metrics"""

@@ -914,6 +914,30 @@ int32_t eavsr_lpips_tap_partials(int32_t h, int32_t w);
 int eavsr_lpips_tap_f32(const float* feat, const float* lin_weight, void* workspace, double* out, int32_t F, int32_t C, int32_t h,
                         int32_t w, int32_t accumulate, void* stream);
 
+/* ---- f4: temporal consistency of the report, warping error and tOF (csrc/temporal.hip; added to ABI 32, nothing above changes) ------
+ * Per pair (t, t + 1) of the F frames of seq (F, C, H, W), C 1 or 3, fp32 NCHW, with fw, bw (F - 1, 2, H, W) the flows t -> t + 1 and
+ * t + 1 -> t in pixels (channel 0 = x) and flow_b (nullable) a second flow of fw's shape.  Per pixel (x, y), every fp32 operation
+ * rounded on its own (no fused multiply-add):
+ *   (u, v) = fw[t,:,y,x];  (sx, sy) = (x + u, y + v);  inside = 0 <= sx <= W - 1 and 0 <= sy <= H - 1 (false for NaN)
+ *   bil(P) = the bilinear sample of P at (sx, sy): x0 = floor(sx), ax = sx - x0, x1 = min(x0 + 1, W - 1), y likewise,
+ *            (1 - ay) ((1 - ax) P[y0,x0] + ax P[y0,x1]) + ay ((1 - ax) P[y1,x0] + ax P[y1,x1])
+ *   (bu, bv) = bil(bw[t]);  m_f = u u + v v;  m_b = bu bu + bv bv;  m_fb = (u + bu)^2 + (v + bv)^2
+ *   g = ((fw[t,0,y,xr] - u)^2 + (fw[t,1,y,xr] - v)^2) + ((fw[t,0,yd,x] - u)^2 + (fw[t,1,yd,x] - v)^2), xr = min(x + 1, W - 1),
+ *       yd = min(y + 1, H - 1)
+ *   valid = inside and m_fb <= 0.01f (m_f + m_b) + 0.5f and g <= 0.01f m_f + 0.002f          (any NaN: not valid)
+ *   count_out[t] = the valid pixels;  err_out[t] = sum over them and the C planes of (double)d (double)d,
+ *                  d = q(seq[t,c,y,x]) - bil(q(seq[t+1,c])), q(p) = rint(clamp(p scale, 0, 255)) as eavsr_frame_metrics_f32
+ *   epe_out[t]   = sum over ALL pixels of sqrt((double)eu eu + (double)ev ev), (eu, ev) = flow_b[t,:,y,x] - (u, v); flow_b and
+ *                  epe_out are both given or both NULL.
+ * workspace: (F - 1) * eavsr_temporal_metrics_partials(F, C, H, W) * 24 bytes, 8-byte aligned (one (fp64, fp64, int64) record per
+ * workgroup; summed per pair in a fixed order by a second launch: no atomics, two calls on the same input agree bit for bit).
+ * NULL pointer, flow_b without epe_out or the reverse: -1; F < 2 or > 65536, C not 1 or 3, H or W < 1 or > 2^24, misaligned
+ * workspace / outputs: -2 (eavsr_temporal_metrics_partials returns -2 as well). */
+int32_t eavsr_temporal_metrics_partials(int32_t F, int32_t C, int32_t H, int32_t W);
+int eavsr_temporal_metrics_f32(const float* seq, const float* fw, const float* bw, const float* flow_b, float scale, int32_t F,
+                               int32_t C, int32_t H, int32_t W, void* workspace, double* err_out, int64_t* count_out, double* epe_out,
+                               void* stream);
+
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
  * Schedules that were built, measured against the stable ones above and retired; kept because DESIGN.md / docs/history quote
