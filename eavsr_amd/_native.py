@@ -197,6 +197,9 @@ SIGNATURES = {
     # temporal consistency of the report: warping error and tOF (csrc/temporal.hip; additions to ABI 32)
     "eavsr_temporal_metrics_partials": (i32, [i32, i32, i32, i32]),
     "eavsr_temporal_metrics_f32": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    # NIQE, the report's no-reference column: block moments and the antialiased half-size resize (csrc/niqe.hip; additions to ABI 32)
+    "eavsr_niqe_moments": (C.c_int, [vp, i32, f32] + [i32] * 9 + [C.POINTER(C.c_double), vp, vp, vp]),
+    "eavsr_niqe_half_f64": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, i32, vp, i32] + [i32] * 5 + [vp]),
     "eavsr_u8_to_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
     # padded ingest of frames of any size, and of a window of them: one kernel family (csrc/ingest_pad.hip; additions to ABI 32)
     "eavsr_ingest_pad": (C.c_int, [vp, vp] + [i32] * 8 + [vp]),

@@ -20,6 +20,7 @@ import time
 import zlib
 from typing import Dict, Iterable, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from .segments import DEFAULT_OVERLAP
@@ -442,14 +443,18 @@ def save_frames_rgb8(rgb8: Tensor, fnames: Sequence, root: str, load_iter="0", f
     return paths
 
 
-def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0, lpips=None) -> Dict[str, List[float]]:
+def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0, lpips=None, niqe=None, niqe_crop: int = 0) -> Dict[str, List[float]]:
     """PSNR and SSIM of every frame on its own, as psnr_total.py:39-44 scores the stored PNG files: sr_seq / hr_seq (n, t, C, H, W)
     device tensors (scale 255: the model's [0, 1] output and target; scale 1: `get_current_visuals()` tensors), quantised to the
     8-bit image inside the kernel (`ops.frame_metrics`).  PSNR = -10 log10(sse / (C H W) / 255^2) in float64 on the host from the
     kernel's exact integer sse (`inf` for identical frames); SSIM is skimage's gaussian-window definition in fp64 (`calc_ssim`).
     Returns {'psnr': [...], 'ssim': [...]} in (n, t) order; with `lpips` (an `eavsr_amd.lpips.LPIPSAlex` on the tensors' device)
-    also 'lpips': the AlexNet LPIPS of every frame pair on the same 8-bit images (psnr_total.py:27-35)."""
+    also 'lpips': the AlexNet LPIPS of every frame pair on the same 8-bit images (psnr_total.py:27-35); with `niqe` (an
+    `eavsr_amd.niqe.NIQE`, or what `niqe_scorer` makes one from) also 'niqe': the no-reference score of every SR frame on the same
+    8-bit image, `niqe_crop` pixels removed on every side."""
     from . import ops
+    if niqe is not None:
+        niqe = niqe_scorer(niqe, None, "frame_metrics")
     if sr_seq.dim() != 5 or sr_seq.shape != hr_seq.shape:
         raise ValueError(f"frame_metrics: (n, t, C, H, W) tensors of one shape, got {tuple(sr_seq.shape)} / {tuple(hr_seq.shape)}")
     c, h, w = (int(v) for v in sr_seq.shape[2:])
@@ -457,6 +462,68 @@ def frame_metrics(sr_seq: Tensor, hr_seq: Tensor, scale: float = 255.0, lpips=No
     out = {"psnr": [psnr_from_sse(v, c * h * w) for v in sse.tolist()], "ssim": ssim.tolist()}
     if lpips is not None:
         out["lpips"] = lpips(sr_seq.detach().reshape(-1, c, h, w), hr_seq.detach().reshape(-1, c, h, w), scale).tolist()
+    if niqe is not None:
+        out["niqe"] = niqe(sr_seq.detach().reshape(-1, c, h, w), scale, niqe_crop)
+    return out
+
+
+# -- NIQE, the no-reference column ---------------------------------------------------------------------------------------------
+def niqe_option(opt=None):
+    """(`opt.niqe_path`, else EAVSR_NIQE=<path>, else None: NIQE is off and nothing is launched for it;  `opt.niqe_crop`, else 0)"""
+    from .segments import read_option, whole_number
+
+    def a_path(value, who):
+        if not isinstance(value, (str, os.PathLike)) or not os.fspath(value):
+            raise ValueError(f"{who}={value!r}: the file name of a pristine model (see niqe.load_niqe_params)")
+        return os.fspath(value)
+    path = read_option(opt, "niqe_path", "EAVSR_NIQE", a_path, a_path)
+    crop = getattr(opt, "niqe_crop", None)
+    return path, (0 if crop is None else whole_number(0, "a number of pixels >= 0")(crop, "opt.niqe_crop"))
+
+
+def niqe_scorer(niqe, opt=None, who: str = "niqe"):
+    """The scorer behind `niqe=`: an `eavsr_amd.niqe.NIQE` as it is; a file name or a mapping, read with `niqe.load_niqe_params`;
+    True: `opt.niqe_path`.  A missing or malformed file is a ValueError that names it -- raised before anything is launched."""
+    from .niqe import NIQE
+    if isinstance(niqe, NIQE):
+        return niqe
+    if niqe is True:
+        niqe = getattr(opt, "niqe_path", None)
+        if niqe is None:
+            raise ValueError(f"{who}: niqe=True reads the pristine model from opt.niqe_path, and the options carry none "
+                             "(no pristine model ships with this project)")
+    if isinstance(niqe, (str, os.PathLike)) or hasattr(niqe, "keys"):
+        return NIQE(niqe)
+    raise ValueError(f"{who}: niqe={niqe!r}: a niqe.NIQE, the file name of a pristine model, a mapping, or True (opt.niqe_path)")
+
+
+def _resolve_niqe(niqe, niqe_crop, opt, who: str):
+    """(scorer or None, crop) for the `niqe=` / `niqe_crop=` arguments of `evaluate` and `super_resolve`: an argument left None is
+    `niqe_option`'s; niqe=False is off whatever the options say."""
+    opt_path, opt_crop = niqe_option(opt)
+    if niqe is None:
+        niqe = opt_path
+    if niqe_crop is None:
+        niqe_crop = opt_crop
+    if isinstance(niqe_crop, bool) or not isinstance(niqe_crop, int) or niqe_crop < 0:
+        raise ValueError(f"{who}: niqe_crop={niqe_crop!r}: a number of pixels >= 0")
+    if niqe is None or niqe is False:
+        return None, niqe_crop
+    return niqe_scorer(niqe, opt, who), niqe_crop
+
+
+def _niqe_values(niqe, parts) -> List[float]:
+    """The scores of the frames behind `parts` = [(frames, `NIQE.moments` of them on the device, or None), ...], in order: the
+    moments are read back once (per frame size), at the end, so nothing waits for the device while the frames are produced."""
+    held = [m for _, m in parts if m is not None]
+    if held and all(m.shape[1:] == held[0].shape[1:] for m in held):
+        host = torch.cat(held, 0).cpu().numpy()
+        host = iter(np.split(host, np.cumsum([int(m.shape[0]) for m in held])[:-1]))
+    else:
+        host = iter([m.cpu().numpy() for m in held])
+    out: List[float] = []
+    for count, m in parts:
+        out += [math.nan] * count if m is None else niqe.scores(next(host))
     return out
 
 
@@ -615,8 +682,8 @@ def psnr_from_sse(sse: int, count: int, range: float = 255.0) -> float:
 TEMPORAL_COLUMNS = ("ewarp", "tof")
 
 
-def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[float], lpips: Optional[Sequence[float]] = None,
-                 temporal: Optional[Dict] = None) -> Dict:
+def scene_report(names: Sequence[str], psnr: Optional[Sequence[float]], ssim: Optional[Sequence[float]],
+                 lpips: Optional[Sequence[float]] = None, temporal: Optional[Dict] = None, niqe: Optional[Sequence[float]] = None) -> Dict:
     """The averaging of psnr_total.py:89-133 (host only): frames are grouped by the scene in the first three characters of their
     name, every scene's frames are averaged, then the scene means are averaged -- NOT the frames, so a short scene weighs as much
     as a long one.  Returns {'frames': [{'name', 'scene', 'psnr', 'ssim'}, ...] in the given order, 'scenes': {scene: {'psnr',
@@ -627,7 +694,20 @@ def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[flo
     frame), None for a frame that has no predecessor in its clip) every frame, scene and 'final' carry 'ewarp' and 'tof': a scene's
     mean runs over its entries that are not None, the final mean over the scene means that are not None; None where there is none.
     A pair without a valid pixel has the warping error `nan`: the frame keeps it, the means leave it out as they leave out None (one
-    fully masked pair does not turn a column into `nan`).  Without it the report has no such fields."""
+    fully masked pair does not turn a column into `nan`).  Without it the report has no such fields.
+    With `niqe` (one score per frame, `nan` for a frame too small to score) every frame, scene and 'final' carry 'niqe':
+    the frame keeps a `nan`, the means leave it out as the temporal columns do; None where nothing is left.  Footage without
+    ground truth: psnr = ssim = None (both; `niqe` is then required) -- no row, scene or 'final' has a 'psnr' / 'ssim' field at
+    all, they carry the names, the counts and 'niqe'; `lpips` and `temporal` keep their meaning."""
+    if (psnr is None) != (ssim is None):
+        raise ValueError("scene_report: psnr and ssim are given together or both None")
+    scored = psnr is not None
+    if not scored:
+        if niqe is None:
+            raise ValueError("scene_report: without psnr / ssim the report needs niqe")
+        psnr = ssim = [math.nan] * len(names)
+    if niqe is not None and len(niqe) != len(names):
+        raise ValueError(f"scene_report: {len(names)} names and {len(niqe)} NIQE values")
     if not (len(names) == len(psnr) == len(ssim)):
         raise ValueError(f"scene_report: {len(names)} names, {len(psnr)} PSNR and {len(ssim)} SSIM values")
     if lpips is not None and len(lpips) != len(names):
@@ -639,6 +719,10 @@ def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[flo
                 raise ValueError(f"scene_report: {len(names)} names and {len(v)} {k} entries")
     frames = [{"name": str(nm), "scene": str(nm)[:3], "psnr": float(p), "ssim": float(s)} for nm, p, s in zip(names, psnr, ssim)]
     cols = ["psnr", "ssim"]
+    if not scored:
+        cols = []
+        for fr in frames:
+            del fr["psnr"], fr["ssim"]
     if lpips is not None:
         cols.append("lpips")
         for fr, v in zip(frames, lpips):
@@ -658,6 +742,13 @@ def scene_report(names: Sequence[str], psnr: Sequence[float], ssim: Sequence[flo
             for scene, row in scenes.items():
                 row[k] = some([fr[k] for fr in frames if fr["scene"] == scene and has(fr[k])])
             final[k] = some([row[k] for row in scenes.values() if row[k] is not None])
+    if niqe is not None:
+        some = lambda v: sum(v) / len(v) if v else None
+        for fr, v in zip(frames, niqe):
+            fr["niqe"] = float(v)
+        for scene, row in scenes.items():
+            row["niqe"] = some([fr["niqe"] for fr in frames if fr["scene"] == scene and math.isfinite(fr["niqe"])])
+        final["niqe"] = some([row["niqe"] for row in scenes.values() if row["niqe"] is not None])
     return {"frames": frames, "scenes": scenes, "final": final}
 
 
@@ -666,23 +757,28 @@ def write_metrics_log(report: Dict, path: str) -> str:
     the precision of the reference's log (psnr_total.py:116-138), in this project's own layout.  A report with LPIPS (see
     `scene_report`) gets `  lpips %.3f` at the end of every line, the reference's three decimals; one without it produces the
     file it always produced.  A report with the temporal columns gets `  ewarp %.6f  tof %.4f` after that, `-` where a row has no
-    value (a frame without a predecessor; tOF without HR flows)."""
+    value (a frame without a predecessor; tOF without HR flows).  A report with NIQE gets `  niqe %.4f` after that, `-` where the
+    value is `nan` or absent; a report without PSNR / SSIM (footage without ground truth) has no `psnr` / `ssim` cells."""
     lines = []
     cell = lambda fmt, v: "-" if v is None else fmt % v
+    scored = "psnr" in report["final"]
+    first = lambda row: "  psnr %.2f  ssim %.4f" % (row["psnr"], row["ssim"]) if scored else ""
 
     def third(row):
         text = "  lpips %.3f" % row["lpips"] if "lpips" in report["final"] else ""
         if "ewarp" in report["final"]:
             text += "  ewarp %s  tof %s" % (cell("%.6f", row["ewarp"]), cell("%.4f", row["tof"]))
+        if "niqe" in report["final"]:
+            text += "  niqe %s" % cell("%.4f", None if row["niqe"] is None or row["niqe"] != row["niqe"] else row["niqe"])
         return text
     for scene, mean in report["scenes"].items():
         lines.append(f"scene {scene}")
         for fr in report["frames"]:
             if fr["scene"] == scene:
-                lines.append("  %s  psnr %.2f  ssim %.4f" % (fr["name"], fr["psnr"], fr["ssim"]) + third(fr))
-        lines.append("  mean of %d frames  psnr %.2f  ssim %.4f" % (mean["frames"], mean["psnr"], mean["ssim"]) + third(mean))
+                lines.append("  %s" % fr["name"] + first(fr) + third(fr))
+        lines.append("  mean of %d frames" % mean["frames"] + first(mean) + third(mean))
     final = report["final"]
-    lines.append("final, mean of %d scenes  psnr %.2f  ssim %.4f" % (final["scenes"], final["psnr"], final["ssim"]) + third(final))
+    lines.append("final, mean of %d scenes" % final["scenes"] + first(final) + third(final))
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -735,7 +831,7 @@ def crop_center(img: Tensor, p: int) -> Tensor:
 
 def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssim_flag: bool = False,
              save_root: Optional[str] = None, load_iter="0", full_res: bool = False, per_frame: bool = False, lpips=None,
-             temporal=None, temporal_flow: Optional[str] = None) -> Dict:
+             temporal=None, temporal_flow: Optional[str] = None, niqe=None, niqe_crop: Optional[int] = None) -> Dict:
     """The timed loop of test_basic.py:56-83 for a model wrapper (EAVSRPModel / EAVSRPx2Model); with `save_root` the frames are
     written as the reference's `--save_imgs` does (test_basic.py:85-92, `save_visuals`); `calc_ssim_flag` adds psnr_total.py's SSIM
     per item (mean over the item's frames).
@@ -760,7 +856,16 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
     (`opt.pwc_path`); the default is `opt.temporal` / EAVSR_TEMPORAL (`temporal_option`).  Every pair of consecutive frames inside
     an item, separately for each batch entry, is scored with `temporal_metrics` (`temporal_flow`: its `flow_from`): the result gains
     'frame_ewarp' / 'frame_tof' / 'frame_valid' -- one entry per frame, None for an item's first frame -- and the report its
-    'ewarp' / 'tof' columns.  Unset, nothing is launched for it and the result is what it was."""
+    'ewarp' / 'tof' columns.  Unset, nothing is launched for it and the result is what it was.
+
+    `niqe` (with `per_frame=True` only; it raises otherwise): an `eavsr_amd.niqe.NIQE`, the file name of a pristine model, or
+    True (`opt.niqe_path`); the default is `opt.niqe_path` / EAVSR_NIQE (`niqe_option`); `niqe_crop` (default `opt.niqe_crop`, else
+    0) pixels are removed on every side.  Every SR frame of an item with HR frames is scored: the result gains 'frame_niqe' and the
+    report its 'niqe' column.  Unset, nothing is launched for it and the result is what it was."""
+    if niqe is not None and niqe is not False and not per_frame:
+        raise ValueError("evaluate: niqe needs per_frame=True (NIQE is part of the per-frame report)")
+    niqe, niqe_crop = _resolve_niqe(niqe, niqe_crop, getattr(model, "opt", None), "evaluate") if per_frame else (None, 0)
+    niqe_parts = []
     if lpips is not None and not per_frame:
         raise ValueError("evaluate: lpips needs per_frame=True (LPIPS is part of the per-frame report)")
     if temporal is False:
@@ -812,6 +917,8 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
                 frame_ssim += fs
                 if lpips is not None:
                     frame_lpips += lpips(sr.reshape(n * t, c, h, w), hr.reshape(n * t, c, h, w), 255.0).tolist()
+                if niqe is not None:
+                    niqe_parts.append((n * t, niqe.moments(sr.reshape(n * t, c, h, w), 255.0, niqe_crop)))
                 if temporal is not None:
                     vals = ({"ewarp": [], "valid": [], "tof": None} if t < 2 else
                             temporal_metrics(model.data_sr_seq.detach(), hr, temporal, 255.0, temporal_flow))
@@ -849,11 +956,15 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
         "frames_per_s": frames / seconds if seconds > 0 else math.nan,
     }
     if per_frame:
+        frame_niqe = None if niqe is None else _niqe_values(niqe, niqe_parts)
         out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
                    report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips if lpips is not None else None,
-                                       **({} if temporal is None else {"temporal": frame_temporal})))
+                                       **({} if temporal is None else {"temporal": frame_temporal}),
+                                       **({} if niqe is None else {"niqe": frame_niqe})))
         if lpips is not None:
             out["frame_lpips"] = frame_lpips
+        if niqe is not None:
+            out["frame_niqe"] = frame_niqe
         if temporal is not None:
             out.update(frame_ewarp=frame_temporal["ewarp"], frame_tof=frame_temporal["tof"], frame_valid=frame_temporal["valid"])
     return out
@@ -910,7 +1021,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
                   cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
-                  tile_overlap: Optional[int] = None, ensemble=None, temporal=None, temporal_flow: Optional[str] = None) -> Dict:
+                  tile_overlap: Optional[int] = None, ensemble=None, temporal=None, temporal_flow: Optional[str] = None, niqe=None,
+                  niqe_crop: Optional[int] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -974,7 +1086,15 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     sink sees: cropped (`pad`), blended (`tile`), averaged (`ensemble`).  The result gains 'frame_ewarp' / 'frame_tof' /
     'frame_valid', one entry per frame in (n, t) order and None for a frame without a scored predecessor, and the report (with `hr`)
     its 'ewarp' / 'tof' columns.  None: `opt.temporal` of a model wrapper, else EAVSR_TEMPORAL=hr|sr (`temporal_option`; the weights
-    then come from `opt.pwc_path`), else off: no launch and no byte differs from a run without it."""
+    then come from `opt.pwc_path`), else off: no launch and no byte differs from a run without it.
+
+    NIQE, opt-in: `niqe` -- an `eavsr_amd.niqe.NIQE`, the file name of a pristine model, or True (`opt.niqe_path`) -- scores
+    every frame the sink sees (cropped, blended, averaged, as above) without ground truth, `niqe_crop` pixels removed on every side:
+    two moment launches and one resize per chunk, the moments read back once when the forward has ended.  The result gains
+    'frame_niqe' ((n, t) order; `nan` for frames below two 96 x 96 blocks) and the report its 'niqe' column; with hr=None there is
+    a 'report' all the same, whose rows carry the names and 'niqe' only (`scene_report`).  A frame's score does not depend on
+    `frame_chunk`.  None: `opt.niqe_path` of a model wrapper, else EAVSR_NIQE=<path>, else off (`niqe_option`; `niqe_crop`:
+    `opt.niqe_crop`, else 0): no launch and no byte differs from a run without it."""
     from . import ops
     from .segments import (check_pad, check_tile, find_cuts, keep_starts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
                            tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP,
@@ -1011,6 +1131,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     device = next(net.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("super_resolve: the network must be on the GPU (eavsr_amd has no CPU path)")
+    niqe, niqe_crop = _resolve_niqe(niqe, niqe_crop, getattr(model, "opt", None), "super_resolve")      # refused before a file is read
+    niqe_parts = []
     if temporal is False:
         temporal = None
     check_temporal_flow(temporal_flow, "super_resolve: temporal_flow")
@@ -1141,6 +1263,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                 lpips_parts.append(lpips(flat, ref, 255.0).view(n, k))
         elif out_dir is not None:
             rgb8 = ops.rgb8(flat, 255.0)
+        if niqe is not None:
+            niqe_parts.append((first, k, niqe.moments(flat, 255.0, niqe_crop)))
         if temporal is not None:
             score_pairs(first, sr, ref.view(n, k, c, hh, ww) if temporal_flow == "hr" else None)
         if staging is not None:
@@ -1191,6 +1315,15 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                         row[b][at:at + len(vals[key])] = vals[key]
         frame_temporal = {key: [v for row in rows[key] for v in row] for key in rows}      # (n, t) order
         out.update(frame_ewarp=frame_temporal["ewarp"], frame_tof=frame_temporal["tof"], frame_valid=frame_temporal["valid"])
+    frame_niqe = None
+    if niqe is not None:
+        values = _niqe_values(niqe, [(n * k, m) for _, k, m in niqe_parts])      # per chunk in (n, k) order
+        rows, at = [[math.nan] * t for _ in range(n)], 0
+        for first, k, _ in niqe_parts:
+            for b in range(n):
+                rows[b][first:first + k] = values[at + b * k:at + (b + 1) * k]
+            at += n * k
+        frame_niqe = out["frame_niqe"] = [v for row in rows for v in row]      # (n, t) order
     if hr is not None:
         sse = torch.cat(sse_parts, 1).reshape(-1).tolist()      # (n, t) order, as evaluate
         frame_ssim = torch.cat(ssim_parts, 1).reshape(-1).tolist()
@@ -1199,7 +1332,11 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         frame_lpips = torch.cat(lpips_parts, 1).reshape(-1).tolist() if lpips is not None else None
         out.update(frame_psnr=frame_psnr, frame_ssim=frame_ssim, frame_names=frame_names,
                    report=scene_report(frame_names, frame_psnr, frame_ssim, frame_lpips,
-                                       **({} if frame_temporal is None else {"temporal": frame_temporal})))
+                                       **({} if frame_temporal is None else {"temporal": frame_temporal}),
+                                       **({} if frame_niqe is None else {"niqe": frame_niqe})))
         if lpips is not None:
             out["frame_lpips"] = frame_lpips
+    elif frame_niqe is not None:      # footage without ground truth: the names and the no-reference column
+        frame_names = [_frame_name(names, i, b) for b in range(n) for i in range(t)]
+        out.update(frame_names=frame_names, report=scene_report(frame_names, None, None, niqe=frame_niqe))
     return out

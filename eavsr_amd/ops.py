@@ -1560,6 +1560,108 @@ def temporal_metrics(seq: Tensor, fw: Tensor, bw: Tensor, scale: float = 255.0, 
     return err, count, epe
 
 
+# ------------------------------------------------------------------------------------------
+# NIQE, the report's no-reference column: block moments and the antialiased half-size resize  (csrc/niqe.hip)
+# ------------------------------------------------------------------------------------------
+NIQE_HALF_TILE = 32      # output columns per workgroup of eavsr_niqe_half_f64: one col_lo entry each
+
+
+def niqe_moments(src: Tensor, scale: float = 255.0, block: int = 96, crop: Optional[Tuple[int, int, int, int]] = None):
+    """The 25 moments of every `block` x `block` block of a luma plane, one launch over all frames of the call.
+    src: the (N, C, H, W) fp32 frames, C 1 or 3 -- quantised as `frame_metrics` quantises (rint(clamp(v * scale, 0, 255))) and, for
+    C = 3, turned into the integer BT.601 studio-range luma inside the kernel -- or an (N, 1, h, w) fp64 plane, read as it is (`scale`
+    is not used).  crop = (y0, x0, h, w): the plane is src[:, :, y0:y0 + h, x0:x0 + w], h and w multiples of `block` (default: the
+    largest such window from the top left).  Per block the map M = (I - mu) / (sigma + 1) of the 7-tap gaussian window
+    (`niqe.gaussian_window`; the edge of the CROPPED plane replicated) and, for M and its products with `np.roll(M, s)`, s = (0, 1),
+    (1, 0), (1, 1), (1, -1), the five numbers (n_neg, n_pos, sum v^2 over v < 0, sum v^2 over v > 0, sum |v|).
+    -> (moments fp64 (N, h / block, w / block, 25), luma fp64 (N, 1, h, w) for fp32 frames -- the cropped plane `niqe_half` reads --
+    or None for an fp64 plane), on the device.  A non-contiguous source is copied.  Fixed-order sums, no atomics: two calls on the
+    same input agree bit for bit, and a frame's numbers do not depend on the frames that share the call."""
+    from .niqe import gaussian_window
+    if not isinstance(src, torch.Tensor):
+        raise TypeError(f"niqe_moments: expected a tensor, got {type(src)}")
+    if not src.is_cuda:
+        raise RuntimeError(f"niqe_moments: tensor is on {src.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if src.dtype not in (torch.float32, torch.float64) or src.dim() != 4:
+        raise ValueError(f"niqe_moments: (N, C, H, W) fp32 frames or an (N, 1, h, w) fp64 plane, got {src.dtype} {tuple(src.shape)}")
+    f64 = src.dtype == torch.float64
+    n, c, H, W = (int(v) for v in src.shape)
+    if n < 1 or (c != 1 if f64 else c not in (1, 3)):
+        raise ValueError(f"niqe_moments: {tuple(src.shape)} {src.dtype}: N >= 1 and C = 1 or 3 (an fp64 plane: C = 1)")
+    if isinstance(block, bool) or not isinstance(block, int) or not 8 <= block <= 96:
+        raise ValueError(f"niqe_moments: block {block!r}: an int in 8..96")
+    if crop is None:
+        crop = (0, 0, H // block * block, W // block * block)
+    y0, x0, h, w = (int(v) for v in crop)
+    if min(y0, x0) < 0 or h < block or w < block or h % block or w % block or y0 + h > H or x0 + w > W:
+        raise ValueError(f"niqe_moments: crop {crop}: whole blocks of {block} (at least one) inside the {H} x {W} frame")
+    src = src if src.is_contiguous() else src.contiguous()
+    bh, bw = h // block, w // block
+    out = torch.empty((n, bh, bw, 25), device=src.device, dtype=torch.float64)
+    luma = None if f64 else torch.empty((n, 1, h, w), device=src.device, dtype=torch.float64)
+    window = (C.c_double * 7)(*gaussian_window()[0].tolist())
+    st = _stream(src)
+    px = float(n) * h * w
+    _launch("niqe_moments", px * 90.0, px * ((8.0 if f64 else 4.0 * c + 8.0)) + 200.0 * n * bh * bw, src,
+            lambda: lib().eavsr_niqe_moments(_p(src), int(f64), float(scale), n, c, H, W, y0, x0, block, bh, bw, window, _p(luma), _p(out),
+                                             st), "niqe_moments")
+    return out, luma
+
+
+class NiqeHalfTables(NamedTuple):
+    """The tables of `niqe_half` on the device (`niqe_half_tables`)"""
+    row_idx: Tensor
+    row_w: Tensor
+    col_idx: Tensor
+    col_w: Tensor
+    col_lo: Tensor
+    span: int
+
+
+def niqe_half_tables(rows, cols, device) -> NiqeHalfTables:
+    """Host tables (`niqe.resize_tables`: (idx int32 (out, taps), weight fp64 (out, taps)) per axis) -> their device copies, with
+    the first input column and the widest span of every run of NIQE_HALF_TILE output columns (what a workgroup stages)."""
+    import numpy as np
+    bundle = []
+    for name, (idx, wgt) in (("rows", rows), ("cols", cols)):
+        idx, wgt = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(wgt, np.float64)
+        if idx.ndim != 2 or idx.shape != wgt.shape or idx.shape[0] < 1 or not 1 <= idx.shape[1] <= 64:
+            raise ValueError(f"niqe_half: {name}: (idx, weight) of one (out, taps) shape with 1..64 taps, got {idx.shape} / {wgt.shape}")
+        bundle.append((idx, wgt))
+    cidx = bundle[1][0]
+    runs = [cidx[a:a + NIQE_HALF_TILE] for a in range(0, cidx.shape[0], NIQE_HALF_TILE)]
+    lo = np.array([int(r.min()) for r in runs], np.int32)
+    span = max(int(r.max()) - int(r.min()) + 1 for r in runs)
+    dev = lambda a: torch.from_numpy(a).to(device)
+    return NiqeHalfTables(dev(bundle[0][0]), dev(bundle[0][1]), dev(bundle[1][0]), dev(bundle[1][1]), dev(lo), span)
+
+
+def niqe_half(y: Tensor, tables) -> Tensor:
+    """The antialiased resize between the two scales of NIQE: y (N, 1, H, W) fp64 on the device, `tables` =
+    (rows, cols) from `niqe.resize_tables(H)` / `(W)` (or their device copies, `niqe_half_tables`) -> (N, 1, h, w) fp64.  Rows
+    (along H) first, then columns, each an fp64 accumulation in tap order; nothing is rounded or clamped between the two."""
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise RuntimeError("niqe_half: an fp64 tensor on the GPU (eavsr_amd has no CPU path)")
+    if y.dtype != torch.float64 or y.dim() != 4 or int(y.shape[1]) != 1 or int(y.shape[0]) < 1:
+        raise ValueError(f"niqe_half: an (N, 1, H, W) fp64 plane, got {y.dtype} {tuple(y.shape)}")
+    if not isinstance(tables, NiqeHalfTables):
+        tables = niqe_half_tables(tables[0], tables[1], y.device)
+    y = y if y.is_contiguous() else y.contiguous()
+    n, _, H, W = (int(v) for v in y.shape)
+    h, kr = (int(v) for v in tables.row_idx.shape)
+    w, kc = (int(v) for v in tables.col_idx.shape)
+    if tables.row_idx.device != y.device:
+        raise ValueError(f"niqe_half: tables on {tables.row_idx.device}, the plane on {y.device}")
+    if int(tables.col_lo.numel()) != -(-w // NIQE_HALF_TILE):
+        raise ValueError(f"niqe_half: {int(tables.col_lo.numel())} col_lo entries for {w} output columns")
+    out = torch.empty((n, 1, h, w), device=y.device, dtype=torch.float64)
+    st = _stream(y)
+    _launch("niqe_half", 2.0 * n * (h * W * kr + h * w * kc), 8.0 * n * (H * W + h * w), y,
+            lambda: lib().eavsr_niqe_half_f64(_p(y), _p(out), _p(tables.row_idx), _p(tables.row_w), kr, _p(tables.col_idx), _p(tables.col_w),
+                                              kc, _p(tables.col_lo), int(tables.span), n, H, W, h, w, st), "niqe_half")
+    return out
+
+
 def rgb8(sr: Tensor, scale: float = 255.0) -> Tensor:
     """sr (F, C, H, W), C 1 or 3 -> uint8 (F, H, W, C): rint(clamp(v * scale, 0, 255)) interleaved, the bytes of the frame's PNG
     scanlines (test_basic.py:85-92), without the metrics"""

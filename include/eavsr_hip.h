@@ -938,6 +938,36 @@ int eavsr_temporal_metrics_f32(const float* seq, const float* fw, const float* b
                                int32_t C, int32_t H, int32_t W, void* workspace, double* err_out, int64_t* count_out, double* epe_out,
                                void* stream);
 
+/* ---- f4: NIQE, the report's no-reference column (csrc/niqe.hip; added to ABI 32, nothing above changes) ---------------------
+ * eavsr_niqe_moments: the 25 block moments of the metric, one workgroup per block, all N frames in one launch.
+ *   src: src_f64 = 0: fp32 frames (N, C, H, W), C 1 or 3; a sample is quantised as eavsr_frame_metrics_f32 quantises,
+ *        q(p) = rint(clamp(p scale, 0, 255)), and for C = 3 turned into the BT.601 studio-range luma in integers,
+ *        16 + round_half_even((65481 R + 128553 G + 24966 B) / 255000);  src_f64 = 1: an fp64 plane (N, 1, H, W) read as it is.
+ *   The plane I is the blocks_h x blocks_w blocks of `block` x `block` samples whose top-left sample is (y0, x0) of the source.
+ *   window: 7 HOST doubles g (a symmetric window that sums to 1).  In fp64, every product and sum rounded on its own (no fused
+ *   multiply-add), taps in ascending order, the edge of I replicated:
+ *     a[y,x] = sum_k g[k] I[y, x + k - 3];  mu[y,x] = sum_k g[k] a[y + k - 3, x];  likewise e2 from I I
+ *     M = (I - mu) / (sqrt(|e2 - mu mu|) + 1)
+ *   moments (N, blocks_h, blocks_w, 25) fp64: per block, for each of the maps M, M roll(M,(0,1)), M roll(M,(1,0)), M roll(M,(1,1)),
+ *   M roll(M,(1,-1)) (numpy's roll, circular inside the block): the number of values < 0, of values > 0 (both exact), the sum of
+ *   v v over the values < 0, over the values > 0, and the sum of |v|.  Summed in a fixed order, no atomics: two calls agree bit for bit.
+ *   luma_out (nullable): (N, blocks_h block, blocks_w block) fp64, the plane I itself.
+ *   NULL src / window / moments: -1.  N outside 1..65535, C not as above, block outside 8..96 (an fp64 plane: above 80, the LDS of
+ *   a workgroup), blocks that leave the frame, pointers not 8-byte aligned: -2.
+ * eavsr_niqe_half_f64: a separable resize of fp64 planes in (N, H, W) -> out (N, h, w) from tables on the device: output row o is
+ *   sum_k row_w[o, k] in[row_idx[o, k], :] over k = 0 .. row_taps - 1 in that order, then output column likewise from the row
+ *   pass, which is not rounded to anything narrower.  row_idx (h, row_taps) int32 and row_w (h, row_taps) fp64, col_idx / col_w
+ *   (w, col_taps); col_lo (ceil(w / 32)) int32: the smallest col_idx of each run of 32 output columns; span: the largest number
+ *   of input columns such a run reads (max col_idx - col_lo + 1).  Indices outside the plane, or outside [col_lo, col_lo + span),
+ *   are clamped into it.  The tables of MATLAB's antialiased bicubic `imresize`: eavsr_amd/niqe.py resize_tables.
+ *   NULL pointer: -1.  Sizes < 1, N > 65535, taps outside 1..64, span above 2560, misaligned fp64 pointers: -2. */
+int eavsr_niqe_moments(const void* src, int32_t src_f64, float scale, int32_t N, int32_t C, int32_t H, int32_t W, int32_t y0, int32_t x0,
+                       int32_t block, int32_t blocks_h, int32_t blocks_w, const double* window, double* luma_out, double* moments,
+                       void* stream);
+int eavsr_niqe_half_f64(const double* in, double* out, const int32_t* row_idx, const double* row_w, int32_t row_taps,
+                        const int32_t* col_idx, const double* col_w, int32_t col_taps, const int32_t* col_lo, int32_t span, int32_t N,
+                        int32_t H, int32_t W, int32_t h, int32_t w, void* stream);
+
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
  * Schedules that were built, measured against the stable ones above and retired; kept because DESIGN.md / docs/history quote
