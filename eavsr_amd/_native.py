@@ -209,6 +209,10 @@ SIGNATURES = {
     # self-ensemble inference: flips / transposes of LR frames, their inverses into the accumulator (csrc/ensemble.hip; additions to ABI 32)
     "eavsr_dihedral_f32": (C.c_int, [vp, vp] + [i32] * 5 + [vp]),
     "eavsr_blend_dihedral_f32": (C.c_int, [vp] * 4 + [i32] * 10 + [i64] * 4 + [vp]),
+    # the 16-bit feature cache of the long-clip path: fp32 <-> fp16 / bf16 over a list of segments (csrc/cache16.hip; additions to ABI 32)
+    "eavsr_cache16_max_segments": (C.c_int, []),
+    "eavsr_pack16": (C.c_int, [vp, vp, vp, i32, i32, vp]),
+    "eavsr_unpack16": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
     # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)

@@ -1,0 +1,228 @@
+// The 16-bit feature cache of the long-clip path: fp32 features are rounded to fp16 or bf16 when they enter the frame
+// store (`framestore.py`) and widened when they leave it.  Two streaming kernels, each over a LIST of contiguous segments in one
+// launch (everything a time step of `propagate` fetches is widened together); no compute kernel reads 16 bits.
+//
+// pack16   -- dst16[i] = round(src32[i]), to nearest even.  fp16: the hardware convert (v_cvt_f16_f32 under the default mode:
+//             overflow to +-inf from 65520 on, subnormals produced, NaN quieted).  bf16: in integer arithmetic,
+//             (u + 0x7FFF + ((u >> 16) & 1)) >> 16, a NaN written as 0x7FC0 as torch writes it.  +-0 keep their sign.
+// unpack16 -- dst32[i] = src16[i], exact (fp16: v_cvt_f32_f16, subnormals included; bf16: the 16 bits moved up).
+//
+// A segment of n elements is cut by its 16-BIT side's address: `head` scalar elements up to the next 16-byte boundary there (0 .. 7),
+// then vectors of 8 elements -- one 16-byte access on the 16-bit side, two on the fp32 side -- then a scalar tail (0 .. 7).  The fp32
+// side of a vector is read / written by 16-, 8- or 4-byte accesses, by what its address past the head is aligned to (uniform over
+// the segment, as tile.hip's rows).  An ITEM is one vector or one scalar element, one lane each; a workgroup of 256 lanes takes
+// kUnroll x 256 consecutive items of one segment: vectors first, then head and tail elements.  Which segment a workgroup serves
+// comes from the prefix sums of the segments' workgroup counts in the kernel arguments (pointers and extents by value, at most
+// EAVSR_CACHE16_MAX_SEGMENTS; a longer list is split on the host).  Every extent is 64-bit.  The grid is capped at 2048 workgroups,
+// the rest is a grid stride.  No LDS, no atomics.
+#include "common.h"
+
+#include <stdint.h>
+
+namespace {
+
+constexpr int kMaxSeg = EAVSR_CACHE16_MAX_SEGMENTS;
+constexpr int kThreads = 256;
+constexpr int kUnroll = 4;                                 // items per lane and workgroup pass: 8 x 16-byte fp32 accesses in flight
+constexpr int64_t kBlockItems = (int64_t)kThreads * kUnroll;
+constexpr int kGridCap = 2048;                             // 256 CUs x 8 workgroups of 4 waves
+
+struct Segments {
+  const void* src[kMaxSeg];
+  void* dst[kMaxSeg];
+  int64_t n[kMaxSeg];               // elements
+  int64_t first_block[kMaxSeg + 1]; // prefix sums of the segments' workgroup passes
+  int32_t nseg;
+};
+
+// the cut of a segment whose 16-bit side starts at `p16`: [0, head) scalar, nvec vectors from head on, then n - head - 8 nvec scalar
+struct Cut {
+  int64_t head, nvec, items;
+};
+
+__host__ __device__ inline Cut cut_of(const void* p16, int64_t n) {
+  int64_t head = (int64_t)((8 - (((uintptr_t)p16 >> 1) & 7)) & 7);
+  if (head > n) head = n;
+  const int64_t nvec = (n - head) >> 3;
+  return Cut{head, nvec, n - 7 * nvec};      // nvec vectors + (n - 8 nvec) scalar elements
+}
+
+__device__ __forceinline__ int align_of(const void* p) {
+  const uintptr_t a = (uintptr_t)p;
+  return (a & 15) == 0 ? 16 : ((a & 7) == 0 ? 8 : 4);
+}
+
+__device__ __forceinline__ float4 load_quad(const float* p, int align) {
+  if (align == 16) return *reinterpret_cast<const float4*>(p);
+  if (align == 8) {
+    const float2 a = *reinterpret_cast<const float2*>(p), b = *reinterpret_cast<const float2*>(p + 2);
+    return make_float4(a.x, a.y, b.x, b.y);
+  }
+  return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+__device__ __forceinline__ void store_quad(float* p, int align, float4 v) {
+  if (align == 16) {
+    *reinterpret_cast<float4*>(p) = v;
+  } else if (align == 8) {
+    *reinterpret_cast<float2*>(p) = make_float2(v.x, v.y);
+    *reinterpret_cast<float2*>(p + 2) = make_float2(v.z, v.w);
+  } else {
+    p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
+  }
+}
+
+template <int BF16>
+__device__ __forceinline__ uint32_t round16(float x) {
+  if (BF16) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;      // NaN: torch's
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;             // nearest even; the carry out of the mantissa is the overflow to inf
+  }
+  const _Float16 h = (_Float16)x;
+  return (uint32_t)__builtin_bit_cast(uint16_t, h);
+}
+
+template <int BF16>
+__device__ __forceinline__ float widen16(uint32_t b) {
+  if (BF16) return __uint_as_float(b << 16);
+  return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
+}
+
+template <int BF16>
+__device__ __forceinline__ uint32_t round_pair(float lo, float hi) {
+  return round16<BF16>(lo) | (round16<BF16>(hi) << 16);
+}
+
+// where scalar item j (0 <= j < n - 8 nvec) of a segment lies: the head's elements, then the tail's
+__device__ __forceinline__ int64_t scalar_index(int64_t j, const Cut& c) { return j < c.head ? j : j + 8 * c.nvec; }
+
+template <int BF16>
+__global__ __launch_bounds__(kThreads) void pack16_kernel(Segments g, int64_t total_blocks) {
+  for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
+    int s = 0;
+    while (s + 1 < g.nseg && blk >= g.first_block[s + 1]) ++s;      // uniform: the segment of this pass
+    const float* src = reinterpret_cast<const float*>(g.src[s]);
+    uint16_t* dst = reinterpret_cast<uint16_t*>(g.dst[s]);
+    const int64_t n = g.n[s];
+    const Cut c = cut_of(dst, n);
+    const int align = align_of(src + c.head);
+    const int64_t base = (blk - g.first_block[s]) * kBlockItems + threadIdx.x;
+    float4 a[kUnroll], b[kUnroll];
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j) {      // every load of the pass before its first store
+      const int64_t i = base + (int64_t)j * kThreads;
+      if (i < c.nvec) {
+        const float* p = src + c.head + 8 * i;
+        a[j] = load_quad(p, align);
+        b[j] = load_quad(p + 4, align);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j) {
+      const int64_t i = base + (int64_t)j * kThreads;
+      if (i < c.nvec) {
+        uint4 v;
+        v.x = round_pair<BF16>(a[j].x, a[j].y);
+        v.y = round_pair<BF16>(a[j].z, a[j].w);
+        v.z = round_pair<BF16>(b[j].x, b[j].y);
+        v.w = round_pair<BF16>(b[j].z, b[j].w);
+        *reinterpret_cast<uint4*>(dst + c.head + 8 * i) = v;      // 16-byte aligned: what the head is for
+      } else if (i < c.items) {
+        const int64_t e = scalar_index(i - c.nvec, c);
+        dst[e] = (uint16_t)round16<BF16>(src[e]);
+      }
+    }
+  }
+}
+
+template <int BF16>
+__global__ __launch_bounds__(kThreads) void unpack16_kernel(Segments g, int64_t total_blocks) {
+  for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
+    int s = 0;
+    while (s + 1 < g.nseg && blk >= g.first_block[s + 1]) ++s;
+    const uint16_t* src = reinterpret_cast<const uint16_t*>(g.src[s]);
+    float* dst = reinterpret_cast<float*>(g.dst[s]);
+    const int64_t n = g.n[s];
+    const Cut c = cut_of(src, n);
+    const int align = align_of(dst + c.head);
+    const int64_t base = (blk - g.first_block[s]) * kBlockItems + threadIdx.x;
+    uint4 v[kUnroll];
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j) {
+      const int64_t i = base + (int64_t)j * kThreads;
+      if (i < c.nvec) v[j] = *reinterpret_cast<const uint4*>(src + c.head + 8 * i);
+    }
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j) {
+      const int64_t i = base + (int64_t)j * kThreads;
+      if (i < c.nvec) {
+        float* p = dst + c.head + 8 * i;
+        store_quad(p, align, make_float4(widen16<BF16>(v[j].x & 0xFFFFu), widen16<BF16>(v[j].x >> 16), widen16<BF16>(v[j].y & 0xFFFFu),
+                                         widen16<BF16>(v[j].y >> 16)));
+        store_quad(p + 4, align, make_float4(widen16<BF16>(v[j].z & 0xFFFFu), widen16<BF16>(v[j].z >> 16), widen16<BF16>(v[j].w & 0xFFFFu),
+                                             widen16<BF16>(v[j].w >> 16)));
+      } else if (i < c.items) {
+        const int64_t e = scalar_index(i - c.nvec, c);
+        dst[e] = widen16<BF16>(src[e]);
+      }
+    }
+  }
+}
+
+// the checked segment table of both entry points; `side16`: which list holds the 16-bit pointers (0: src, 1: dst)
+int fill(const char* who, const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype, int side16,
+         Segments& g, int64_t& total) {
+  EAVSR_REQUIRE(nseg >= 0 && nseg <= kMaxSeg, -1, "%s: %d segments (0..%d)", who, nseg, kMaxSeg);
+  EAVSR_REQUIRE(dtype == EAVSR_CACHE16_FP16 || dtype == EAVSR_CACHE16_BF16, -2, "%s: dtype %d (0: fp16, 1: bf16)", who, dtype);
+  EAVSR_REQUIRE(nseg == 0 || (src_list && dst_list && n_list), -1, "%s: NULL list", who);
+  total = 0;
+  g.nseg = nseg;
+  for (int s = 0; s < kMaxSeg; ++s) {
+    g.first_block[s] = total;
+    g.src[s] = nullptr, g.dst[s] = nullptr, g.n[s] = 0;
+    if (s >= nseg) continue;
+    const int64_t n = n_list[s];
+    EAVSR_REQUIRE(n >= 0 && n < (int64_t(1) << 60), -2, "%s: segment %d has %lld elements", who, s, (long long)n);
+    if (n == 0) continue;      // an empty segment: no pass, its pointers are never read
+    const void* p16 = side16 ? (const void*)dst_list[s] : src_list[s];
+    const void* p32 = side16 ? src_list[s] : (const void*)dst_list[s];
+    EAVSR_REQUIRE(p16 && p32, -1, "%s: segment %d: NULL pointer", who, s);
+    EAVSR_REQUIRE(((uintptr_t)p16 & 1) == 0 && ((uintptr_t)p32 & 3) == 0, -2,
+                  "%s: segment %d: the 16-bit side must be 2-byte and the fp32 side 4-byte aligned", who, s);
+    g.src[s] = src_list[s], g.dst[s] = dst_list[s], g.n[s] = n;
+    total += (cut_of(p16, n).items + kBlockItems - 1) / kBlockItems;
+  }
+  g.first_block[kMaxSeg] = total;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int eavsr_pack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype,
+                            void* stream) {
+  Segments g;
+  int64_t total;
+  if (int rc = fill("pack16", src_list, dst_list, n_list, nseg, dtype, 1, g, total)) return rc;
+  if (total == 0) return 0;
+  const dim3 grid((unsigned)(total < kGridCap ? total : kGridCap));
+  if (dtype == EAVSR_CACHE16_BF16)
+    hipLaunchKernelGGL(pack16_kernel<1>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total);
+  else
+    hipLaunchKernelGGL(pack16_kernel<0>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total);
+  return eavsr::launch_status("pack16");
+}
+
+extern "C" int eavsr_unpack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype,
+                              void* stream) {
+  Segments g;
+  int64_t total;
+  if (int rc = fill("unpack16", src_list, dst_list, n_list, nseg, dtype, 0, g, total)) return rc;
+  if (total == 0) return 0;
+  const dim3 grid((unsigned)(total < kGridCap ? total : kGridCap));
+  if (dtype == EAVSR_CACHE16_BF16)
+    hipLaunchKernelGGL(unpack16_kernel<1>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total);
+  else
+    hipLaunchKernelGGL(unpack16_kernel<0>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total);
+  return eavsr::launch_status("unpack16");
+}

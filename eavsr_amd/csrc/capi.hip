@@ -33,6 +33,7 @@ extern "C" const char* eavsr_version(void) { return "eavsr-hip 0.1.0 gfx950"; }
 extern "C" const char* eavsr_last_error(void) { return eavsr::g_err; }
 extern "C" size_t eavsr_conv2d_desc_size(void) { return sizeof(eavsr_conv2d_desc); }
 extern "C" int eavsr_lab_build(void) { return EAVSR_LAB; }
+extern "C" int eavsr_cache16_max_segments(void) { return EAVSR_CACHE16_MAX_SEGMENTS; }
 
 // ---------------------------------------------------------------------------------------------
 // MFMA layout self-test.  One wave computes D(32x32) = A(32x2) . B(2x32) with the operand map

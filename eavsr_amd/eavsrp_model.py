@@ -422,7 +422,8 @@ class EAVSRP(nn.Module):
         return self.conv_last(hr, residual=skip)                                     # :359-360
 
     # -- long clips ------------------------------------------------------------------------
-    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None, transform=None):
+    def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None, transform=None,
+                     cache_dtype=None):
         """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
 
         The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
@@ -467,12 +468,21 @@ class EAVSRP(nn.Module):
         launch -- goes through `ops.dihedral(.., k)`, and at the tail the crop is `segments.valid_region`, where the transform has
         moved the frame's samples to (a view, taken whether or not the size needed padding).  The sink, or the result, holds the
         frames in the TRANSFORMED orientation: `forward_long(g_k(<the padded window>))[valid region]`, bit for bit.  transform=None
-        or 0: today's launches and today's crop."""
+        or 0: today's launches and today's crop.
+
+        cache_dtype="fp16" / "bf16" (or the torch dtypes): the store holds the pyramid levels and the branches' outputs in
+        16 bits -- rounded to nearest even when they enter it (`ops.pack16`), widened when they leave it (`ops.unpack16`, everything a
+        time step fetches in one launch; with cache="host" on the side stream, and half the bytes cross the link).  No compute kernel
+        changes; what a step keeps in hand (the recurrence's state) is not rounded; flows and LR frames stay fp32.  The result is NOT
+        bit-identical to `forward`: it is `forward_long` on a store that returns `x.to(dtype).to(torch.float32)`, bit for bit, and the
+        same for both caches.  fp16 keeps 11 significant bits and overflows to inf above 65504; bf16 cannot overflow and keeps 8.
+        cache_dtype=None: today's stores, launches and bytes."""
         from .segments import check_pad, padded_size, valid_region
         if transform is not None and (isinstance(transform, bool) or not isinstance(transform, int) or not 0 <= transform <= 7):
             raise ValueError(f"forward_long: transform {transform!r}: a mode 0 .. 7, or None")
         transform = transform or None
         FS.check_cache(cache)
+        cache_dtype = FS.check_cache_dtype(cache_dtype)
         check_pad(pad, "forward_long: pad")
         u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_long")
         if window is not None:
@@ -499,7 +509,7 @@ class EAVSRP(nn.Module):
             ea, eb = (int(v) for v in emit)
             if not 0 <= ea < eb <= t:
                 raise ValueError(f"forward_long: emit {emit!r}: frames (a, b) with 0 <= a < b <= {t}")
-        store = FS.make_store(cache, n, t, device)
+        store = FS.make_store(cache, n, t, device) if cache_dtype is None else FS.make_store(cache, n, t, device, dtype=cache_dtype)
 
         # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
         last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
@@ -578,16 +588,18 @@ class EAVSRP(nn.Module):
         Frames of any size: `forward_segments_padded`."""
         return self.forward_segments_padded(lrs, segments, None, frame_chunk=frame_chunk, cache=cache, sink=sink)
 
-    def forward_segments_padded(self, lrs, segments, pad, frame_chunk=None, cache="device", sink=None):
+    def forward_segments_padded(self, lrs, segments, pad, frame_chunk=None, cache="device", sink=None, cache_dtype=None):
         """`forward_segments` for frames of any size: `pad` is `forward_long`'s -- "reflect" / "edge": every window is
         padded on the device while it is converted and its SR frames are cropped; None: `forward_segments` itself.  A method of its
-        own: `forward_segments` keeps the parameter list it was published with."""
+        own: `forward_segments` keeps the parameter list it was published with.  `cache_dtype` is `forward_long`'s, for
+        every window; it is also how `forward_segments` is called with a 16-bit cache (pad=None)."""
         from .segments import check_pad, check_plan
         check_pad(pad, "forward_segments_padded: pad")
+        more = _cache_dtype_kw(cache_dtype)
         _, _, _, t, _, _ = _clip_geometry(lrs, "forward_segments")
 
         def segment(part, emit, part_sink, last):
-            return self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=part_sink, emit=emit, pad=pad)
+            return self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=part_sink, emit=emit, pad=pad, **more)
         return self._over_plan(lrs, check_plan(t, segments), sink, segment)
 
     def _over_plan(self, lrs, plan, sink, segment):
@@ -611,7 +623,7 @@ class EAVSRP(nn.Module):
             del sr
         return out
 
-    def forward_tiled(self, lrs, tile, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device", sink=None):
+    def forward_tiled(self, lrs, tile, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device", sink=None, cache_dtype=None):
         """Frames of any resolution, inference only: the network runs on overlapped spatial tiles and the SR tiles are
         blended into the frame with a feathered partition of unity, so what is resident follows the tile's area, not the frame's.
 
@@ -628,9 +640,11 @@ class EAVSRP(nn.Module):
         on each hand-cropped window, bit for bit.  It is NOT the whole-frame result: flow, DCN offsets and the 120 residual blocks
         of a tile see the tile alone, and near a seam two such views are averaged.
 
-        Where one tile covers the frame the call IS `forward_long` / `forward_segments_padded`: no accumulator, no blend."""
+        Where one tile covers the frame the call IS `forward_long` / `forward_segments_padded`: no accumulator, no blend.
+        `cache_dtype` is `forward_long`'s, for every tile."""
         from .segments import check_pad, check_plan, check_tile, plan_tiles, tile_axis, tile_weights
         FS.check_cache(cache)
+        more = _cache_dtype_kw(cache_dtype)
         check_pad(pad, "forward_tiled: pad")
         u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_tiled")
         sides = check_tile(tile, "forward_tiled: tile")
@@ -641,7 +655,9 @@ class EAVSRP(nn.Module):
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
         if len(tiles) == 1:      # the untiled call: `forward_video` decides between `forward_long` and the segment plan
-            return self.forward_video(lrs, segments=segments, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            if not more:
+                return self.forward_video(lrs, segments=segments, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            return self._video(lrs, segments, None, 32, pad, frame_chunk, cache, sink, more)
         device = self._clip_device(lrs)
         s = self.scale
         rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
@@ -658,7 +674,8 @@ class EAVSRP(nn.Module):
             acc.zero_()
             for ti, (y0, y1, x0, x1) in enumerate(tiles):
                 blend = _TileBlend(acc, emit[0], s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)])
-                self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=(y0, y1, x0, x1))
+                self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=(y0, y1, x0, x1),
+                                  **more)
             if part_sink is not None:
                 fc = k if frame_chunk is None else min(int(frame_chunk), k)
                 for a in range(0, k, fc):
@@ -671,17 +688,33 @@ class EAVSRP(nn.Module):
         """The one dispatch between the inference paths (`harness.super_resolve`, `EAVSRPModel.forward`): `forward_tiled` where
         `tile` (None: untiled) cuts the frames into more than one tile, else `forward_segments_padded` where there is a segment
         plan (`segments`, as `forward_segments` takes it), else `forward_long`.  `pad`, `frame_chunk`, `cache` and `sink` are
-        handed on; so is the result."""
+        handed on; so is the result.  (With a 16-bit feature cache: `forward_cached`.)"""
+        return self._video(lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, {})
+
+    def _video(self, lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, more):
+        """`forward_video`'s dispatch; `more`: `_cache_dtype_kw(cache_dtype)`, handed on where it is set and only there"""
         from .segments import check_tile, plan_tiles
         sides = check_tile(tile, "forward_video: tile")
         if sides is not None:
             h, w = _clip_geometry(lrs, "forward_video")[4:]
             if len(plan_tiles(h, w, sides, tile_overlap)) > 1:
                 return self.forward_tiled(lrs, tile, overlap=tile_overlap, segments=segments, pad=pad, frame_chunk=frame_chunk,
-                                          cache=cache, sink=sink)
+                                          cache=cache, sink=sink, **more)
         if segments is not None:
-            return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
-        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad)
+            return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink, **more)
+        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad, **more)
+
+    def forward_cached(self, lrs, cache_dtype, ensemble=None, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None,
+                       cache="device", sink=None):
+        """`forward_ensemble` -- and through it `forward_video`, `forward_tiled`, `forward_segments_padded` and `forward_long` -- with
+        the 16-bit feature cache of `forward_long(cache_dtype=...)` in every `forward_long` call it makes.  A method of
+        its own: `forward_video`, `forward_ensemble` and `forward_segments` keep the parameter lists they were published with.
+        ensemble=None: no ensemble.  cache_dtype=None IS `forward_ensemble` / `forward_video`.  Refused before anything runs: a
+        `cache_dtype` that is not None, "fp16", "bf16" or one of the two torch dtypes."""
+        more = _cache_dtype_kw(cache_dtype)
+        if ensemble is None:
+            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, more)
+        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, more)
 
     def forward_ensemble(self, lrs, ensemble=8, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device",
                          sink=None):
@@ -703,7 +736,12 @@ class EAVSRP(nn.Module):
         differ and this is their mean, not an equivariant network.  Nothing is claimed about quality: no trained weights exist
         in this project, and the gain a published "+" row reports cannot be measured here.
 
-        A spec that is off, or the one mode 0, IS `forward_video(...)`: no accumulator, no blend."""
+        A spec that is off, or the one mode 0, IS `forward_video(...)`: no accumulator, no blend.  (With a 16-bit feature cache:
+        `forward_cached`.)"""
+        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, {})
+
+    def _ensemble(self, lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, more):
+        """`forward_ensemble`'s body; `more`: `_cache_dtype_kw(cache_dtype)`, handed on where it is set and only there"""
         from .segments import (check_ensemble, check_pad, check_plan, check_tile, ensemble_weight, plan_tiles, tile_axis,
                                tile_weights)
         import numpy as np
@@ -717,8 +755,10 @@ class EAVSRP(nn.Module):
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
         if modes is None or modes == (0,):
-            return self.forward_video(lrs, segments=segments, tile=tile, tile_overlap=overlap, pad=pad, frame_chunk=frame_chunk,
-                                      cache=cache, sink=sink)
+            if not more:
+                return self.forward_video(lrs, segments=segments, tile=tile, tile_overlap=overlap, pad=pad, frame_chunk=frame_chunk,
+                                          cache=cache, sink=sink)
+            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, more)
         device = self._clip_device(lrs)
         s = self.scale
         if len(tiles) == 1:      # the whole frame: `forward_long` without a window, every weight 1
@@ -742,7 +782,7 @@ class EAVSRP(nn.Module):
                 for mode in modes:
                     blend = _EnsembleBlend(acc, emit[0], s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)], mode)
                     self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=window,
-                                      transform=mode)
+                                      transform=mode, **more)
             if part_sink is not None:
                 fc = k if frame_chunk is None else min(int(frame_chunk), k)
                 for a in range(0, k, fc):
@@ -794,7 +834,7 @@ class EAVSRP(nn.Module):
         # `propagate`.  A chunked run asked for activations that do not grow with t and the host cache keeps a window of frames on
         # the device: both stay with the per-step form
         pred = None
-        if hoist and HOIST_PREDICTORS and store.cache == "device" and t > 1:
+        if hoist and HOIST_PREDICTORS and getattr(store, "hoists", store.cache == "device") and t > 1:
             pred = self._predict_rows(align, [store.get_range(k, 0, t) for k in _PYR], store.get_range(fkey, 0, t - 1), n, backward)
         for i, idx in enumerate(order):
             store.step(i)
@@ -834,6 +874,13 @@ class EAVSRP(nn.Module):
             store.put(module_name, idx, feat_prop)
             hist = (hist + [feat_prop])[-2:]
             store.done(i)
+
+
+def _cache_dtype_kw(cache_dtype):
+    """{} where `cache_dtype` is None -- the calls below are then today's, argument for argument -- else {'cache_dtype': "fp16" | "bf16"};
+    a bad value is refused here, before anything runs"""
+    name = FS.check_cache_dtype(cache_dtype)
+    return {} if name is None else {"cache_dtype": name}
 
 
 class _TileBlend:
@@ -938,7 +985,23 @@ def long_clip_options(opt=None):
     tile_options(opt)            # likewise: opt.tile / tile_overlap, read by EAVSRPModel.forward and harness.super_resolve
     from .segments import ensemble_options
     ensemble_options(opt)        # likewise: opt.ensemble, read by EAVSRPModel.forward and harness.super_resolve
+    cache_dtype_option(opt)      # likewise: opt.cache_dtype, read by EAVSRPModel.forward and harness.super_resolve
     return fc, cc
+
+
+def cache_dtype_option(opt=None):
+    """None, "fp16" or "bf16": what the long-clip path's frame store holds its features in (`EAVSRP.forward_long(cache_dtype=...)`,
+    DESIGN 7n) -- `opt.cache_dtype` ("fp16" / "bf16" or torch.float16 / torch.bfloat16), falling back to the environment where the
+    options do not carry it (EAVSR_CACHE_DTYPE=fp16|bf16), None -- fp32, today's stores -- where neither does.  Not among the
+    reference's options."""
+    from .segments import one_of, read_option
+
+    def from_opt(value, who):
+        try:
+            return FS.check_cache_dtype(value)
+        except ValueError:
+            raise ValueError(f"{who}={value!r}: 'fp16', 'bf16' (torch.float16 / torch.bfloat16) or None") from None
+    return read_option(opt, "cache_dtype", "EAVSR_CACHE_DTYPE", from_opt, one_of(tuple(FS.CACHE_DTYPES), "fp16 or bf16"))
 
 
 def png_encoder_option(opt=None) -> str:
@@ -976,6 +1039,11 @@ class EAVSRPModel:
         self.isTrain = getattr(opt, "isTrain", False)
         # opt.frame_chunk / opt.cpu_cache (not among the reference's options): the opt-in long-clip inference path (EAVSRP.forward_long)
         self.frame_chunk, self.cpu_cache = long_clip_options(opt)
+        # opt.cache_dtype (not among the reference's options): the frame store's features in 16 bits, outside training
+        self.cache_dtype = cache_dtype_option(opt)
+        if self.isTrain and getattr(opt, "cache_dtype", None) is not None:
+            raise ValueError("opt.cache_dtype: the 16-bit feature cache is an inference option (EAVSRP.forward_long); training keeps "
+                             "its activations for the backward pass in fp32")
         self.png_encoder = png_encoder_option(opt)
         # opt.pad_frames (not among the reference's options): frames of any size outside training (EAVSRP.forward_long(pad=...))
         from .segments import pad_option
@@ -1085,7 +1153,13 @@ class EAVSRPModel:
         start = time.time()
         long_path = not self.isTrain and (self.frame_chunk is not None or self.cpu_cache)
         cache = "host" if self.cpu_cache else "device"
-        if not self.isTrain and self.ensemble is not None:
+        if not self.isTrain and self.cache_dtype is not None:
+            # the long path on a store that holds its features in 16 bits, with whatever else is set
+            with torch.no_grad():
+                self.data_sr_seq = self.netEAVSRP.forward_cached(self.data_lr_seq, self.cache_dtype, ensemble=self.ensemble,
+                                                                 tile=self.tile, overlap=self.tile_overlap, pad=self.pad_frames,
+                                                                 frame_chunk=self.frame_chunk, cache=cache)
+        elif not self.isTrain and self.ensemble is not None:
             # the mean over flips / transposes of the frame, tiled and padded as below
             with torch.no_grad():
                 self.data_sr_seq = self.netEAVSRP.forward_ensemble(self.data_lr_seq, ensemble=self.ensemble, tile=self.tile,

@@ -91,6 +91,44 @@ def check_cache(cache: str) -> str:
     return cache
 
 
+CACHE_DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+def check_cache_dtype(x) -> Optional[str]:
+    """None (fp32 features, today's stores) | "fp16" | "bf16", also given as torch.float16 / torch.bfloat16 -> None, "fp16" or "bf16";
+    anything else is refused"""
+    if x is None:
+        return None
+    if isinstance(x, str) and x in CACHE_DTYPES:
+        return x
+    if isinstance(x, torch.dtype):
+        for name, dt in CACHE_DTYPES.items():
+            if x == dt:
+                return name
+    raise ValueError(f"cache_dtype {x!r}: None, 'fp16' or 'bf16' (torch.float16 / torch.bfloat16)")
+
+
+def is_feature_key(key: str) -> bool:
+    """what a 16-bit store rounds: the pyramid levels and every branch's outputs -- 64 channels each.  The flows (2 channels of pixel
+    offsets) and the LR frames stay fp32."""
+    return key not in FLOW_KEYS and key != "lr"
+
+
+def expected_nbytes(n: int, t: int, h: int, w: int, branches: int = 4, dtype=None, channels: int = 64) -> Dict[str, int]:
+    """`nbytes()` of a store that holds a whole clip of n x t frames of h x w, from shapes alone: per frame and clip
+    channels h w (1 + 1/4 + 1/16 + branches) feature elements of 4 bytes (2 with a 16-bit `dtype`) -- 1360 h w bytes in fp32 with four
+    branches -- plus the t - 1 flows of each direction and the LR frames at full size"""
+    size = 4 if check_cache_dtype(dtype) is None else 2
+    out = {"spatial": channels * h * w, "spatial_d2": channels * (h // 2) * (w // 2), "spatial_d4": channels * (h // 4) * (w // 4)}
+    out.update({f"{d}_{i}": channels * h * w for i in (1, 2) for d in ("backward", "forward")} if branches == 4 else
+               {f"branch_{i}": channels * h * w for i in range(branches)})
+    out = {k: v * size * n * t for k, v in out.items()}
+    out.update({k: 2 * h * w * 4 * n * (t - 1) for k in FLOW_KEYS})
+    out["lr"] = 3 * h * w * 4 * n * t
+    out["total"] = sum(out.values())
+    return out
+
+
 class DeviceStore:
     """Today's residency: every frame stays in device memory.  A range of frames put as one frame-major tensor ((k n, c, h, w),
     frame-major rows) is kept as that tensor; a frame, or an aligned range, is a contiguous slice of it."""
@@ -144,6 +182,12 @@ class DeviceStore:
     def finish(self) -> None:
         pass
 
+    def nbytes(self) -> Dict[str, int]:
+        """bytes resident per key, and their "total": what the store's own blocks hold"""
+        out = {key: sum(int(b.numel()) * b.element_size() for _, _, b in blocks) for key, blocks in self._blocks.items()}
+        out["total"] = sum(out.values())
+        return out
+
 
 class HostStore:
     """`cpu_cache`: frames in pinned host memory, a device window filled ahead of use.
@@ -167,11 +211,14 @@ class HostStore:
     def _main(self):
         return torch.cuda.current_stream(self.device)
 
+    def _held_as(self, key: str, like: Tensor) -> torch.dtype:
+        return like.dtype
+
     def _host_buffer(self, key: str, like: Tensor) -> Tensor:
         buf = self._host.get(key)
         if buf is None:
             frames = self.t - 1 if key in FLOW_KEYS else self.t
-            buf = torch.empty((max(frames, 1), self.n) + tuple(like.shape[1:]), dtype=like.dtype, pin_memory=True)
+            buf = torch.empty((max(frames, 1), self.n) + tuple(like.shape[1:]), dtype=self._held_as(key, like), pin_memory=True)
             self._host[key] = buf
         return buf
 
@@ -252,6 +299,175 @@ class HostStore:
         last.record(self.side)
         self._main().wait_event(last)
 
+    def nbytes(self) -> Dict[str, int]:
+        """bytes resident per key, and their "total": the pinned buffers (the device window is not counted)"""
+        out = {key: int(buf.numel()) * buf.element_size() for key, buf in self._host.items()}
+        out["total"] = sum(out.values())
+        return out
 
-def make_store(cache: str, n: int, t: int, device):
-    return (HostStore if check_cache(cache) == "host" else DeviceStore)(n, t, device)
+
+def _contiguous(x: Tensor) -> Tensor:
+    return x if x.is_contiguous() else x.contiguous()
+
+
+class DeviceStore16(DeviceStore):
+    """The device cache with its features held in 16 bits: `HostStore` with "host" meaning 16-bit device memory and
+    "copy" meaning a kernel.  A feature tensor (`is_feature_key`) is rounded to `dtype` when it is put (`ops.pack16`) and the step that
+    produced it keeps its fp32 tensor in hand; reads follow the schedule as the host cache's do -- everything a time step fetches is
+    widened into fp32 tensors by ONE `ops.unpack16` launch on the compute stream and dropped by `done`; `get_range` widens a range in
+    one launch.  What comes back is `x.to(dtype).to(torch.float32)`, bit for bit.  Flows and LR frames stay fp32 and are served as
+    `DeviceStore` serves them.  The hoisted predictors of a one-chunk run read every frame at once: this store keeps the per-step
+    form (`hoists`)."""
+    hoists = False
+
+    def __init__(self, n: int, t: int, device, dtype):
+        super().__init__(n, t, device)
+        self.cache_dtype = check_cache_dtype(dtype)
+        self.dtype = CACHE_DTYPES[self.cache_dtype]
+        self._window: Dict[Tuple, Tensor] = {}      # (key, frame) -> fp32 tensor
+        self._schedule: Optional[Schedule] = None
+        self.peak_window_items = 0
+
+    def _pack(self, src: Tensor, dst: Tensor) -> None:
+        from . import ops
+        ops.pack16([_contiguous(src)], [dst], self.dtype)
+
+    def put_range(self, key: str, first: int, frames: Tensor) -> None:
+        if not is_feature_key(key):
+            return super().put_range(key, first, frames)
+        if (key, first) in self._where:      # rows of a branch's buffer
+            block, j = self._where[(key, first)]
+            dst = block[j * self.n:j * self.n + int(frames.shape[0])]
+        else:
+            dst = torch.empty(frames.shape, dtype=self.dtype, device=frames.device)
+            super().put_range(key, first, dst)
+        self._pack(frames, dst)
+
+    def new_branch(self, key: str, like: Tensor) -> None:
+        super().put_range(key, 0, torch.empty((self.t * self.n,) + tuple(like.shape[1:]), dtype=self.dtype, device=like.device))
+
+    def out_slot(self, key: str, idx: int) -> Optional[Tensor]:
+        return None      # a fresh fp32 tensor per step: the step keeps it, `put` rounds it into the buffer
+
+    def put(self, key: str, idx: int, frame: Tensor) -> None:
+        self.put_range(key, idx, frame)
+
+    def _held(self, item: Item) -> Tensor:
+        return super().get(*item)
+
+    def _fetch(self, items: Sequence[Item]) -> None:
+        from . import ops
+        items = [it for it in items if is_feature_key(it[0]) and it not in self._window]
+        if not items:
+            return
+        srcs = [self._held(it) for it in items]
+        dsts = [torch.empty(s.shape, dtype=torch.float32, device=s.device) for s in srcs]
+        ops.unpack16(srcs, dsts)
+        self._window.update(zip(items, dsts))
+        self.peak_window_items = max(self.peak_window_items, len(self._window))
+
+    def begin(self, schedule: Schedule) -> None:
+        self._schedule = schedule
+        self._fetch(schedule.prologue)
+
+    def step(self, i: int) -> None:
+        self._fetch(self._schedule.fetch[i])
+
+    def done(self, i: int) -> None:
+        for it in self._schedule.evict[i]:
+            self._window.pop(it, None)
+
+    def get(self, key: str, idx: int) -> Tensor:
+        if not is_feature_key(key):
+            return super().get(key, idx)
+        return self._window[(key, idx)]
+
+    def get_range(self, key: str, a: int, b: int) -> Tensor:
+        if not is_feature_key(key):
+            return super().get_range(key, a, b)
+        from . import ops
+        for first, k, block in self._blocks[key]:
+            if first <= a and b <= first + k:
+                srcs = [block[(a - first) * self.n:(b - first) * self.n]]
+                break
+        else:
+            srcs = [self._held((key, i)) for i in range(a, b)]
+        out = torch.empty((sum(int(s.shape[0]) for s in srcs),) + tuple(srcs[0].shape[1:]), dtype=torch.float32, device=srcs[0].device)
+        rows, dsts = 0, []
+        for s in srcs:
+            dsts.append(out[rows:rows + int(s.shape[0])])
+            rows += int(s.shape[0])
+        ops.unpack16(srcs, dsts)
+        return out
+
+    def finish(self) -> None:
+        self._window.clear()
+
+
+class HostStore16(HostStore):
+    """The host cache with its features held in 16 bits: the pinned buffers of the feature keys are 16-bit, half the bytes
+    cross the link each way.  `put_range` rounds on the compute stream into a temporary 16-bit device tensor (`ops.pack16`) and copies
+    that on the side stream; `_fetch` copies 16-bit frames into staging tensors and widens all of them with ONE `ops.unpack16` launch
+    ON THE SIDE STREAM, and the event the compute stream waits on is recorded behind that launch.  Streams, events and
+    `record_stream` as `HostStore`; the host never synchronises.  The same bits as `DeviceStore16`."""
+
+    def __init__(self, n: int, t: int, device, dtype):
+        super().__init__(n, t, device)
+        self.cache_dtype = check_cache_dtype(dtype)
+        self.dtype = CACHE_DTYPES[self.cache_dtype]
+
+    def _held_as(self, key: str, like: Tensor) -> torch.dtype:
+        return self.dtype if is_feature_key(key) else like.dtype
+
+    def put_range(self, key: str, first: int, frames: Tensor) -> None:
+        if not is_feature_key(key):
+            return super().put_range(key, first, frames)
+        from . import ops
+        k = int(frames.shape[0]) // self.n
+        dst = self._host_buffer(key, frames)[first:first + k]
+        packed = torch.empty(frames.shape, dtype=self.dtype, device=frames.device)
+        ops.pack16([_contiguous(frames)], [packed], self.dtype)      # on the compute stream, behind the producer
+        ready = torch.cuda.Event()
+        ready.record(self._main())
+        self.side.wait_event(ready)
+        with torch.cuda.stream(self.side):
+            dst.view((k * self.n,) + tuple(frames.shape[1:])).copy_(packed, non_blocking=True)
+        packed.record_stream(self.side)
+
+    def _fetch(self, entries) -> None:
+        from . import ops
+        entries = [(wk, src) for wk, src in entries if wk not in self._window]
+        if not entries:
+            return
+        targets = [torch.empty(src.shape, dtype=torch.float32, device=self.device) for _, src in entries]
+        free = torch.cuda.Event()
+        free.record(self._main())
+        self.side.wait_event(free)
+        with torch.cuda.stream(self.side):
+            staged, widened = [], []
+            for (wk, src), dev in zip(entries, targets):
+                if src.dtype == torch.float32:      # a flow, LR frames: today's copy and its own event
+                    dev.copy_(src, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(self.side)
+                    self._window[wk] = [dev, ev]
+                else:      # (the staging tensor is allocated, written, read and released on the side stream alone)
+                    stage = torch.empty(src.shape, dtype=src.dtype, device=self.device)
+                    stage.copy_(src, non_blocking=True)
+                    staged.append(stage)
+                    widened.append((wk, dev))
+            if staged:
+                ops.unpack16(staged, [dev for _, dev in widened])
+                ev = torch.cuda.Event()
+                ev.record(self.side)
+                for wk, dev in widened:
+                    self._window[wk] = [dev, ev]
+        self.peak_window_items = max(self.peak_window_items, len(self._window))
+
+
+def make_store(cache: str, n: int, t: int, device, dtype=None):
+    """dtype=None: the fp32 stores.  "fp16" / "bf16" (`check_cache_dtype`): the stores that hold the feature keys in 16 bits."""
+    host = check_cache(cache) == "host"
+    if check_cache_dtype(dtype) is None:
+        return (HostStore if host else DeviceStore)(n, t, device)
+    return (HostStore16 if host else DeviceStore16)(n, t, device, dtype)

@@ -1022,7 +1022,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
                   cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
                   tile_overlap: Optional[int] = None, ensemble=None, temporal=None, temporal_flow: Optional[str] = None, niqe=None,
-                  niqe_crop: Optional[int] = None) -> Dict:
+                  niqe_crop: Optional[int] = None, cache_dtype=None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -1094,11 +1094,23 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     'frame_niqe' ((n, t) order; `nan` for frames below two 96 x 96 blocks) and the report its 'niqe' column; with hr=None there is
     a 'report' all the same, whose rows carry the names and 'niqe' only (`scene_report`).  A frame's score does not depend on
     `frame_chunk`.  None: `opt.niqe_path` of a model wrapper, else EAVSR_NIQE=<path>, else off (`niqe_option`; `niqe_crop`:
-    `opt.niqe_crop`, else 0): no launch and no byte differs from a run without it."""
+    `opt.niqe_crop`, else 0): no launch and no byte differs from a run without it.
+
+    16-bit feature cache, opt-in: `cache_dtype` = "fp16" / "bf16" (or the torch dtypes) is `forward_long`'s -- the frame
+    store holds the pyramid and the branches' outputs in 16 bits, about half the resident bytes of a window (twice the `max_frames` on
+    the same card) and half the bytes over the link with cache="host"; it composes with everything above.  The frames are NOT the
+    fp32 cache's bit for bit; which dtype is better for quality is not known here (no trained weights exist in this project).  None:
+    `opt.cache_dtype` of a model wrapper, else EAVSR_CACHE_DTYPE=fp16|bf16 (`eavsrp_model.cache_dtype_option`), else off: no launch
+    and no byte differs from a run without it.  The result carries 'cache_dtype': None, "fp16" or "bf16"."""
     from . import ops
     from .segments import (check_pad, check_tile, find_cuts, keep_starts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
                            tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP,
                            check_ensemble, ensemble_options, parse_ensemble)
+    from .framestore import check_cache_dtype
+    if cache_dtype is None:      # a bad value is refused here, before a file is read
+        from .eavsrp_model import cache_dtype_option
+        cache_dtype = cache_dtype_option(getattr(model, "opt", None))
+    cache_dtype = check_cache_dtype(cache_dtype)
     if ensemble is None:      # a bad spec is refused here, before a file is read
         modes = ensemble_options(getattr(model, "opt", None))
     elif isinstance(ensemble, str):
@@ -1292,7 +1304,10 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
             scene_bounds[:] = keep_starts(t, starts, min_scene)
-        if modes == (0,):
+        if cache_dtype is not None:
+            net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
+                               segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+        elif modes == (0,):
             net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
                               frame_chunk=frame_chunk, cache=cache, sink=sink)
         else:
@@ -1303,7 +1318,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     seconds = time.time() - t0
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
            "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
-           "segments": plan, "scene_starts": starts, "tiles": tiles, "ensemble": modes}
+           "segments": plan, "scene_starts": starts, "tiles": tiles, "ensemble": modes, "cache_dtype": cache_dtype}
     frame_temporal = None
     if temporal is not None:
         rows = {key: [[None] * t for _ in range(n)] for key in ("ewarp", "tof", "valid")}

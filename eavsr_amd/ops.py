@@ -1904,6 +1904,120 @@ def blend_dihedral(acc: Tensor, sr: Tensor, k: int, Y0: int, X0: int, wy: Tensor
     return acc
 
 
+# ------------------------------------------------------------------------------------------
+# the 16-bit feature cache of the long-clip path (csrc/cache16.hip)
+# ------------------------------------------------------------------------------------------
+CACHE16_MAX_SEGMENTS = 16      # include/eavsr_hip.h: EAVSR_CACHE16_MAX_SEGMENTS (pointers and extents by value in the kernel arguments)
+CACHE16_DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+_CACHE16_CODE = {torch.float16: 0, torch.bfloat16: 1}
+CACHE16_BLOCK_ITEMS = 1024     # csrc/cache16.hip: kThreads x kUnroll items (a vector of 8 elements, or one scalar element) per workgroup pass
+
+
+def cache16_dtype(dtype) -> torch.dtype:
+    """"fp16" | "bf16" | torch.float16 | torch.bfloat16 -> the torch dtype; anything else is refused"""
+    if isinstance(dtype, str) and dtype in CACHE16_DTYPES:
+        return CACHE16_DTYPES[dtype]
+    if isinstance(dtype, torch.dtype) and dtype in _CACHE16_CODE:
+        return dtype
+    raise ValueError(f"cache16: dtype {dtype!r}: 'fp16' or 'bf16' (torch.float16 / torch.bfloat16)")
+
+
+def cache16_batches(nseg: int, limit: int = CACHE16_MAX_SEGMENTS) -> List[Tuple[int, int]]:
+    """the launches of a list of `nseg` segments: [(a, b)] slices of at most `limit` segments, in order; an empty list: none"""
+    if nseg < 0 or limit < 1:
+        raise ValueError(f"cache16_batches: {nseg} segments in launches of {limit}")
+    return [(a, min(a + limit, nseg)) for a in range(0, nseg, limit)]
+
+
+def cache16_cut(misalign16: int, n: int) -> Tuple[int, int, int]:
+    """(head, vectors, tail) of a segment of n elements whose 16-bit side starts `misalign16` elements (0 .. 7) past a 16-byte
+    boundary -- csrc/cache16.hip's cut_of: `head` scalar elements up to the next boundary (all n where the segment ends before it),
+    vectors of 8 elements from there, the remaining 0 .. 7 elements scalar again"""
+    if not 0 <= misalign16 <= 7 or n < 0:
+        raise ValueError(f"cache16_cut: misalignment {misalign16} (0 .. 7 elements), {n} elements")
+    head = min((8 - misalign16) & 7, n)
+    nvec = (n - head) >> 3
+    return head, nvec, n - head - 8 * nvec
+
+
+def cache16_item(i: int, head: int, nvec: int, tail: int) -> Tuple[int, int]:
+    """the elements [a, b) of its segment that item i of the kernels serves: the vectors first, then the head's and the tail's elements"""
+    if i < nvec:
+        return head + 8 * i, head + 8 * i + 8
+    j = i - nvec
+    if j >= head + tail:
+        return 0, 0
+    e = j if j < head else j + 8 * nvec
+    return e, e + 1
+
+
+def cache16_passes(misalign16: int, n: int) -> int:
+    """workgroup passes the kernels spend on such a segment"""
+    head, nvec, tail = cache16_cut(misalign16, n)
+    return -(-(nvec + head + tail) // CACHE16_BLOCK_ITEMS)
+
+
+def _cache16_lists(who: str, srcs, dsts, src_dtype, dst_dtype):
+    srcs, dsts = list(srcs), list(dsts)
+    if len(srcs) != len(dsts):
+        raise ValueError(f"{who}: {len(srcs)} sources and {len(dsts)} destinations")
+    device = None
+    for i, (s, d) in enumerate(zip(srcs, dsts)):
+        for name, t, dt in (("source", s, src_dtype), ("destination", d, dst_dtype)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{who}: {name} {i}: expected a tensor, got {type(t)}")
+            if not t.is_cuda:
+                raise RuntimeError(f"{who}: {name} {i} is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+            device = t.device if device is None else device
+            if t.dtype != dt or t.device != device:
+                raise ValueError(f"{who}: {name} {i}: {dt} on {device}, got {t.dtype} on {t.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{who}: {name} {i} is not contiguous (a segment is one run of memory; it is converted in place)")
+        if s.numel() != d.numel():
+            raise ValueError(f"{who}: segment {i}: {s.numel()} source and {d.numel()} destination elements")
+    return srcs, dsts
+
+
+def _cache16_run(who: str, entry: str, srcs, dsts, code: int):
+    st = None
+    for a, b in cache16_batches(len(srcs)):
+        part = [(s, d) for s, d in zip(srcs[a:b], dsts[a:b])]
+        total = sum(s.numel() for s, _ in part)
+        if total == 0:
+            continue      # nothing but empty segments: nothing is launched
+        st = _stream(part[0][0]) if st is None else st
+        sl, dl = _ptr_array([s for s, _ in part]), _ptr_array([d for _, d in part])
+        nl = (C.c_int64 * len(part))(*[s.numel() for s, _ in part])
+        _launch(who, 0.0, 6.0 * total, part[0][0], lambda: getattr(lib(), entry)(sl, dl, nl, len(part), code, st), who)
+    return dsts
+
+
+def pack16(srcs: Sequence[Tensor], dsts: Sequence[Tensor], dtype) -> List[Tensor]:
+    """dsts[s] = srcs[s] rounded from fp32 to `dtype` ("fp16" / "bf16" or the torch dtype), for a list of contiguous segments in one
+    launch per CACHE16_MAX_SEGMENTS segments (csrc/cache16.hip).  Round to nearest even; fp16 overflows to +-inf and
+    produces subnormals; NaN stays NaN, +-0 keep their sign: bit for bit `x.to(dtype)` of the CPU for every input that is not a NaN.
+    srcs: fp32 tensors; dsts: tensors of `dtype` with the same numbers of elements, written in place; both contiguous, on one device,
+    at any element alignment (slices are taken as they are).  A segment may be empty.  Returns `dsts`."""
+    dt = cache16_dtype(dtype)
+    srcs, dsts = _cache16_lists("pack16", srcs, dsts, torch.float32, dt)
+    return _cache16_run("pack16", "eavsr_pack16", srcs, dsts, _CACHE16_CODE[dt])
+
+
+def unpack16(srcs: Sequence[Tensor], dsts: Sequence[Tensor]) -> List[Tensor]:
+    """dsts[s] = srcs[s] widened to fp32, exactly: `pack16`'s list the other way round, one launch per CACHE16_MAX_SEGMENTS segments.
+    srcs: fp16 or bf16 tensors, all of one dtype; dsts: fp32, written in place.  Returns `dsts`."""
+    srcs, dsts = list(srcs), list(dsts)
+    if not srcs:
+        if dsts:
+            raise ValueError(f"unpack16: 0 sources and {len(dsts)} destinations")
+        return dsts
+    if not isinstance(srcs[0], torch.Tensor):
+        raise TypeError(f"unpack16: source 0: expected a tensor, got {type(srcs[0])}")
+    dt = cache16_dtype(srcs[0].dtype)
+    srcs, dsts = _cache16_lists("unpack16", srcs, dsts, dt, torch.float32)
+    return _cache16_run("unpack16", "eavsr_unpack16", srcs, dsts, _CACHE16_CODE[dt])
+
+
 def frame_change(frames: Tensor, hwc: Optional[bool] = None):
     """Scene-cut statistics of uint8 frames (F, C, h, w) planes, C 1 or 3, or (F, h, w, 3) interleaved (`hwc` as `u8_to_f32`), F >= 1,
     in one launch (csrc/scene.hip) -> (hist int32 (F, 64), sad int64 (F - 1,)) on the device.  With the luma

@@ -797,6 +797,22 @@ int eavsr_dihedral_f32(const float* in, float* out, int32_t F, int32_t C, int32_
 int eavsr_blend_dihedral_f32(float* acc, const float* sr, const float* wy, const float* wx, int32_t N, int32_t F, int32_t C, int32_t SH,
                              int32_t SW, int32_t th, int32_t tw, int32_t Y0, int32_t X0, int32_t k, int64_t sn, int64_t sf, int64_t sc,
                              int64_t sy, void* stream);
+/* ---- the 16-bit feature cache of the long-clip path (csrc/cache16.hip; added to ABI 32, nothing above changes) ------------------------
+ * eavsr_pack16: dst_list[s][i] = src_list[s][i] rounded from fp32 to fp16 (dtype EAVSR_CACHE16_FP16) or bf16 (EAVSR_CACHE16_BF16), to
+ * nearest even, 0 <= i < n_list[s], for all nseg segments in ONE launch.  fp16: overflow to +-inf, subnormals produced; bf16 cannot
+ * overflow short of the rounding of values above the largest finite bf16.  NaN stays NaN (bf16: 0x7FC0), +-0 keep their sign.
+ * eavsr_unpack16: the exact widening, 16-bit src_list to fp32 dst_list, the same kind of list, one launch.
+ * A segment is contiguous; the 16-bit side 2-byte and the fp32 side 4-byte aligned (16-byte accesses are used where the addresses allow
+ * them, scalar heads and tails elsewhere).  Extents are 64-bit.  n_list[s] == 0: the segment is skipped, its pointers are not read.
+ * Source and destination must not overlap.  nseg outside 0 .. EAVSR_CACHE16_MAX_SEGMENTS or a NULL pointer: -1; a bad dtype, a
+ * negative extent or a misaligned pointer: -2.  Nothing to convert: 0, nothing is launched.
+ * eavsr_cache16_max_segments() returns EAVSR_CACHE16_MAX_SEGMENTS (pointers and extents travel by value in the kernel arguments). */
+#define EAVSR_CACHE16_MAX_SEGMENTS 16
+#define EAVSR_CACHE16_FP16 0
+#define EAVSR_CACHE16_BF16 1
+int eavsr_cache16_max_segments(void);
+int eavsr_pack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype, void* stream);
+int eavsr_unpack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype, void* stream);
 /* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
  * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
  * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
