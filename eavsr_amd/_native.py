@@ -204,9 +204,9 @@ SIGNATURES = {
     # padded ingest of frames of any size, and of a window of them: one kernel family (csrc/ingest_pad.hip; additions to ABI 32)
     "eavsr_ingest_pad": (C.c_int, [vp, vp] + [i32] * 8 + [vp]),
     "eavsr_ingest_window": (C.c_int, [vp, vp] + [i32] * 12 + [vp]),
-    # spatial tiling: weighted accumulation of SR tiles (csrc/tile.hip; addition to ABI 32)
+    # spatial tiling: weighted accumulation of SR tiles (csrc/blend.hip; addition to ABI 32)
     "eavsr_tile_blend_f32": (C.c_int, [vp] * 4 + [i32] * 9 + [i64] * 4 + [vp]),
-    # self-ensemble inference: flips / transposes of LR frames, their inverses into the accumulator (csrc/ensemble.hip; additions to ABI 32)
+    # self-ensemble inference: flips / transposes of LR frames, their inverses into the accumulator (csrc/blend.hip; additions to ABI 32)
     "eavsr_dihedral_f32": (C.c_int, [vp, vp] + [i32] * 5 + [vp]),
     "eavsr_blend_dihedral_f32": (C.c_int, [vp] * 4 + [i32] * 10 + [i64] * 4 + [vp]),
     # the 16-bit feature cache of the long-clip path: fp32 <-> fp16 / bf16 over a list of segments (csrc/cache16.hip; additions to ABI 32)

@@ -10,7 +10,7 @@
 // A segment of n elements is cut by its 16-BIT side's address: `head` scalar elements up to the next 16-byte boundary there (0 .. 7),
 // then vectors of 8 elements -- one 16-byte access on the 16-bit side, two on the fp32 side -- then a scalar tail (0 .. 7).  The fp32
 // side of a vector is read / written by 16-, 8- or 4-byte accesses, by what its address past the head is aligned to (uniform over
-// the segment, as tile.hip's rows).  An ITEM is one vector or one scalar element, one lane each; a workgroup of 256 lanes takes
+// the segment, as blend.hip's rows).  An ITEM is one vector or one scalar element, one lane each; a workgroup of 256 lanes takes
 // kUnroll x 256 consecutive items of one segment: vectors first, then head and tail elements.  Which segment a workgroup serves
 // comes from the prefix sums of the segments' workgroup counts in the kernel arguments (pointers and extents by value, at most
 // EAVSR_CACHE16_MAX_SEGMENTS; a longer list is split on the host).  Every extent is 64-bit.  The grid is capped at 2048 workgroups,

@@ -26,7 +26,7 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// grid.x of the row-streaming kernels (ingest_pad.hip, tile.hip): groups of `per_group` rows per plane, capped as ingest.hip's
+// grid.x of the row-streaming kernels (ingest_pad.hip, blend.hip): groups of `per_group` rows per plane, capped as ingest.hip's
 // blocks_for caps its grid -- about 2048 workgroups in all (256 CUs x 8 workgroups of 4 waves), the rest is a grid-stride loop
 inline unsigned row_blocks(uint32_t rows, int per_group, size_t planes) {
   const size_t want = ((size_t)rows + per_group - 1) / per_group;

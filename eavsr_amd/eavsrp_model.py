@@ -595,11 +595,12 @@ class EAVSRP(nn.Module):
         every window; it is also how `forward_segments` is called with a 16-bit cache (pad=None)."""
         from .segments import check_pad, check_plan
         check_pad(pad, "forward_segments_padded: pad")
-        more = _cache_dtype_kw(cache_dtype)
+        cache_dtype = FS.check_cache_dtype(cache_dtype)
         _, _, _, t, _, _ = _clip_geometry(lrs, "forward_segments")
 
         def segment(part, emit, part_sink, last):
-            return self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=part_sink, emit=emit, pad=pad, **more)
+            return self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=part_sink, emit=emit, pad=pad,
+                                     cache_dtype=cache_dtype)
         return self._over_plan(lrs, check_plan(t, segments), sink, segment)
 
     def _over_plan(self, lrs, plan, sink, segment):
@@ -642,9 +643,9 @@ class EAVSRP(nn.Module):
 
         Where one tile covers the frame the call IS `forward_long` / `forward_segments_padded`: no accumulator, no blend.
         `cache_dtype` is `forward_long`'s, for every tile."""
-        from .segments import check_pad, check_plan, check_tile, plan_tiles, tile_axis, tile_weights
+        from .segments import check_pad, check_plan, check_tile, plan_tiles, tile_axis
         FS.check_cache(cache)
-        more = _cache_dtype_kw(cache_dtype)
+        cache_dtype = FS.check_cache_dtype(cache_dtype)
         check_pad(pad, "forward_tiled: pad")
         u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_tiled")
         sides = check_tile(tile, "forward_tiled: tile")
@@ -654,28 +655,38 @@ class EAVSRP(nn.Module):
         if frame_chunk is not None and int(frame_chunk) < 1:
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
-        if len(tiles) == 1:      # the untiled call: `forward_video` decides between `forward_long` and the segment plan
-            if not more:
-                return self.forward_video(lrs, segments=segments, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
-            return self._video(lrs, segments, None, 32, pad, frame_chunk, cache, sink, more)
+        if len(tiles) == 1:      # the untiled call: `_video` decides between `forward_long` and the segment plan
+            return self._video(lrs, segments, None, 32, pad, frame_chunk, cache, sink, cache_dtype)
+        rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
+        return self._blended("forward_tiled", lrs, (0,), tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype)
+
+    def _blended(self, who, lrs, modes, tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype):
+        """The accumulator loop of `forward_tiled` (modes = (0,)) and `forward_ensemble`, which have checked every argument: `tiles` in
+        `plan_tiles` order over the windows `rows` x `cols` of the two axes (one tile: the frame, read without a window; its
+        weights are 1), `plan` a checked segment plan.  Per segment the window of frames is uploaded once, the accumulator view is
+        zeroed, `forward_long` runs per tile and, inside a tile, per mode in increasing order with a `_Blend` sink, and the
+        accumulator is drained to `sink` in `frame_chunk` pieces."""
+        from .segments import ensemble_weight, tile_weights
+        _, _, n, _, h, w = _clip_geometry(lrs, who)
         device = self._clip_device(lrs)
         s = self.scale
-        rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
-        wy = torch.from_numpy(tile_weights(h, rows, s)).to(device)      # (rows of tiles, s th): row i serves every tile of row i
+        # (rows of tiles, s th): row i serves every tile of row i.  wy' = fp32(wy * weight), rounded once, on the host; one mode: x 1
+        wy = torch.from_numpy(tile_weights(h, rows, s) * ensemble_weight(modes)).to(device)
         wx = torch.from_numpy(tile_weights(w, cols, s)).to(device)
         per_frame = 3 * s * h * s * w
         store = torch.empty(n * max(eb - ea for _, _, ea, eb in plan) * per_frame, device=device, dtype=torch.float32)
 
         def segment(part, emit, part_sink, last):
             if not part.is_cuda:
-                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile reads it on the device
+                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile and mode reads it on the device
             k = emit[1] - emit[0]
             acc = store[:n * k * per_frame].view(n, k, 3, s * h, s * w)
             acc.zero_()
-            for ti, (y0, y1, x0, x1) in enumerate(tiles):
-                blend = _TileBlend(acc, emit[0], s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)])
-                self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=(y0, y1, x0, x1),
-                                  **more)
+            for ti, window in enumerate(tiles):
+                for mode in modes:
+                    blend = _Blend(acc, emit[0], mode, s * window[0], s * window[2], wy[ti // len(cols)], wx[ti % len(cols)])
+                    self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad,
+                                      window=window if len(tiles) > 1 else None, transform=mode, cache_dtype=cache_dtype)
             if part_sink is not None:
                 fc = k if frame_chunk is None else min(int(frame_chunk), k)
                 for a in range(0, k, fc):
@@ -689,20 +700,21 @@ class EAVSRP(nn.Module):
         `tile` (None: untiled) cuts the frames into more than one tile, else `forward_segments_padded` where there is a segment
         plan (`segments`, as `forward_segments` takes it), else `forward_long`.  `pad`, `frame_chunk`, `cache` and `sink` are
         handed on; so is the result.  (With a 16-bit feature cache: `forward_cached`.)"""
-        return self._video(lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, {})
+        return self._video(lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, None)
 
-    def _video(self, lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, more):
-        """`forward_video`'s dispatch; `more`: `_cache_dtype_kw(cache_dtype)`, handed on where it is set and only there"""
+    def _video(self, lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, cache_dtype):
+        """`forward_video`'s dispatch, with `forward_long`'s `cache_dtype` for whichever path is taken"""
         from .segments import check_tile, plan_tiles
         sides = check_tile(tile, "forward_video: tile")
         if sides is not None:
             h, w = _clip_geometry(lrs, "forward_video")[4:]
             if len(plan_tiles(h, w, sides, tile_overlap)) > 1:
                 return self.forward_tiled(lrs, tile, overlap=tile_overlap, segments=segments, pad=pad, frame_chunk=frame_chunk,
-                                          cache=cache, sink=sink, **more)
+                                          cache=cache, sink=sink, cache_dtype=cache_dtype)
         if segments is not None:
-            return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink, **more)
-        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad, **more)
+            return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink,
+                                                cache_dtype=cache_dtype)
+        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad, cache_dtype=cache_dtype)
 
     def forward_cached(self, lrs, cache_dtype, ensemble=None, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None,
                        cache="device", sink=None):
@@ -711,10 +723,10 @@ class EAVSRP(nn.Module):
         its own: `forward_video`, `forward_ensemble` and `forward_segments` keep the parameter lists they were published with.
         ensemble=None: no ensemble.  cache_dtype=None IS `forward_ensemble` / `forward_video`.  Refused before anything runs: a
         `cache_dtype` that is not None, "fp16", "bf16" or one of the two torch dtypes."""
-        more = _cache_dtype_kw(cache_dtype)
+        cache_dtype = FS.check_cache_dtype(cache_dtype)
         if ensemble is None:
-            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, more)
-        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, more)
+            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, cache_dtype)
+        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, cache_dtype)
 
     def forward_ensemble(self, lrs, ensemble=8, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device",
                          sink=None):
@@ -738,13 +750,11 @@ class EAVSRP(nn.Module):
 
         A spec that is off, or the one mode 0, IS `forward_video(...)`: no accumulator, no blend.  (With a 16-bit feature cache:
         `forward_cached`.)"""
-        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, {})
+        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, None)
 
-    def _ensemble(self, lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, more):
-        """`forward_ensemble`'s body; `more`: `_cache_dtype_kw(cache_dtype)`, handed on where it is set and only there"""
-        from .segments import (check_ensemble, check_pad, check_plan, check_tile, ensemble_weight, plan_tiles, tile_axis,
-                               tile_weights)
-        import numpy as np
+    def _ensemble(self, lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, cache_dtype):
+        """`forward_ensemble`'s body, with `forward_long`'s `cache_dtype` (checked by the caller) for every call it makes"""
+        from .segments import check_ensemble, check_pad, check_plan, check_tile, plan_tiles, tile_axis
         modes = check_ensemble(ensemble, "forward_ensemble: ensemble")      # refused before anything runs
         FS.check_cache(cache)
         check_pad(pad, "forward_ensemble: pad")
@@ -754,42 +764,13 @@ class EAVSRP(nn.Module):
         if frame_chunk is not None and int(frame_chunk) < 1:
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
-        if modes is None or modes == (0,):
-            if not more:
-                return self.forward_video(lrs, segments=segments, tile=tile, tile_overlap=overlap, pad=pad, frame_chunk=frame_chunk,
-                                          cache=cache, sink=sink)
-            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, more)
-        device = self._clip_device(lrs)
-        s = self.scale
-        if len(tiles) == 1:      # the whole frame: `forward_long` without a window, every weight 1
-            cols, windows = [(0, w)], [None]
-            wy, wx = np.ones((1, s * h), np.float32), np.ones((1, s * w), np.float32)
+        if modes is None or modes == (0,):      # off: no accumulator, no blend
+            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, cache_dtype)
+        if len(tiles) == 1:      # the whole frame (no tile, or one that covers it): one window per axis
+            rows, cols = [(0, h)], [(0, w)]
         else:
-            rows, cols, windows = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap), tiles
-            wy, wx = tile_weights(h, rows, s), tile_weights(w, cols, s)
-        wy = torch.from_numpy(wy * ensemble_weight(modes)).to(device)      # fp32 x fp32, rounded once: wy'
-        wx = torch.from_numpy(wx).to(device)
-        per_frame = 3 * s * h * s * w
-        store = torch.empty(n * max(eb - ea for _, _, ea, eb in plan) * per_frame, device=device, dtype=torch.float32)
-
-        def segment(part, emit, part_sink, last):
-            if not part.is_cuda:
-                part = part.to(device, non_blocking=True)      # once per segment, as bytes: every tile and mode reads it on the device
-            k = emit[1] - emit[0]
-            acc = store[:n * k * per_frame].view(n, k, 3, s * h, s * w)
-            acc.zero_()
-            for ti, ((y0, _, x0, _), window) in enumerate(zip(tiles, windows)):
-                for mode in modes:
-                    blend = _EnsembleBlend(acc, emit[0], s * y0, s * x0, wy[ti // len(cols)], wx[ti % len(cols)], mode)
-                    self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad, window=window,
-                                      transform=mode, **more)
-            if part_sink is not None:
-                fc = k if frame_chunk is None else min(int(frame_chunk), k)
-                for a in range(0, k, fc):
-                    chunk = acc[:, a:a + fc]
-                    part_sink(emit[0] + a, chunk.contiguous() if last else chunk.clone())
-            return acc
-        return self._over_plan(lrs, plan, sink, segment)
+            rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
+        return self._blended("forward_ensemble", lrs, modes, tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype)
 
     def _clip_device(self, lrs):
         """the device a clip runs on: its own, or the network's for 8-bit frames in host memory; anything but a GPU is refused"""
@@ -876,40 +857,16 @@ class EAVSRP(nn.Module):
             store.done(i)
 
 
-def _cache_dtype_kw(cache_dtype):
-    """{} where `cache_dtype` is None -- the calls below are then today's, argument for argument -- else {'cache_dtype': "fp16" | "bf16"};
-    a bad value is refused here, before anything runs"""
-    name = FS.check_cache_dtype(cache_dtype)
-    return {} if name is None else {"cache_dtype": name}
-
-
-class _TileBlend:
-    """`forward_tiled`'s sink: adds every SR chunk of one tile, as the view `forward_long` holds, to the accumulator"""
+class _Blend:
+    """`EAVSRP._blended`'s sink: adds every SR chunk of one tile, as the view `forward_long` holds and in the orientation of mode k, to
+    the accumulator -- inv_k on the load (`ops.blend_dihedral`; k = 0 is `ops.tile_blend`'s launch)"""
     takes_views = True
 
-    def __init__(self, acc, first, Y0, X0, wy, wx):
-        self.acc, self.first, self.Y0, self.X0, self.wy, self.wx = acc, first, Y0, X0, wy, wx
+    def __init__(self, acc, first, k, Y0, X0, wy, wx):
+        self.acc, self.first, self.k, self.Y0, self.X0, self.wy, self.wx = acc, first, k, Y0, X0, wy, wx
 
     def __call__(self, first_frame, sr):
         a = first_frame - self.first      # the chunk's first frame among the emitted ones
-        b = a + int(sr.shape[1])
-        n = int(self.acc.shape[0])
-        if n == 1 or (a == 0 and b == int(self.acc.shape[1])):
-            ops.tile_blend(self.acc[:, a:b], sr, self.Y0, self.X0, self.wy, self.wx)
-        else:      # frames a .. b of several clips are not one contiguous block: clip by clip
-            for i in range(n):
-                ops.tile_blend(self.acc[i:i + 1, a:b], sr[i:i + 1], self.Y0, self.X0, self.wy, self.wx)
-
-
-class _EnsembleBlend(_TileBlend):
-    """`forward_ensemble`'s sink: `_TileBlend` for SR chunks that arrive under mode k -- inv_k on the load (`ops.blend_dihedral`)"""
-
-    def __init__(self, acc, first, Y0, X0, wy, wx, k):
-        super().__init__(acc, first, Y0, X0, wy, wx)
-        self.k = k
-
-    def __call__(self, first_frame, sr):
-        a = first_frame - self.first
         b = a + int(sr.shape[1])
         n = int(self.acc.shape[0])
         if n == 1 or (a == 0 and b == int(self.acc.shape[1])):

@@ -1779,48 +1779,60 @@ def ingest_window(frames: Tensor, y0: int, x0: int, wh: int, ww: int, H: Optiona
     return _ingest_frames("ingest_window", frames, (y0, x0, wh, ww), H, W, mode, hwc)
 
 
+def _blend(who: str, acc: Tensor, sr: Tensor, k: int, Y0: int, X0: int, wy: Tensor, wx: Tensor) -> Tensor:
+    """The body of `tile_blend` (k = 0) and `blend_dihedral` (k = 1 .. 7): the checks under the caller's name and the one launch of
+    csrc/blend.hip's kernels."""
+    for name, t in (("acc", acc), ("sr", sr), ("wy", wy), ("wx", wx)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a tensor, got {type(t)}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+        if t.dtype != torch.float32 or t.device != acc.device:
+            raise ValueError(f"{who}: {name}: fp32 on {acc.device}, got {t.dtype} on {t.device}")
+    if acc.dim() != 5 or sr.dim() != 5 or not acc.is_contiguous():
+        either = "," if k == 0 else " -- (n, F, C, tw, th) for a transposed mode --"
+        raise ValueError(f"{who}: acc is a contiguous (n, F, C, SH, SW) tensor and sr (n, F, C, th, tw){either} got {tuple(acc.shape)} "
+                         f"(contiguous: {acc.is_contiguous()}) and {tuple(sr.shape)}")
+    n, f, c, SH, SW = (int(v) for v in acc.shape)
+    rows, row = int(sr.shape[3]), int(sr.shape[4])      # of the source; the tile as acc sees it is th x tw
+    th, tw = (row, rows) if k & 4 else (rows, row)
+    if tuple(sr.shape[:3]) != (n, f, c):
+        raise ValueError(f"{who}: sr holds {tuple(sr.shape[:3])} (n, F, C) planes, acc {(n, f, c)}")
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (Y0, X0)):
+        raise ValueError(f"{who}: Y0, X0 {Y0!r}, {X0!r}: integers")
+    if n * f > 0 and (c < 1 or th < 1 or tw < 1):
+        raise ValueError(f"{who}: an empty tile {tuple(sr.shape)}")
+    if Y0 < 0 or X0 < 0 or Y0 + th > SH or X0 + tw > SW:
+        raise ValueError(f"{who}: the tile [{Y0}, {Y0 + th}) x [{X0}, {X0 + tw}) does not lie inside frames of {SH} x {SW}")
+    if tuple(wy.shape) != (th,) or tuple(wx.shape) != (tw,) or not wy.is_contiguous() or not wx.is_contiguous():
+        raise ValueError(f"{who}: wy, wx are contiguous ({th},) and ({tw},) tensors, got {tuple(wy.shape)} and {tuple(wx.shape)}")
+    sn, sf, sc, sy, sx = (int(v) for v in sr.stride())
+    sn, sf, sc = (0 if d == 1 else v for d, v in zip((n, f, c), (sn, sf, sc)))      # the stride of a dimension of 1 is never used
+    if (row > 1 and sx != 1) or min(sn, sf, sc, sy) < 0 or (rows > 1 and sy < row):
+        raise ValueError(f"{who}: sr has unit stride along {'x' if k == 0 else 'its rows'} and non-negative strides elsewhere, "
+                         f"got {tuple(sr.stride())}")
+    if n * f > 65535 or c > 65535:
+        raise ValueError(f"{who}: n F={n * f}, C={c}: at most 65535 each (grid dimensions)")
+    if n * f == 0:
+        return acc
+    st = _stream(acc)
+    if k == 0:
+        fn = lambda: lib().eavsr_tile_blend_f32(_p(acc), _p(sr), _p(wy), _p(wx), n, f, c, SH, SW, th, tw, Y0, X0, sn, sf, sc, max(sy, row), st)
+    else:
+        fn = lambda: lib().eavsr_blend_dihedral_f32(_p(acc), _p(sr), _p(wy), _p(wx), n, f, c, SH, SW, th, tw, Y0, X0, k, sn, sf, sc,
+                                                    max(sy, row), st)
+    _launch(who, 3.0 * sr.numel(), 12.0 * sr.numel(), acc, fn, who)
+    return acc
+
+
 def tile_blend(acc: Tensor, sr: Tensor, Y0: int, X0: int, wy: Tensor, wx: Tensor) -> Tensor:
-    """acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * sr[n, f, c, y, x], in place, one launch (csrc/tile.hip): three
+    """acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * sr[n, f, c, y, x], in place, one launch (csrc/blend.hip): three
     separately rounded fp32 operations in that order, never a fused multiply-add -- bit for bit what numpy computes.  `acc`: a
     contiguous fp32 (n, F, C, SH, SW); `sr`: fp32 (n, F, C, th, tw) with any non-negative strides on n, f, c and rows and unit stride
     along x (the transposed, cropped view `forward_long` holds is taken as it is, not copied); `wy` (th,), `wx` (tw,): contiguous fp32
     rows of `segments.tile_weights` on the device.  Plain stores: tiles that overlap are blended one after another on one stream.
     Returns `acc`."""
-    for name, t in (("acc", acc), ("sr", sr), ("wy", wy), ("wx", wx)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"tile_blend: {name}: expected a tensor, got {type(t)}")
-        if not t.is_cuda:
-            raise RuntimeError(f"tile_blend: {name} is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
-        if t.dtype != torch.float32 or t.device != acc.device:
-            raise ValueError(f"tile_blend: {name}: fp32 on {acc.device}, got {t.dtype} on {t.device}")
-    if acc.dim() != 5 or sr.dim() != 5 or not acc.is_contiguous():
-        raise ValueError(f"tile_blend: acc is a contiguous (n, F, C, SH, SW) tensor and sr (n, F, C, th, tw), got {tuple(acc.shape)} "
-                         f"(contiguous: {acc.is_contiguous()}) and {tuple(sr.shape)}")
-    n, f, c, SH, SW = (int(v) for v in acc.shape)
-    th, tw = int(sr.shape[3]), int(sr.shape[4])
-    if tuple(sr.shape[:3]) != (n, f, c):
-        raise ValueError(f"tile_blend: sr holds {tuple(sr.shape[:3])} (n, F, C) planes, acc {(n, f, c)}")
-    if any(isinstance(v, bool) or not isinstance(v, int) for v in (Y0, X0)):
-        raise ValueError(f"tile_blend: Y0, X0 {Y0!r}, {X0!r}: integers")
-    if n * f > 0 and (c < 1 or th < 1 or tw < 1):
-        raise ValueError(f"tile_blend: an empty tile {tuple(sr.shape)}")
-    if Y0 < 0 or X0 < 0 or Y0 + th > SH or X0 + tw > SW:
-        raise ValueError(f"tile_blend: the tile [{Y0}, {Y0 + th}) x [{X0}, {X0 + tw}) does not lie inside frames of {SH} x {SW}")
-    if tuple(wy.shape) != (th,) or tuple(wx.shape) != (tw,) or not wy.is_contiguous() or not wx.is_contiguous():
-        raise ValueError(f"tile_blend: wy, wx are contiguous ({th},) and ({tw},) tensors, got {tuple(wy.shape)} and {tuple(wx.shape)}")
-    sn, sf, sc, sy, sx = (int(v) for v in sr.stride())
-    sn, sf, sc = (0 if d == 1 else v for d, v in zip((n, f, c), (sn, sf, sc)))      # the stride of a dimension of 1 is never used
-    if (tw > 1 and sx != 1) or min(sn, sf, sc, sy) < 0 or (th > 1 and sy < tw):
-        raise ValueError(f"tile_blend: sr has unit stride along x and non-negative strides elsewhere, got {tuple(sr.stride())}")
-    if n * f > 65535 or c > 65535:
-        raise ValueError(f"tile_blend: n F={n * f}, C={c}: at most 65535 each (grid dimensions)")
-    if n * f == 0:
-        return acc
-    st = _stream(acc)
-    _launch("tile_blend", 3.0 * sr.numel(), 12.0 * sr.numel(), acc,
-            lambda: lib().eavsr_tile_blend_f32(_p(acc), _p(sr), _p(wy), _p(wx), n, f, c, SH, SW, th, tw, Y0, X0, sn, sf, sc, max(sy, tw), st),
-            "tile_blend")
-    return acc
+    return _blend("tile_blend", acc, sr, 0, Y0, X0, wy, wx)
 
 
 def _dihedral_mode(who: str, k) -> int:
@@ -1831,7 +1843,7 @@ def _dihedral_mode(who: str, k) -> int:
 
 def dihedral(x: Tensor, k: int) -> Tensor:
     """g_k(x): fp32 (F, C, H, W) frames under one of the eight flips / transposes of the plane, a new contiguous tensor, one launch
-    (csrc/ensemble.hip).  Mode k: bit 0 hflip, bit 1 vflip, bit 2 transpose, applied in that order on the last two axes
+    (csrc/blend.hip).  Mode k: bit 0 hflip, bit 1 vflip, bit 2 transpose, applied in that order on the last two axes
     (`dataset.py`'s augmentation flags); a transposed mode returns (F, C, W, H).  The 32 bits of every sample are copied.  F == 0:
     an empty tensor, nothing is launched."""
     if not isinstance(x, torch.Tensor):
@@ -1856,52 +1868,14 @@ def dihedral(x: Tensor, k: int) -> Tensor:
 
 
 def blend_dihedral(acc: Tensor, sr: Tensor, k: int, Y0: int, X0: int, wy: Tensor, wx: Tensor) -> Tensor:
-    """acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * inv_k(sr)[n, f, c, y, x], in place, one launch (csrc/ensemble.hip, DESIGN
+    """acc[n, f, c, Y0 + y, X0 + x] += (wy[y] * wx[x]) * inv_k(sr)[n, f, c, y, x], in place, one launch (csrc/blend.hip, DESIGN
     7k): `tile_blend` with the inverse of `dihedral`'s mode k on the load -- the same three separately rounded fp32 operations,
     bit for bit what numpy computes.  `acc`: a contiguous fp32 (n, F, C, SH, SW); `sr`: fp32 (n, F, C, th, tw) or, for a transposed
     mode, (n, F, C, tw, th), with any non-negative strides on n, f, c and rows and unit stride along its rows (the cropped,
     transposed view `forward_long` holds is taken as it is); `wy` (th,), `wx` (tw,): contiguous fp32 on the device.  Plain stores:
     calls that overlap are ordered on one stream.  k == 0 is `tile_blend`, the existing launch.  Returns `acc`."""
     k = _dihedral_mode("blend_dihedral", k)
-    if k == 0:
-        return tile_blend(acc, sr, Y0, X0, wy, wx)
-    for name, t in (("acc", acc), ("sr", sr), ("wy", wy), ("wx", wx)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"blend_dihedral: {name}: expected a tensor, got {type(t)}")
-        if not t.is_cuda:
-            raise RuntimeError(f"blend_dihedral: {name} is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
-        if t.dtype != torch.float32 or t.device != acc.device:
-            raise ValueError(f"blend_dihedral: {name}: fp32 on {acc.device}, got {t.dtype} on {t.device}")
-    if acc.dim() != 5 or sr.dim() != 5 or not acc.is_contiguous():
-        raise ValueError(f"blend_dihedral: acc is a contiguous (n, F, C, SH, SW) tensor and sr (n, F, C, th, tw) -- (n, F, C, tw, th) "
-                         f"for a transposed mode -- got {tuple(acc.shape)} (contiguous: {acc.is_contiguous()}) and {tuple(sr.shape)}")
-    n, f, c, SH, SW = (int(v) for v in acc.shape)
-    rows, row = int(sr.shape[3]), int(sr.shape[4])      # of the source; the tile as acc sees it is th x tw
-    th, tw = (row, rows) if k & 4 else (rows, row)
-    if tuple(sr.shape[:3]) != (n, f, c):
-        raise ValueError(f"blend_dihedral: sr holds {tuple(sr.shape[:3])} (n, F, C) planes, acc {(n, f, c)}")
-    if any(isinstance(v, bool) or not isinstance(v, int) for v in (Y0, X0)):
-        raise ValueError(f"blend_dihedral: Y0, X0 {Y0!r}, {X0!r}: integers")
-    if n * f > 0 and (c < 1 or th < 1 or tw < 1):
-        raise ValueError(f"blend_dihedral: an empty tile {tuple(sr.shape)}")
-    if Y0 < 0 or X0 < 0 or Y0 + th > SH or X0 + tw > SW:
-        raise ValueError(f"blend_dihedral: the tile [{Y0}, {Y0 + th}) x [{X0}, {X0 + tw}) does not lie inside frames of {SH} x {SW}")
-    if tuple(wy.shape) != (th,) or tuple(wx.shape) != (tw,) or not wy.is_contiguous() or not wx.is_contiguous():
-        raise ValueError(f"blend_dihedral: wy, wx are contiguous ({th},) and ({tw},) tensors, got {tuple(wy.shape)} and {tuple(wx.shape)}")
-    sn, sf, sc, sy, sx = (int(v) for v in sr.stride())
-    sn, sf, sc = (0 if d == 1 else v for d, v in zip((n, f, c), (sn, sf, sc)))      # the stride of a dimension of 1 is never used
-    if (row > 1 and sx != 1) or min(sn, sf, sc, sy) < 0 or (rows > 1 and sy < row):
-        raise ValueError(f"blend_dihedral: sr has unit stride along its rows and non-negative strides elsewhere, got {tuple(sr.stride())}")
-    if n * f > 65535 or c > 65535:
-        raise ValueError(f"blend_dihedral: n F={n * f}, C={c}: at most 65535 each (grid dimensions)")
-    if n * f == 0:
-        return acc
-    st = _stream(acc)
-    _launch("blend_dihedral", 3.0 * sr.numel(), 12.0 * sr.numel(), acc,
-            lambda: lib().eavsr_blend_dihedral_f32(_p(acc), _p(sr), _p(wy), _p(wx), n, f, c, SH, SW, th, tw, Y0, X0, k, sn, sf, sc,
-                                                   max(sy, row), st),
-            "blend_dihedral")
-    return acc
+    return _blend("blend_dihedral" if k else "tile_blend", acc, sr, k, Y0, X0, wy, wx)
 
 
 # ------------------------------------------------------------------------------------------

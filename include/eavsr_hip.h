@@ -757,7 +757,7 @@ int eavsr_u8_to_f32(const uint8_t* in, float* out, int32_t F, int32_t C, int32_t
  * NULL pointer: -1; H < h, W < w, bad kind / mode / dims, F > 65535, C > 65535, a misaligned out: -2.  F == 0: 0, nothing is launched. */
 int eavsr_ingest_pad(const void* in, float* out, int32_t F, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, int32_t kind,
                      int32_t mode, void* stream);
-/* ---- spatial tiling: frames of any resolution (csrc/ingest_pad.hip, csrc/tile.hip; added to ABI 32, nothing above changes) ------------
+/* ---- spatial tiling: frames of any resolution (csrc/ingest_pad.hip, csrc/blend.hip; added to ABI 32, nothing above changes) ------------
  * eavsr_ingest_window is eavsr_ingest_pad, the same kernels, reading the window [y0, y0 + wh) x [x0, x0 + ww) of frames of h x w,
  * addressed with the frames' own pitch (no copy of the slice):
  *     out[f, c, y, x] = conv(in[f, c, y0 + r(y, wh), x0 + r(x, ww)]),   out fp32 (F, C, H, W), H >= wh, W >= ww
@@ -777,7 +777,7 @@ int eavsr_ingest_window(const void* in, float* out, int32_t F, int32_t C, int32_
 int eavsr_tile_blend_f32(float* acc, const float* sr, const float* wy, const float* wx, int32_t N, int32_t F, int32_t C, int32_t SH,
                          int32_t SW, int32_t th, int32_t tw, int32_t Y0, int32_t X0, int64_t sn, int64_t sf, int64_t sc, int64_t sy,
                          void* stream);
-/* ---- self-ensemble inference: flips and transposes in, their inverses out (csrc/ensemble.hip; added to ABI 32, nothing above changes) ----
+/* ---- self-ensemble inference: flips and transposes in, their inverses out (csrc/blend.hip; added to ABI 32, nothing above changes) ----
  * Mode k in 0 .. 7: bit 0 hflip, bit 1 vflip, bit 2 transpose, applied in that order on the last two axes (the flags of
  * eavsr_gather_pairs_u8 below):
  *     g_k(x)[i, j]   = x[vflip ? H-1-r : r][hflip ? W-1-q : q],   (r, q) = (j, i) if transposed, else (i, j)

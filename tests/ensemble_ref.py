@@ -1,6 +1,6 @@
 """Self-ensemble inference restated with numpy, nothing of eavsr_amd imported: the eight modes (`g`, `inv`), where the
 frame's samples lie after padding and transforming (`valid_region`), the blend with its three separately rounded float32 steps
-(`blend_oracle`, `ensemble_blend`), and the address arithmetic of csrc/ensemble.hip's four kernels, workgroup by workgroup and lane by
+(`blend_oracle`, `ensemble_blend`), and the address arithmetic of csrc/blend.hip's four kernels, workgroup by workgroup and lane by
 lane (`dihedral_transcription`, `blend_dihedral_transcription`): every load asserts that it lies inside its source and that a wide
 load is aligned, every store that it lies inside its destination and is aligned; the dihedral stores each sample exactly once."""
 import numpy as np
@@ -76,7 +76,7 @@ def _reversed_words(q):
 
 
 def dihedral_transcription(x, k, bases=(0, 0), grid_x=None):
-    """csrc/ensemble.hip's two dihedral kernels on x float32 (F, C, H, W); `bases`: the byte addresses of in and out (multiples of 4)
+    """csrc/blend.hip's two dihedral kernels on x float32 (F, C, H, W); `bases`: the byte addresses of in and out (multiples of 4)
     -> (g_k(x) as the kernel writes it, {access width: count})"""
     x = np.ascontiguousarray(x, dtype=F32)
     F, C, H, W = x.shape
@@ -146,14 +146,15 @@ def dihedral_transcription(x, k, bases=(0, 0), grid_x=None):
 
 
 def blend_dihedral_transcription(acc, sr_store, sr_offset, sr_shape, sr_strides, k, Y0, X0, wy, wx, bases=(0, 0, 0, 0), grid_x=None):
-    """csrc/ensemble.hip's two blend kernels (k in 1 .. 7): acc float32 (n, F, C, SH, SW) contiguous; the source is the strided view of
-    the flat float32 array `sr_store` that starts `sr_offset` elements in, with `sr_shape` (n, F, C, rows, row) -- (tw, th) for a
-    transposed mode -- and element strides `sr_strides` (n, f, c, rows; unit along a row); wy (th,), wx (tw,).  `bases`: the byte
-    addresses of acc, sr_store, wy, wx.  -> (the new acc, {access width: count})"""
+    """csrc/blend.hip's two blend kernels (k in 0 .. 7; 0 is the tile blend): acc float32 (n, F, C, SH, SW) contiguous; the source is the
+    strided view of the flat float32 array `sr_store` that starts `sr_offset` elements in, with `sr_shape` (n, F, C, rows, row) --
+    (tw, th) for a transposed mode -- and element strides `sr_strides` (n, f, c, rows; unit along a row); wy (th,), wx (tw,).
+    `bases`: the byte addresses of acc, sr_store, wy, wx (multiples of 4).  -> (the new acc, {access width: how many accesses the
+    QUADS of the rows kernel made at it}; the single words of a row's tail, of wy and of the transposing kernel are not counted)"""
     n, F, C, SH, SW = acc.shape
     rows_s, row_s = sr_shape[3:]
     th, tw = (row_s, rows_s) if k & 4 else (rows_s, row_s)
-    assert 1 <= k <= 7 and tuple(sr_shape[:3]) == (n, F, C) and 0 <= Y0 and 0 <= X0 and Y0 + th <= SH and X0 + tw <= SW
+    assert 0 <= k <= 7 and tuple(sr_shape[:3]) == (n, F, C) and 0 <= Y0 and 0 <= X0 and Y0 + th <= SH and X0 + tw <= SW
     assert wy.shape == (th,) and wx.shape == (tw,)
     sn, sf, sc, sy = sr_strides
     assert all(b % 4 == 0 for b in bases) and min(sn, sf, sc) >= 0 and sy >= row_s
@@ -166,7 +167,6 @@ def blend_dihedral_transcription(acc, sr_store, sr_offset, sr_shape, sr_strides,
         return F32(a + F32(F32(wyv * wxv) * v))
 
     def word(mem, addr):
-        widths[4] += 1
         return f32(mem.load(addr, 4, 4))[0]
 
     for bz in range(n * F):

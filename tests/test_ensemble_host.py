@@ -141,7 +141,7 @@ def test_dihedral_address_arithmetic_is_numpy_slicing(k):
 
 
 @pytest.mark.parametrize("X0", [0, 1, 2, 3])
-@pytest.mark.parametrize("k", range(1, 8))
+@pytest.mark.parametrize("k", MODES)
 def test_blend_dihedral_address_arithmetic_is_numpy(k, X0):
     """a strided (frame-major, cropped) source into 2 x 2 x 2 x 30 x 84; tiles of 10 x 16, 10 x 18 (a quad tail of 2) and 9 x 70 (two LDS
     tiles along one axis, a tail on both); acc, source and weights at every alignment class; everything outside the tile untouched"""
@@ -195,9 +195,9 @@ def test_entry_points_are_declared_in_the_stable_section_and_bound():
             assert (t is N.vp) == ("*" in a), (a, t)
             assert (t is N.i32) == a.startswith("int32_t"), (a, t)
             assert (t is N.i64) == a.startswith("int64_t"), (a, t)
-    assert any(p.endswith(os.sep + "ensemble.hip") for p in build.sources()) and any(p.endswith("ensemble.hip") for p in build.sources(lab=True))
+    assert any(p.endswith(os.sep + "blend.hip") for p in build.sources()) and any(p.endswith("blend.hip") for p in build.sources(lab=True))
     assert callable(ops.dihedral) and callable(ops.blend_dihedral)
-    with open(os.path.join(ROOT, "eavsr_amd", "csrc", "ensemble.hip")) as f:
+    with open(os.path.join(ROOT, "eavsr_amd", "csrc", "blend.hip")) as f:
         source = f.read()
     assert "fp contract(off)" in source and "atomic" not in source.lower()
     with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
@@ -268,15 +268,96 @@ def test_the_published_parameter_lists():
 
 
 def test_an_ensemble_that_is_off_is_forward_video():
-    """`forward_ensemble` with `forward_video` replaced by a recorder: 1, None and (0,) hand everything on, nothing else is touched"""
+    """the three methods `forward_video` chooses between replaced by recorders: `forward_ensemble` with 1, None and (0,) makes the call
+    `forward_video` makes with the same arguments -- the same method, the same arguments -- and touches nothing else"""
     from eavsr_amd.eavsrp_model import EAVSRP
     net = EAVSRP.__new__(EAVSRP)
     calls = []
-    net.__dict__["forward_video"] = lambda *a, **k: calls.append((a, k)) or "forward_video"
+    for name in ("forward_long", "forward_segments_padded", "forward_tiled"):
+        net.__dict__[name] = lambda *a, _n=name, **k: calls.append((_n, a, k)) or _n
     x = torch.zeros(1, 4, 3, 96, 112)
     plan = [(0, 3, 0, 2), (1, 4, 2, 4)]
     with torch.no_grad():
-        for spec in (1, None, (0,), [0]):
+        for tile, segments, path in ((64, plan, "forward_tiled"), (64, None, "forward_tiled"), (128, plan, "forward_segments_padded"),
+                                     (None, plan, "forward_segments_padded"), (128, None, "forward_long"), (None, None, "forward_long")):
             calls.clear()
-            assert net.forward_ensemble(x, spec, tile=64, overlap=16, segments=plan, pad="edge", frame_chunk=2, cache="host") == "forward_video"
-            assert calls == [((x,), dict(segments=plan, tile=64, tile_overlap=16, pad="edge", frame_chunk=2, cache="host", sink=None))]
+            assert net.forward_video(x, segments=segments, tile=tile, tile_overlap=16, pad="edge", frame_chunk=2, cache="host") == path
+            want = list(calls)
+            assert len(want) == 1 and want[0][0] == path and want[0][1][0] is x
+            for spec in (1, None, (0,), [0]):
+                calls.clear()
+                assert net.forward_ensemble(x, spec, tile=tile, overlap=16, segments=segments, pad="edge", frame_chunk=2, cache="host") == path
+                assert calls == want
+        calls.clear()
+        assert net.forward_ensemble(x, 1, tile=64, overlap=16, segments=plan, pad="edge", frame_chunk=2, cache="host") == "forward_tiled"
+    assert calls ==[("forward_tiled", (x, 64), dict(overlap=16, segments=plan, pad="edge", frame_chunk=2, cache="host", sink=None,
+                                                     cache_dtype=None))]
+
+
+# ------------------------------------------------------------------------------------------------------------- the shared loop
+def _fake_clip_run(net, calls, blends):
+    """`forward_long` and `ops.blend_dihedral` as recorders on a bare network whose clips "run" on the CPU: the first records the
+    arguments that decide what it computes and feeds its sink one zero chunk of the shape the real call emits; the second records
+    where, under which mode and with which weights that chunk is blended"""
+    def forward_long(lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None, transform=None, cache_dtype=None):
+        calls.append(dict(frames=int(lrs.shape[1]), window=window, emit=emit, pad=pad, transform=transform or None,      # 0 is None
+                          cache_dtype=cache_dtype, frame_chunk=frame_chunk, cache=cache))
+        y0, y1, x0, x1 = window or (0, int(lrs.shape[2]), 0, int(lrs.shape[3]))
+        th, tw = net.scale * (y1 - y0), net.scale * (x1 - x0)
+        sink(emit[0], torch.zeros((int(lrs.shape[0]), emit[1] - emit[0], 3) + ((tw, th) if (transform or 0) & 4 else (th, tw))))
+
+    def blend(acc, sr, k, Y0, X0, wy, wx):
+        blends.append((tuple(acc.shape), tuple(sr.shape), k, Y0, X0, wy.numpy().tobytes(), wx.numpy().tobytes()))
+    net.__dict__["forward_long"] = forward_long
+    net.__dict__["_clip_device"] = lambda lrs: torch.device("cpu")
+    return blend
+
+
+@pytest.mark.parametrize("plan", [None, [(0, 2, 0, 1), (0, 2, 1, 2)]])
+def test_the_tiled_and_the_ensemble_path_run_one_accumulator_loop(plan, monkeypatch):
+    """1 x 2 x 96 x 112 x 3 bytes, tile 64 at overlap 16 (2 x 2 tiles), one segment and a plan of two: `forward_tiled`,
+    `forward_ensemble((0, 5))` on the same tiles and the untiled `forward_ensemble((0, 5))` call `forward_long` tile-major, modes in
+    increasing order inside a tile, with exactly the window, emit, pad, transform, cache_dtype, frame_chunk and cache that the plan
+    gives; each SR chunk is blended at the tile's place with the tile's rows of `tile_weights`, wy scaled by fp32(1 / modes) on the
+    host; the sink gets the accumulator in `frame_chunk` pieces -- copies while a segment is still to come, views after the last"""
+    from eavsr_amd import ops
+    from eavsr_amd.eavsrp_model import EAVSRP
+    net = EAVSRP.__new__(EAVSRP)
+    net.__dict__["scale"] = s = 4
+    calls, blends, sunk = [], [], []
+    monkeypatch.setattr(ops, "blend_dihedral", _fake_clip_run(net, calls, blends))
+    clip = torch.zeros(1, 2, 96, 112, 3, dtype=torch.uint8)
+    h, w, t = 96, 112, 2
+    tiles = S.plan_tiles(h, w, 64, 16)
+    rows, cols = S.tile_axis(h, 64, 16), S.tile_axis(w, 64, 16)
+    assert len(tiles) == 4 and len(cols) == 2
+    segs = plan or [(0, t, 0, t)]
+    sink = lambda first, chunk: sunk.append((first, tuple(chunk.shape), chunk.untyped_storage().data_ptr()))
+    common = dict(segments=plan, pad="reflect", frame_chunk=1, cache="host", sink=sink)
+    runs = (("tiled", (0,), tiles, rows, cols, "bf16", lambda: net.forward_tiled(clip, 64, overlap=16, cache_dtype="bf16", **common)),
+            ("ensemble, tiled", (0, 5), tiles, rows, cols, None, lambda: net.forward_ensemble(clip, (5, 0), tile=64, overlap=16, **common)),
+            ("ensemble, tiled, 16-bit cache", (0, 5), tiles, rows, cols, "fp16",
+             lambda: net.forward_cached(clip, torch.float16, ensemble=(0, 5), tile=64, overlap=16, **common)),
+            ("ensemble", (0, 5), [None], [(0, h)], [(0, w)], None, lambda: net.forward_ensemble(clip, (0, 5), **common)))
+    for name, modes, windows, rows_, cols_, cache_dtype, run in runs:
+        calls.clear(), blends.clear(), sunk.clear()
+        with torch.no_grad():
+            assert run() is None, name
+        wy = (S.tile_weights(h, rows_, s) * S.ensemble_weight(modes)).astype(np.float32)
+        wx = S.tile_weights(w, cols_, s)
+        want_calls, want_blends = [], []
+        for a, b, ea, eb in segs:
+            for ti, window in enumerate(windows):
+                y0, y1, x0, x1 = window or (0, h, 0, w)
+                for k in modes:
+                    want_calls.append(dict(frames=b - a, window=window, emit=(ea - a, eb - a), pad="reflect", transform=k or None,
+                                           cache_dtype=cache_dtype, frame_chunk=1, cache="host"))
+                    th, tw = s * (y1 - y0), s * (x1 - x0)
+                    want_blends.append(((1, eb - ea, 3, s * h, s * w), (1, eb - ea, 3) + ((tw, th) if k & 4 else (th, tw)), k, s * y0, s * x0,
+                                        wy[ti // len(cols_)].tobytes(), wx[ti % len(cols_)].tobytes()))
+        assert calls == want_calls, name
+        assert blends == want_blends, name
+        assert [(first, shape) for first, shape, _ in sunk] == [(f, (1, 1, 3, s * h, s * w)) for f in range(t)], name
+        # two segments: frame 0 leaves as a copy, segment 1 zeroes and refills the accumulator; one: both chunks are views of it
+        assert (sunk[0][2] == sunk[1][2]) == (plan is None), name
+    assert S.ensemble_weight((0,)) == np.float32(1) and S.ensemble_weight((0, 5)) == np.float32(0.5)

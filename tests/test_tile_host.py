@@ -190,9 +190,9 @@ def test_entry_points_are_declared_in_the_stable_section_and_bound():
             assert (t is N.vp) == ("*" in a), (a, t)
             assert (t is N.i32) == a.startswith("int32_t"), (a, t)
             assert (t is N.i64) == a.startswith("int64_t"), (a, t)
-    assert any(p.endswith(os.sep + "tile.hip") for p in build.sources()) and any(p.endswith("tile.hip") for p in build.sources(lab=True))
+    assert any(p.endswith(os.sep + "blend.hip") for p in build.sources()) and any(p.endswith("blend.hip") for p in build.sources(lab=True))
     assert callable(ops.ingest_window) and callable(ops.tile_blend)
-    with open(os.path.join(ROOT, "eavsr_amd", "csrc", "tile.hip")) as f:
+    with open(os.path.join(ROOT, "eavsr_amd", "csrc", "blend.hip")) as f:
         source = f.read()
     assert "fp contract(off)" in source and "atomic" not in source.lower()
 
@@ -289,28 +289,29 @@ def test_forward_video_chooses_one_of_the_four_paths():
     u8_hwc = torch.zeros(1, 4, 96, 112, 3, dtype=torch.uint8)
     plan = [(0, 3, 0, 2), (1, 4, 2, 4)]
     common = dict(frame_chunk=2, cache="host", sink=None)
+    handed = dict(common, cache_dtype=None)      # what each of the four is called with: `forward_video` has no 16-bit cache
     with torch.no_grad():
         for lrs in (x, u8_hwc):
             calls.clear()
             assert net.forward_video(lrs, pad="edge", **common) == "forward_long"
-            assert calls == [("forward_long", (lrs,), dict(common, pad="edge"))]
+            assert calls == [("forward_long", (lrs,), dict(handed, pad="edge"))]
             calls.clear()
             assert net.forward_video(lrs, segments=plan, pad="edge", **common) == "forward_segments_padded"
-            assert calls == [("forward_segments_padded", (lrs, plan, "edge"), common)]
+            assert calls == [("forward_segments_padded", (lrs, plan, "edge"), handed)]
             calls.clear()      # one segment is still a plan: its frames go through the segment path
             assert net.forward_video(lrs, segments=[(0, 4, 0, 4)], **common) == "forward_segments_padded"
-            assert calls == [("forward_segments_padded", (lrs, [(0, 4, 0, 4)], None), common)]
+            assert calls == [("forward_segments_padded", (lrs, [(0, 4, 0, 4)], None), handed)]
             for tile, segments in ((64, None), ((64, 112), plan), ((96, 64), None)):      # 2 x 2, 2 x 1 and 1 x 2 tiles
                 calls.clear()
                 assert net.forward_video(lrs, segments=segments, tile=tile, tile_overlap=16, pad="reflect", **common) == "forward_tiled"
-                assert calls == [("forward_tiled", (lrs, tile), dict(common, overlap=16, segments=segments, pad="reflect"))]
+                assert calls == [("forward_tiled", (lrs, tile), dict(handed, overlap=16, segments=segments, pad="reflect"))]
             for tile in (128, (96, 112)):      # one tile
                 calls.clear()
                 assert net.forward_video(lrs, segments=plan, tile=tile, **common) == "forward_segments_padded"
-                assert calls == [("forward_segments_padded", (lrs, plan, None), common)]
+                assert calls == [("forward_segments_padded", (lrs, plan, None), handed)]
                 calls.clear()
                 assert net.forward_video(lrs, tile=tile, **common) == "forward_long"
-                assert calls == [("forward_long", (lrs,), dict(common, pad=None))]
+                assert calls == [("forward_long", (lrs,), dict(handed, pad=None))]
         calls.clear()
         for tile, overlap in ((66, 0), (64, 33), ((64, 32), 0)):      # refused here, before any of the four is called
             with pytest.raises(ValueError, match="tile|overlap"):

@@ -225,54 +225,7 @@ def ingest_window_transcription(x, y0, x0, wh, ww, H, W, mode, kind, base=0, gri
 
 
 def tile_blend_transcription(acc, sr_store, sr_offset, sr_shape, sr_strides, Y0, X0, wy, wx, bases=(0, 0, 0, 0), grid_x=None):
-    """csrc/tile.hip's blend kernel: acc float32 (n, F, C, SH, SW) contiguous; the tile is the strided view of the flat float32
-    array `sr_store` that starts `sr_offset` elements in, with `sr_shape` (n, F, C, th, tw) and element strides `sr_strides`
-    (n, f, c, rows; unit along x); wy (th,), wx (tw,).  `bases`: the byte addresses of acc, sr_store, wy, wx (multiples of 4).
-    -> (the new acc, [accesses of 16, 8 and 4 bytes])"""
-    n, F, C, SH, SW = acc.shape
-    th, tw = sr_shape[3:]
-    assert tuple(sr_shape[:3]) == (n, F, C) and 0 <= Y0 and 0 <= X0 and Y0 + th <= SH and X0 + tw <= SW
-    sn, sf, sc, sy = sr_strides
-    assert all(b % 4 == 0 for b in bases) and min(sn, sf, sc) >= 0 and sy >= tw
-    A, S, WY, WX = (Memory(a, b, 4) for a, b in zip((acc, sr_store, wy, wx), bases))
-    widths = {16: 0, 8: 0, 4: 0}
-
-    def align_of(addr):
-        return 16 if addr % 16 == 0 else (8 if addr % 8 == 0 else 4)
-
-    def load_quad(mem, addr, align):
-        widths[align] += 16 // align
-        return np.frombuffer(b"".join(mem.load(addr + k, align, align) for k in range(0, 16, align)), F32)
-
-    def blend(a, wyv, wxv, v):
-        return F32(a + F32(F32(wyv * wxv) * v))
-
-    gx = row_blocks(th, n * F * C) if grid_x is None else grid_x
-    for bz in range(n * F):
-        nn, f = bz // F, bz % F
-        for by in range(C):
-            plane = bz * C + by
-            dst = bases[0] + 4 * ((plane * SH + Y0) * SW + X0)
-            src = bases[1] + 4 * (sr_offset + nn * sn + f * sf + by * sc)
-            for bx in range(gx):
-                for ty in range(ROWS):
-                    y = bx * ROWS + ty
-                    while y < th:
-                        arow, srow = dst + 4 * y * SW, src + 4 * y * sy
-                        wyv = np.frombuffer(WY.load(bases[2] + 4 * y, 4, 4), F32)[0]
-                        a_al, s_al, w_al = align_of(arow), align_of(srow), align_of(bases[3])
-                        for xv in range(tw // 4):
-                            x = 4 * xv
-                            a = load_quad(A, arow + 4 * x, a_al)
-                            v = load_quad(S, srow + 4 * x, s_al)
-                            w = load_quad(WX, bases[3] + 4 * x, w_al)
-                            res = np.array([blend(a[j], wyv, w[j], v[j]) for j in range(4)], F32).tobytes()
-                            for k in range(0, 16, a_al):
-                                A.store(arow + 4 * x + k, res[k:k + a_al], a_al)
-                        for x in range(4 * (tw // 4), tw):      # lanes 0 .. tw % 4 - 1
-                            a = np.frombuffer(A.load(arow + 4 * x, 4, 4), F32)[0]
-                            v = np.frombuffer(S.load(srow + 4 * x, 4, 4), F32)[0]
-                            w = np.frombuffer(WX.load(bases[3] + 4 * x, 4, 4), F32)[0]
-                            A.store(arow + 4 * x, blend(a, wyv, w, v).tobytes(), 4)
-                        y += gx * ROWS
-    return A.array(F32, acc.shape), widths
+    """csrc/blend.hip's rows kernel with both flips off: `ensemble_ref.blend_dihedral_transcription` at k = 0 (which see; that module
+    imports this one, hence the import here)"""
+    from tests.ensemble_ref import blend_dihedral_transcription
+    return blend_dihedral_transcription(acc, sr_store, sr_offset, sr_shape, sr_strides, 0, Y0, X0, wy, wx, bases=bases, grid_x=grid_x)
