@@ -213,6 +213,7 @@ SIGNATURES = {
     "eavsr_cache16_max_segments": (C.c_int, []),
     "eavsr_pack16": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     "eavsr_unpack16": (C.c_int, [vp, vp, vp, i32, i32, vp]),
+    "eavsr_pack16_census": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),      # pack16 + the five counts of what the rounding did
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
     # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)

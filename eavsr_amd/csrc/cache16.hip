@@ -14,8 +14,15 @@
 // kUnroll x 256 consecutive items of one segment: vectors first, then head and tail elements.  Which segment a workgroup serves
 // comes from the prefix sums of the segments' workgroup counts in the kernel arguments (pointers and extents by value, at most
 // EAVSR_CACHE16_MAX_SEGMENTS; a longer list is split on the host).  Every extent is 64-bit.  The grid is capped at 2048 workgroups,
-// the rest is a grid stride.  No LDS, no atomics.
+// the rest is a grid stride.  pack16 and unpack16: No LDS, no atomics.
+//
+// pack16_census -- pack16 (the same segment table, cut, accesses and 16-bit result: one body, `pack_passes`, with a compile-time
+//             switch) that also counts what the rounding did into a record of five 64-bit words: the largest finite |x|, the
+//             non-finite inputs, the overflows to +-inf, the flushes to +-0 and the subnormal results.  The definitions, the lane's
+//             registers and the one reduction per workgroup (cross-lane moves, a few words of LDS, one update per non-zero slot) are
+//             cache16_census.h's; with the switch off nothing of it is compiled and pack16 is the kernel it was.
 #include "common.h"
+#include "cache16_census.h"
 
 #include <stdint.h>
 
@@ -89,16 +96,25 @@ __device__ __forceinline__ float widen16(uint32_t b) {
   return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
 }
 
-template <int BF16>
-__device__ __forceinline__ uint32_t round_pair(float lo, float hi) {
-  return round16<BF16>(lo) | (round16<BF16>(hi) << 16);
-}
-
 // where scalar item j (0 <= j < n - 8 nvec) of a segment lies: the head's elements, then the tail's
 __device__ __forceinline__ int64_t scalar_index(int64_t j, const Cut& c) { return j < c.head ? j : j + 8 * c.nvec; }
 
-template <int BF16>
-__global__ __launch_bounds__(kThreads) void pack16_kernel(Segments g, int64_t total_blocks) {
+// round16, and with CENSUS the element's entry in the lane's tally
+template <int BF16, int CENSUS>
+__device__ __forceinline__ uint32_t round_count(float x, census16::Tally& tally) {
+  const uint32_t o = round16<BF16>(x);
+  if (CENSUS) tally.count<BF16>(__float_as_uint(x), o);
+  return o;
+}
+
+template <int BF16, int CENSUS>
+__device__ __forceinline__ uint32_t round_pair(float lo, float hi, census16::Tally& tally) {
+  return round_count<BF16, CENSUS>(lo, tally) | (round_count<BF16, CENSUS>(hi, tally) << 16);
+}
+
+// every pass of one workgroup: the body of both pack kernels (CENSUS 0: `tally` is never touched)
+template <int BF16, int CENSUS>
+__device__ __forceinline__ void pack_passes(const Segments& g, int64_t total_blocks, census16::Tally& tally) {
   for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
     int s = 0;
     while (s + 1 < g.nseg && blk >= g.first_block[s + 1]) ++s;      // uniform: the segment of this pass
@@ -123,17 +139,33 @@ __global__ __launch_bounds__(kThreads) void pack16_kernel(Segments g, int64_t to
       const int64_t i = base + (int64_t)j * kThreads;
       if (i < c.nvec) {
         uint4 v;
-        v.x = round_pair<BF16>(a[j].x, a[j].y);
-        v.y = round_pair<BF16>(a[j].z, a[j].w);
-        v.z = round_pair<BF16>(b[j].x, b[j].y);
-        v.w = round_pair<BF16>(b[j].z, b[j].w);
+        v.x = round_pair<BF16, CENSUS>(a[j].x, a[j].y, tally);
+        v.y = round_pair<BF16, CENSUS>(a[j].z, a[j].w, tally);
+        v.z = round_pair<BF16, CENSUS>(b[j].x, b[j].y, tally);
+        v.w = round_pair<BF16, CENSUS>(b[j].z, b[j].w, tally);
         *reinterpret_cast<uint4*>(dst + c.head + 8 * i) = v;      // 16-byte aligned: what the head is for
       } else if (i < c.items) {
         const int64_t e = scalar_index(i - c.nvec, c);
-        dst[e] = (uint16_t)round16<BF16>(src[e]);
+        dst[e] = (uint16_t)round_count<BF16, CENSUS>(src[e], tally);
       }
     }
   }
+}
+
+template <int BF16>
+__global__ __launch_bounds__(kThreads) void pack16_kernel(Segments g, int64_t total_blocks) {
+  census16::Tally unused;
+  pack_passes<BF16, 0>(g, total_blocks, unused);
+}
+
+// pack16 + the census: `record` is five 64-bit words in device memory that the kernel adds into (the caller zeroes them)
+template <int BF16>
+__global__ __launch_bounds__(kThreads) void pack16_census_kernel(Segments g, int64_t total_blocks, unsigned long long* record) {
+  static_assert(kThreads == 64 * census16::kWaves, "the census reduction is written for this workgroup");
+  census16::Tally tally;
+  tally.clear();
+  pack_passes<BF16, 1>(g, total_blocks, tally);
+  tally.commit(record);      // every lane, after the grid stride: a workgroup without a pass adds nothing
 }
 
 template <int BF16>
@@ -211,6 +243,23 @@ extern "C" int eavsr_pack16(const void* const* src_list, void* const* dst_list, 
   else
     hipLaunchKernelGGL(pack16_kernel<0>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total);
   return eavsr::launch_status("pack16");
+}
+
+extern "C" int eavsr_pack16_census(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype,
+                                   uint64_t* census, void* stream) {
+  EAVSR_REQUIRE(census != nullptr, -1, "pack16_census: NULL census");
+  EAVSR_REQUIRE(((uintptr_t)census & 7) == 0, -2, "pack16_census: the census must be 8-byte aligned");
+  Segments g;
+  int64_t total;
+  if (int rc = fill("pack16_census", src_list, dst_list, n_list, nseg, dtype, 1, g, total)) return rc;
+  if (total == 0) return 0;
+  const dim3 grid((unsigned)(total < kGridCap ? total : kGridCap));
+  unsigned long long* record = reinterpret_cast<unsigned long long*>(census);
+  if (dtype == EAVSR_CACHE16_BF16)
+    hipLaunchKernelGGL(pack16_census_kernel<1>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total, record);
+  else
+    hipLaunchKernelGGL(pack16_census_kernel<0>, grid, dim3(kThreads), 0, eavsr::as_stream(stream), g, total, record);
+  return eavsr::launch_status("pack16_census");
 }
 
 extern "C" int eavsr_unpack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype,

@@ -204,6 +204,8 @@ class EAVSRP(nn.Module):
         self.scale = int(scale if scale is not None else getattr(opt, "scale", 4))
         if self.scale not in (2, 4):
             raise NotImplementedError("EAVSRP exists for x4 (eavsrp_model) and x2 (eavsrpx2_model)")
+        # one entry per `forward_long` call that ran under a `cache_check` (addendum); the caller clears it
+        self.cache_census = []
 
         self.spynet = SPyNet(pretrained=spynet_pretrained)
         for p in self.spynet.parameters():
@@ -423,7 +425,7 @@ class EAVSRP(nn.Module):
 
     # -- long clips ------------------------------------------------------------------------
     def forward_long(self, lrs, frame_chunk=None, cache="device", sink=None, emit=None, pad=None, window=None, transform=None,
-                     cache_dtype=None):
+                     cache_dtype=None, cache_check=None):
         """`forward` for a whole scene, inference only (call it under torch.no_grad(); it raises otherwise).
 
         The three stages that `forward` runs on all t n frames as one batch -- SPyNet on the frame pairs, the encoder with the
@@ -476,13 +478,28 @@ class EAVSRP(nn.Module):
         changes; what a step keeps in hand (the recurrence's state) is not rounded; flows and LR frames stay fp32.  The result is NOT
         bit-identical to `forward`: it is `forward_long` on a store that returns `x.to(dtype).to(torch.float32)`, bit for bit, and the
         same for both caches.  fp16 keeps 11 significant bits and overflows to inf above 65504; bf16 cannot overflow and keeps 8.
-        cache_dtype=None: today's stores, launches and bytes."""
+        cache_dtype=None: today's stores, launches and bytes.
+
+        cache_check="report" / "raise" / "bf16" (addendum), with a `cache_dtype`: the packs of this call also count what the
+        rounding did, per feature key (`ops.pack16_census`: the largest finite |x|, the non-finite inputs, the overflows to inf, the
+        flushes to zero, the subnormal results), and the call appends one entry to `self.cache_census` -- a list the caller clears:
+        {'asked', 'used', 'fallback', 'frames', 'size', 'keys': {key: `ops.census_record`}}.  Every pack of the call happens in stages
+        1 and 2, before the first frame reaches the sink (`framestore.checked_window` is the order).  "report": the census is read
+        back once, after stage 3; no synchronisation inside the call, and the frames are those of cache_check=None, bit for bit.
+        "raise": it is read between stages 2 and 3, and a key that overflowed or held inf / NaN raises `framestore.CacheRangeError`
+        (a ValueError) before the sink has seen anything of this call.  "bf16" (cache_dtype="fp16" only): read at the same point; where
+        a key overflowed, the store is dropped and stages 1 and 2 run again on a bf16 store -- the result is then
+        `forward_long(cache_dtype="bf16")`'s, bit for bit, the entry says 'fallback': True, 'used': "bf16", keeps the fp16 attempt's
+        census under 'keys' and gains the bf16 run's under 'keys_used'; a call without overflow is cache_dtype="fp16"'s, bit for
+        bit.  Non-finite inputs are reported but trigger no fallback: bf16 cannot cure them.  Per call, not sticky.
+        cache_check=None: every launch and byte is what it was."""
         from .segments import check_pad, padded_size, valid_region
         if transform is not None and (isinstance(transform, bool) or not isinstance(transform, int) or not 0 <= transform <= 7):
             raise ValueError(f"forward_long: transform {transform!r}: a mode 0 .. 7, or None")
         transform = transform or None
         FS.check_cache(cache)
         cache_dtype = FS.check_cache_dtype(cache_dtype)
+        cache_check = FS.check_cache_check(cache_check, cache_dtype)
         check_pad(pad, "forward_long: pad")
         u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_long")
         if window is not None:
@@ -509,75 +526,85 @@ class EAVSRP(nn.Module):
             ea, eb = (int(v) for v in emit)
             if not 0 <= ea < eb <= t:
                 raise ValueError(f"forward_long: emit {emit!r}: frames (a, b) with 0 <= a < b <= {t}")
-        store = FS.make_store(cache, n, t, device) if cache_dtype is None else FS.make_store(cache, n, t, device, dtype=cache_dtype)
+        def make(dtype, census):      # (the calls without a census are the ones they were)
+            if census:
+                return FS.make_store(cache, n, t, device, dtype=dtype, census=True)
+            return FS.make_store(cache, n, t, device) if dtype is None else FS.make_store(cache, n, t, device, dtype=dtype)
 
-        # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
-        last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
-        for a, b in chunks:
-            lr_c = self._ingest(lrs, a, b, device, hwc, pad, size, window)
-            if transform is not None:
-                lr_c = ops.dihedral(lr_c, transform)
-            store.put_range("lr", a, lr_c)
-            seq = lr_c if last is None else torch.cat([last, lr_c], 0)
-            m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
-            if m > 0:
-                lrs_1, lrs_2 = seq[:m], seq[n:]
-                with ops.route_batch(pin(2 * n * (t - 1))):
-                    both = self.spynet(torch.cat([lrs_1, lrs_2], 0), torch.cat([lrs_2, lrs_1], 0))
-                first = a if last is None else a - 1
-                store.put_range("flow_backward", first, both[:m])
-                store.put_range("flow_forward", first, both[m:])
-            with ops.route_batch(pin(t * n)):
-                f1 = self.encoder(lr_c)
-                f2, f4 = AG.pyramid(f1)
-            for key, val in zip(_PYR, (f1, f2, f4)):
-                store.put_range(key, a, val)
-            last = lr_c[-n:]
-            del lr_c, seq, f1, f2, f4
+        def fill(store):
+            # -- stage 1, per chunk: ingest, the flows of the chunk's frame pairs, encoder + pyramid
+            last = None      # the previous chunk's last frame (first frame of this chunk's first pair)
+            for a, b in chunks:
+                lr_c = self._ingest(lrs, a, b, device, hwc, pad, size, window)
+                if transform is not None:
+                    lr_c = ops.dihedral(lr_c, transform)
+                store.put_range("lr", a, lr_c)
+                seq = lr_c if last is None else torch.cat([last, lr_c], 0)
+                m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
+                if m > 0:
+                    lrs_1, lrs_2 = seq[:m], seq[n:]
+                    with ops.route_batch(pin(2 * n * (t - 1))):
+                        both = self.spynet(torch.cat([lrs_1, lrs_2], 0), torch.cat([lrs_2, lrs_1], 0))
+                    first = a if last is None else a - 1
+                    store.put_range("flow_backward", first, both[:m])
+                    store.put_range("flow_forward", first, both[m:])
+                with ops.route_batch(pin(t * n)):
+                    f1 = self.encoder(lr_c)
+                    f2, f4 = AG.pyramid(f1)
+                for key, val in zip(_PYR, (f1, f2, f4)):
+                    store.put_range(key, a, val)
+                last = lr_c[-n:]
+                del lr_c, seq, f1, f2, f4
 
-        # -- stage 2: the four branches, one time step at a time
-        branches = []
-        for iter_ in (1, 2):
-            for direction in ("backward", "forward"):
-                module = f"{direction}_{iter_}"
-                self._propagate_long(store, module, list(branches), n, t, hoist=single)
-                branches.append(module)
+            # -- stage 2: the four branches, one time step at a time
+            branches = []
+            for iter_ in (1, 2):
+                for direction in ("backward", "forward"):
+                    module = f"{direction}_{iter_}"
+                    self._propagate_long(store, module, list(branches), n, t, hoist=single)
+                    branches.append(module)
+            return branches
 
-        # -- stage 3, per chunk: reconstruction + upsampling tail
-        keys = ["spatial"] + branches + ["lr"]
-        out = None
-        if emit is None:
-            tail, pin_tail, base, single_tail = chunks, pin, 0, single
-        else:      # the chunks' parts inside [ea, eb); always pinned: fewer rows than t n must not choose another kernel
-            tail = [(max(a, ea), min(b, eb)) for a, b in chunks if max(a, ea) < min(b, eb)]
-            pin_tail, base, single_tail = (lambda rows: rows), ea, len(tail) == 1
-        for key in keys:
-            store.prefetch_range(key, *tail[0])
-        for ci, (a, b) in enumerate(tail):
-            tensors = [store.get_range(key, a, b) for key in keys]
-            if ci + 1 < len(tail):      # (host cache: the next chunk's copies overlap this chunk's kernels)
-                for key in keys:
-                    store.prefetch_range(key, *tail[ci + 1])
-            with ops.route_batch(pin_tail(t * n)):
-                sr = self._upsample_tm(tensors[:-1], tensors[-1])
-            del tensors
-            sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
-            if transform is not None:      # where mode k has moved the frame's samples to, inside its (transposed: s W x s H) SR frame
-                r0, r1, c0, c1 = valid_region(transform, h, w, *(size or (h, w)), self.scale)
-                sr = sr[..., r0:r1, c0:c1]
-            elif size is not None:      # the crop: a view here, one copy of the chunk's output where it is made contiguous / stored below
-                sr = sr[..., :self.scale * h, :self.scale * w]
-            if sink is not None:      # (`forward_tiled`'s own sink blends the view as it stands: `ops.tile_blend` reads strides)
-                sink(a, sr if getattr(sink, "takes_views", False) else sr.contiguous())
-            elif single_tail:
-                out = sr.contiguous()
-            else:
-                if out is None:
-                    out = sr.new_empty((n, tail[-1][1] - base) + tuple(sr.shape[2:]))
-                out[:, a - base:b - base] = sr
-            del sr
-        store.finish()
-        return out
+        def drain(store, branches):
+            # -- stage 3, per chunk: reconstruction + upsampling tail
+            keys = ["spatial"] + branches + ["lr"]
+            out = None
+            if emit is None:
+                tail, pin_tail, base, single_tail = chunks, pin, 0, single
+            else:      # the chunks' parts inside [ea, eb); always pinned: fewer rows than t n must not choose another kernel
+                tail = [(max(a, ea), min(b, eb)) for a, b in chunks if max(a, ea) < min(b, eb)]
+                pin_tail, base, single_tail = (lambda rows: rows), ea, len(tail) == 1
+            for key in keys:
+                store.prefetch_range(key, *tail[0])
+            for ci, (a, b) in enumerate(tail):
+                tensors = [store.get_range(key, a, b) for key in keys]
+                if ci + 1 < len(tail):      # (host cache: the next chunk's copies overlap this chunk's kernels)
+                    for key in keys:
+                        store.prefetch_range(key, *tail[ci + 1])
+                with ops.route_batch(pin_tail(t * n)):
+                    sr = self._upsample_tm(tensors[:-1], tensors[-1])
+                del tensors
+                sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
+                if transform is not None:      # where mode k has moved the frame's samples to, inside its (transposed: s W x s H) SR frame
+                    r0, r1, c0, c1 = valid_region(transform, h, w, *(size or (h, w)), self.scale)
+                    sr = sr[..., r0:r1, c0:c1]
+                elif size is not None:      # the crop: a view here, one copy of the chunk's output where it is made contiguous / stored below
+                    sr = sr[..., :self.scale * h, :self.scale * w]
+                if sink is not None:      # (`forward_tiled`'s own sink blends the view as it stands: `ops.tile_blend` reads strides)
+                    sink(a, sr if getattr(sink, "takes_views", False) else sr.contiguous())
+                elif single_tail:
+                    out = sr.contiguous()
+                else:
+                    if out is None:
+                        out = sr.new_empty((n, tail[-1][1] - base) + tuple(sr.shape[2:]))
+                    out[:, a - base:b - base] = sr
+                del sr
+            return out
+
+        if cache_check is None:      # make, fill, drain, finish
+            return FS.checked_window(make, fill, drain, cache_dtype, None, None, None)
+        return FS.checked_window(make, fill, drain, cache_dtype, cache_check, dict(frames=t, size=(h, w)),
+                                 self.__dict__.setdefault("cache_census", []))
 
     def forward_segments(self, lrs, segments, frame_chunk=None, cache="device", sink=None):
         """A clip of any length as a sequence of `forward_long` calls: for every (start, stop, emit_start, emit_stop) of
@@ -588,19 +615,21 @@ class EAVSRP(nn.Module):
         Frames of any size: `forward_segments_padded`."""
         return self.forward_segments_padded(lrs, segments, None, frame_chunk=frame_chunk, cache=cache, sink=sink)
 
-    def forward_segments_padded(self, lrs, segments, pad, frame_chunk=None, cache="device", sink=None, cache_dtype=None):
+    def forward_segments_padded(self, lrs, segments, pad, frame_chunk=None, cache="device", sink=None, cache_dtype=None, cache_check=None):
         """`forward_segments` for frames of any size: `pad` is `forward_long`'s -- "reflect" / "edge": every window is
         padded on the device while it is converted and its SR frames are cropped; None: `forward_segments` itself.  A method of its
         own: `forward_segments` keeps the parameter list it was published with.  `cache_dtype` is `forward_long`'s, for
-        every window; it is also how `forward_segments` is called with a 16-bit cache (pad=None)."""
+        every window; it is also how `forward_segments` is called with a 16-bit cache (pad=None).  `cache_check` is `forward_long`'s
+        too: one entry of `self.cache_census` per window, and with "bf16" each window falls back on its own."""
         from .segments import check_pad, check_plan
         check_pad(pad, "forward_segments_padded: pad")
         cache_dtype = FS.check_cache_dtype(cache_dtype)
+        cache_check = FS.check_cache_check(cache_check, cache_dtype)
         _, _, _, t, _, _ = _clip_geometry(lrs, "forward_segments")
 
         def segment(part, emit, part_sink, last):
             return self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=part_sink, emit=emit, pad=pad,
-                                     cache_dtype=cache_dtype)
+                                     cache_dtype=cache_dtype, **_checked(cache_check))
         return self._over_plan(lrs, check_plan(t, segments), sink, segment)
 
     def _over_plan(self, lrs, plan, sink, segment):
@@ -624,7 +653,8 @@ class EAVSRP(nn.Module):
             del sr
         return out
 
-    def forward_tiled(self, lrs, tile, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device", sink=None, cache_dtype=None):
+    def forward_tiled(self, lrs, tile, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device", sink=None, cache_dtype=None,
+                      cache_check=None):
         """Frames of any resolution, inference only: the network runs on overlapped spatial tiles and the SR tiles are
         blended into the frame with a feathered partition of unity, so what is resident follows the tile's area, not the frame's.
 
@@ -642,10 +672,12 @@ class EAVSRP(nn.Module):
         of a tile see the tile alone, and near a seam two such views are averaged.
 
         Where one tile covers the frame the call IS `forward_long` / `forward_segments_padded`: no accumulator, no blend.
-        `cache_dtype` is `forward_long`'s, for every tile."""
+        `cache_dtype` is `forward_long`'s, for every tile, and so is `cache_check`: one entry of `self.cache_census` per
+        tile and segment; with "bf16" a tile that overflowed is blended from its bf16 run beside fp16 neighbours."""
         from .segments import check_pad, check_plan, check_tile, plan_tiles, tile_axis
         FS.check_cache(cache)
         cache_dtype = FS.check_cache_dtype(cache_dtype)
+        cache_check = FS.check_cache_check(cache_check, cache_dtype)
         check_pad(pad, "forward_tiled: pad")
         u8, hwc, n, t, h, w = _clip_geometry(lrs, "forward_tiled")
         sides = check_tile(tile, "forward_tiled: tile")
@@ -656,11 +688,11 @@ class EAVSRP(nn.Module):
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
         if len(tiles) == 1:      # the untiled call: `_video` decides between `forward_long` and the segment plan
-            return self._video(lrs, segments, None, 32, pad, frame_chunk, cache, sink, cache_dtype)
+            return self._video(lrs, segments, None, 32, pad, frame_chunk, cache, sink, cache_dtype, cache_check)
         rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
-        return self._blended("forward_tiled", lrs, (0,), tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype)
+        return self._blended("forward_tiled", lrs, (0,), tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype, cache_check)
 
-    def _blended(self, who, lrs, modes, tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype):
+    def _blended(self, who, lrs, modes, tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype, cache_check=None):
         """The accumulator loop of `forward_tiled` (modes = (0,)) and `forward_ensemble`, which have checked every argument: `tiles` in
         `plan_tiles` order over the windows `rows` x `cols` of the two axes (one tile: the frame, read without a window; its
         weights are 1), `plan` a checked segment plan.  Per segment the window of frames is uploaded once, the accumulator view is
@@ -686,7 +718,8 @@ class EAVSRP(nn.Module):
                 for mode in modes:
                     blend = _Blend(acc, emit[0], mode, s * window[0], s * window[2], wy[ti // len(cols)], wx[ti % len(cols)])
                     self.forward_long(part, frame_chunk=frame_chunk, cache=cache, sink=blend, emit=emit, pad=pad,
-                                      window=window if len(tiles) > 1 else None, transform=mode, cache_dtype=cache_dtype)
+                                      window=window if len(tiles) > 1 else None, transform=mode, cache_dtype=cache_dtype,
+                                      **_checked(cache_check))
             if part_sink is not None:
                 fc = k if frame_chunk is None else min(int(frame_chunk), k)
                 for a in range(0, k, fc):
@@ -702,31 +735,37 @@ class EAVSRP(nn.Module):
         handed on; so is the result.  (With a 16-bit feature cache: `forward_cached`.)"""
         return self._video(lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, None)
 
-    def _video(self, lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, cache_dtype):
-        """`forward_video`'s dispatch, with `forward_long`'s `cache_dtype` for whichever path is taken"""
+    def _video(self, lrs, segments, tile, tile_overlap, pad, frame_chunk, cache, sink, cache_dtype, cache_check=None):
+        """`forward_video`'s dispatch, with `forward_long`'s `cache_dtype` -- and `cache_check`, handed on only where one is set -- for
+        whichever path is taken"""
         from .segments import check_tile, plan_tiles
         sides = check_tile(tile, "forward_video: tile")
         if sides is not None:
             h, w = _clip_geometry(lrs, "forward_video")[4:]
             if len(plan_tiles(h, w, sides, tile_overlap)) > 1:
                 return self.forward_tiled(lrs, tile, overlap=tile_overlap, segments=segments, pad=pad, frame_chunk=frame_chunk,
-                                          cache=cache, sink=sink, cache_dtype=cache_dtype)
+                                          cache=cache, sink=sink, cache_dtype=cache_dtype, **_checked(cache_check))
         if segments is not None:
             return self.forward_segments_padded(lrs, segments, pad, frame_chunk=frame_chunk, cache=cache, sink=sink,
-                                                cache_dtype=cache_dtype)
-        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad, cache_dtype=cache_dtype)
+                                                cache_dtype=cache_dtype, **_checked(cache_check))
+        return self.forward_long(lrs, frame_chunk=frame_chunk, cache=cache, sink=sink, pad=pad, cache_dtype=cache_dtype,
+                                 **_checked(cache_check))
 
     def forward_cached(self, lrs, cache_dtype, ensemble=None, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None,
-                       cache="device", sink=None):
+                       cache="device", sink=None, cache_check=None):
         """`forward_ensemble` -- and through it `forward_video`, `forward_tiled`, `forward_segments_padded` and `forward_long` -- with
         the 16-bit feature cache of `forward_long(cache_dtype=...)` in every `forward_long` call it makes.  A method of
         its own: `forward_video`, `forward_ensemble` and `forward_segments` keep the parameter lists they were published with.
         ensemble=None: no ensemble.  cache_dtype=None IS `forward_ensemble` / `forward_video`.  Refused before anything runs: a
-        `cache_dtype` that is not None, "fp16", "bf16" or one of the two torch dtypes."""
+        `cache_dtype` that is not None, "fp16", "bf16" or one of the two torch dtypes.  `cache_check` is `forward_long`'s (DESIGN 7n,
+        addendum), for every call made: each appends its own entry to `self.cache_census` and, with "bf16", falls back on its own --
+        a tiled, segmented or ensembled run may mix fp16 and bf16 windows, and the entries say which.  Refused with the rest: an
+        unknown value, a check without a `cache_dtype`, "bf16" beside a cache that is not fp16."""
         cache_dtype = FS.check_cache_dtype(cache_dtype)
+        cache_check = FS.check_cache_check(cache_check, cache_dtype)
         if ensemble is None:
-            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, cache_dtype)
-        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, cache_dtype)
+            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, cache_dtype, cache_check)
+        return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, cache_dtype, cache_check)
 
     def forward_ensemble(self, lrs, ensemble=8, tile=None, overlap=32, segments=None, pad=None, frame_chunk=None, cache="device",
                          sink=None):
@@ -752,8 +791,8 @@ class EAVSRP(nn.Module):
         `forward_cached`.)"""
         return self._ensemble(lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, None)
 
-    def _ensemble(self, lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, cache_dtype):
-        """`forward_ensemble`'s body, with `forward_long`'s `cache_dtype` (checked by the caller) for every call it makes"""
+    def _ensemble(self, lrs, ensemble, tile, overlap, segments, pad, frame_chunk, cache, sink, cache_dtype, cache_check=None):
+        """`forward_ensemble`'s body, with `forward_long`'s `cache_dtype` and `cache_check` (checked by the caller) for every call it makes"""
         from .segments import check_ensemble, check_pad, check_plan, check_tile, plan_tiles, tile_axis
         modes = check_ensemble(ensemble, "forward_ensemble: ensemble")      # refused before anything runs
         FS.check_cache(cache)
@@ -765,12 +804,12 @@ class EAVSRP(nn.Module):
             raise ValueError(f"frame_chunk {frame_chunk!r}: a positive number of frames, or None")
         plan = [(0, t, 0, t)] if segments is None else check_plan(t, segments)
         if modes is None or modes == (0,):      # off: no accumulator, no blend
-            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, cache_dtype)
+            return self._video(lrs, segments, tile, overlap, pad, frame_chunk, cache, sink, cache_dtype, cache_check)
         if len(tiles) == 1:      # the whole frame (no tile, or one that covers it): one window per axis
             rows, cols = [(0, h)], [(0, w)]
         else:
             rows, cols = tile_axis(h, sides[0], overlap), tile_axis(w, sides[1], overlap)
-        return self._blended("forward_ensemble", lrs, modes, tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype)
+        return self._blended("forward_ensemble", lrs, modes, tiles, rows, cols, plan, pad, frame_chunk, cache, sink, cache_dtype, cache_check)
 
     def _clip_device(self, lrs):
         """the device a clip runs on: its own, or the network's for 8-bit frames in host memory; anything but a GPU is refused"""
@@ -943,7 +982,30 @@ def long_clip_options(opt=None):
     from .segments import ensemble_options
     ensemble_options(opt)        # likewise: opt.ensemble, read by EAVSRPModel.forward and harness.super_resolve
     cache_dtype_option(opt)      # likewise: opt.cache_dtype, read by EAVSRPModel.forward and harness.super_resolve
+    cache_check_option(opt)      # likewise: opt.cache_check, read beside it
     return fc, cc
+
+
+def _checked(cache_check):
+    """the keyword a `forward_long` call (or one of the methods that lead to it) gains under a `cache_check`; none without one: the
+    call is then the call it was"""
+    return {} if cache_check is None else {"cache_check": cache_check}
+
+
+def cache_check_option(opt=None):
+    """None, "report", "raise" or "bf16": what is done about the range of the 16-bit feature cache (`EAVSRP.forward_long(cache_check=...)`,
+    DESIGN 7n addendum) -- `opt.cache_check`, falling back to the environment where the options do not carry it
+    (EAVSR_CACHE_CHECK=report|raise|bf16), None -- no census -- where neither does.  The spelling alone is checked here; that a
+    check needs a `cache_dtype`, and "bf16" an fp16 one, is refused where both are known (`framestore.check_cache_check`).  Not among
+    the reference's options."""
+    from .segments import one_of, read_option
+    choices = one_of(FS.CACHE_CHECKS, "report, raise or bf16")
+
+    def from_opt(value, who):
+        if not isinstance(value, str):
+            raise ValueError(f"{who}={value!r}: 'report', 'raise', 'bf16' or None")
+        return one_of(FS.CACHE_CHECKS, "'report', 'raise', 'bf16' or None")(value, who)
+    return read_option(opt, "cache_check", "EAVSR_CACHE_CHECK", from_opt, choices)
 
 
 def cache_dtype_option(opt=None):
@@ -1001,6 +1063,12 @@ class EAVSRPModel:
         if self.isTrain and getattr(opt, "cache_dtype", None) is not None:
             raise ValueError("opt.cache_dtype: the 16-bit feature cache is an inference option (EAVSRP.forward_long); training keeps "
                              "its activations for the backward pass in fp32")
+        # opt.cache_check (not among the reference's options): the census of that cache and what is done about it (addendum)
+        if self.isTrain and getattr(opt, "cache_check", None) is not None:
+            raise ValueError("opt.cache_check: the census belongs to the 16-bit feature cache, an inference option (EAVSRP.forward_long)")
+        self.cache_check = cache_check_option(opt)
+        if not self.isTrain:      # (training reads neither: an environment set for inference runs does not stop it)
+            FS.check_cache_check(self.cache_check, self.cache_dtype)
         self.png_encoder = png_encoder_option(opt)
         # opt.pad_frames (not among the reference's options): frames of any size outside training (EAVSRP.forward_long(pad=...))
         from .segments import pad_option
@@ -1115,7 +1183,8 @@ class EAVSRPModel:
             with torch.no_grad():
                 self.data_sr_seq = self.netEAVSRP.forward_cached(self.data_lr_seq, self.cache_dtype, ensemble=self.ensemble,
                                                                  tile=self.tile, overlap=self.tile_overlap, pad=self.pad_frames,
-                                                                 frame_chunk=self.frame_chunk, cache=cache)
+                                                                 frame_chunk=self.frame_chunk, cache=cache,
+                                                                 **_checked(self.cache_check))
         elif not self.isTrain and self.ensemble is not None:
             # the mean over flips / transposes of the frame, tiled and padded as below
             with torch.no_grad():

@@ -108,6 +108,114 @@ def check_cache_dtype(x) -> Optional[str]:
     raise ValueError(f"cache_dtype {x!r}: None, 'fp16' or 'bf16' (torch.float16 / torch.bfloat16)")
 
 
+CACHE_CHECKS = ("report", "raise", "bf16")
+# the rows of a store's census tensor, one per key a 16-bit store rounds (`is_feature_key`): the pyramid and the four branches
+CENSUS_KEYS = PYR + ("backward_1", "forward_1", "backward_2", "forward_2")
+
+
+def check_cache_check(x, cache_dtype) -> Optional[str]:
+    """`cache_check` beside a `cache_dtype` that `check_cache_dtype` has passed (addendum): None (no census: today's
+    launches) | "report" (count what the rounding did, read it when the window has ended) | "raise" (read it before the first frame
+    leaves, refuse a window that overflowed or held inf / NaN) | "bf16" (likewise, and run an fp16 window that overflowed again on a
+    bf16 store).  Refused: anything else, a check without a 16-bit cache to check, "bf16" where the cache is not fp16."""
+    if x is None:
+        return None
+    if not isinstance(x, str) or x not in CACHE_CHECKS:
+        raise ValueError(f"cache_check {x!r}: None, 'report', 'raise' or 'bf16'")
+    if cache_dtype is None:
+        raise ValueError(f"cache_check {x!r} without cache_dtype: the census is taken where features are rounded to 16 bits")
+    if x == "bf16" and cache_dtype != "fp16":
+        raise ValueError(f"cache_check 'bf16' with cache_dtype {cache_dtype!r}: the fallback is from an fp16 cache")
+    return x
+
+
+def out_of_range(keys: Dict[str, Dict]) -> List[str]:
+    """the keys of a census whose features did not fit: a finite value rounded to inf, or inf / NaN going in"""
+    return [k for k, r in keys.items() if r["overflow"] > 0 or r["nonfinite"] > 0]
+
+
+class CacheRangeError(ValueError):
+    """a window whose features do not fit the 16-bit cache (`cache_check="raise"`); `entry` is the window's census entry"""
+
+    def __init__(self, entry: Dict):
+        self.entry = entry
+        keys = entry["keys"]
+        parts = [f"{k}: max |x| {keys[k]['max_abs']:.6g}, {keys[k]['overflow']} overflowed, {keys[k]['nonfinite']} non-finite "
+                 f"of {keys[k]['elements']}" for k in out_of_range(keys)]
+        super().__init__(f"cache_dtype {entry['asked']!r}: features out of range in a window of {entry['frames']} frames of "
+                         f"{entry['size'][0]} x {entry['size'][1]} -- " + "; ".join(parts) +
+                         " (nothing of this window has reached the sink; cache_check='bf16' runs such a window on a bf16 cache)")
+
+
+def checked_window(make, fill, drain, cache_dtype, cache_check, about: Dict, log: List):
+    """The order of one `forward_long` call under a `cache_check` -- pure host code over three callables: `make(dtype, census)` builds
+    a store, `fill(store)` runs stages 1 and 2 (every pack of the window) and returns what `drain(store, state)`, stage 3 -- the only
+    stage that feeds the sink -- needs.  None: make, fill, drain, finish, as ever.  "report": the same with a census, read back once
+    after `finish`.  "raise" / "bf16": the census is read between fill and drain (the one synchronisation the check adds); "raise"
+    refuses a window that is `out_of_range`; "bf16" drops the store of a window that overflowed, makes a bf16 one and fills it again
+    -- once -- and reads that store's census after `finish` ('keys_used').  Every checked call appends its entry to `log`, a refused
+    one before it raises.  Returns what `drain` returned."""
+    store = make(cache_dtype, cache_check is not None)
+    state = fill(store)
+    if cache_check is None:
+        out = drain(store, state)
+        store.finish()
+        return out
+    entry = dict(asked=cache_dtype, used=cache_dtype, fallback=False, **about, keys=None)
+    if cache_check != "report":
+        entry["keys"] = store.census()
+        if cache_check == "raise" and out_of_range(entry["keys"]):
+            store.finish()
+            log.append(entry)
+            raise CacheRangeError(entry)
+        if cache_check == "bf16" and any(r["overflow"] > 0 for r in entry["keys"].values()):
+            store.finish()
+            store = state = None      # the fp16 store's memory goes before the bf16 store's is taken
+            store = make("bf16", True)
+            state = fill(store)
+            entry.update(used="bf16", fallback=True)
+    out = drain(store, state)
+    store.finish()
+    if cache_check == "report":
+        entry["keys"] = store.census()
+    elif entry["fallback"]:
+        entry["keys_used"] = store.census()
+    log.append(entry)
+    return out
+
+
+def census_summary(log: Sequence[Dict]) -> Dict:
+    """one line over the entries of `EAVSRP.cache_census`: the largest |x| any key of any window held, the totals of its counts, and
+    how many windows fell back to bf16 (the counts of a window that fell back are its fp16 attempt's, 'keys')"""
+    rows = [r for e in log for r in (e["keys"] or {}).values()]
+    out = {"windows": len(log), "fallbacks": sum(1 for e in log if e["fallback"]), "max_abs": max([r["max_abs"] for r in rows], default=0.0)}
+    out.update({k: sum(r[k] for r in rows) for k in ("nonfinite", "overflow", "flushed", "subnormal")})
+    return out
+
+
+class _Census:
+    """What a 16-bit store adds with census=True: one int64 (len(CENSUS_KEYS), 5) tensor on the device, zeroed once; a key's packs add
+    into the key's row (`ops.pack16_census`); the elements put per key are counted on the host."""
+
+    def _census_init(self, census: bool, device) -> None:
+        self._counts: Optional[Tensor] = torch.zeros((len(CENSUS_KEYS), 5), dtype=torch.int64, device=device) if census else None
+        self._elements: Dict[str, int] = {}
+
+    def _census_row(self, key: str, src: Tensor) -> Tensor:
+        if key not in CENSUS_KEYS:
+            raise ValueError(f"census: no row for feature key {key!r} ({', '.join(CENSUS_KEYS)})")
+        self._elements[key] = self._elements.get(key, 0) + int(src.numel())
+        return self._counts[CENSUS_KEYS.index(key)]
+
+    def census(self) -> Dict[str, Dict]:
+        """{key: `ops.census_record`} for the keys that were put, from ONE read-back of the tensor (the host waits for the packs)"""
+        if self._counts is None:
+            raise RuntimeError("census(): the store was made without census=True")
+        from . import ops
+        rows = self._counts.cpu().tolist()
+        return {key: ops.census_record(rows[i], self._elements[key], self.dtype) for i, key in enumerate(CENSUS_KEYS) if key in self._elements}
+
+
 def is_feature_key(key: str) -> bool:
     """what a 16-bit store rounds: the pyramid levels and every branch's outputs -- 64 channels each.  The flows (2 channels of pixel
     offsets) and the LR frames stay fp32."""
@@ -310,20 +418,21 @@ def _contiguous(x: Tensor) -> Tensor:
     return x if x.is_contiguous() else x.contiguous()
 
 
-class DeviceStore16(DeviceStore):
+class DeviceStore16(_Census, DeviceStore):
     """The device cache with its features held in 16 bits: `HostStore` with "host" meaning 16-bit device memory and
     "copy" meaning a kernel.  A feature tensor (`is_feature_key`) is rounded to `dtype` when it is put (`ops.pack16`) and the step that
     produced it keeps its fp32 tensor in hand; reads follow the schedule as the host cache's do -- everything a time step fetches is
     widened into fp32 tensors by ONE `ops.unpack16` launch on the compute stream and dropped by `done`; `get_range` widens a range in
     one launch.  What comes back is `x.to(dtype).to(torch.float32)`, bit for bit.  Flows and LR frames stay fp32 and are served as
     `DeviceStore` serves them.  The hoisted predictors of a one-chunk run read every frame at once: this store keeps the per-step
-    form (`hoists`)."""
+    form (`hoists`).  census=True: every pack also counts what the rounding did, per key (`_Census`)."""
     hoists = False
 
-    def __init__(self, n: int, t: int, device, dtype):
+    def __init__(self, n: int, t: int, device, dtype, census: bool = False):
         super().__init__(n, t, device)
         self.cache_dtype = check_cache_dtype(dtype)
         self.dtype = CACHE_DTYPES[self.cache_dtype]
+        self._census_init(census, device)
         self._window: Dict[Tuple, Tensor] = {}      # (key, frame) -> fp32 tensor
         self._schedule: Optional[Schedule] = None
         self.peak_window_items = 0
@@ -331,6 +440,10 @@ class DeviceStore16(DeviceStore):
     def _pack(self, src: Tensor, dst: Tensor) -> None:
         from . import ops
         ops.pack16([_contiguous(src)], [dst], self.dtype)
+
+    def _pack_census(self, key: str, src: Tensor, dst: Tensor) -> None:
+        from . import ops
+        ops.pack16_census([_contiguous(src)], [dst], self.dtype, self._census_row(key, src))
 
     def put_range(self, key: str, first: int, frames: Tensor) -> None:
         if not is_feature_key(key):
@@ -341,7 +454,10 @@ class DeviceStore16(DeviceStore):
         else:
             dst = torch.empty(frames.shape, dtype=self.dtype, device=frames.device)
             super().put_range(key, first, dst)
-        self._pack(frames, dst)
+        if self._counts is None:
+            self._pack(frames, dst)
+        else:
+            self._pack_census(key, frames, dst)
 
     def new_branch(self, key: str, like: Tensor) -> None:
         super().put_range(key, 0, torch.empty((self.t * self.n,) + tuple(like.shape[1:]), dtype=self.dtype, device=like.device))
@@ -404,17 +520,19 @@ class DeviceStore16(DeviceStore):
         self._window.clear()
 
 
-class HostStore16(HostStore):
+class HostStore16(_Census, HostStore):
     """The host cache with its features held in 16 bits: the pinned buffers of the feature keys are 16-bit, half the bytes
     cross the link each way.  `put_range` rounds on the compute stream into a temporary 16-bit device tensor (`ops.pack16`) and copies
     that on the side stream; `_fetch` copies 16-bit frames into staging tensors and widens all of them with ONE `ops.unpack16` launch
     ON THE SIDE STREAM, and the event the compute stream waits on is recorded behind that launch.  Streams, events and
-    `record_stream` as `HostStore`; the host never synchronises.  The same bits as `DeviceStore16`."""
+    `record_stream` as `HostStore`; the host never synchronises.  The same bits as `DeviceStore16`.  census=True: the device-side
+    pack also counts what the rounding did, per key (`_Census`); the counts stay on the device until `census()` is called."""
 
-    def __init__(self, n: int, t: int, device, dtype):
+    def __init__(self, n: int, t: int, device, dtype, census: bool = False):
         super().__init__(n, t, device)
         self.cache_dtype = check_cache_dtype(dtype)
         self.dtype = CACHE_DTYPES[self.cache_dtype]
+        self._census_init(census, device)
 
     def _held_as(self, key: str, like: Tensor) -> torch.dtype:
         return self.dtype if is_feature_key(key) else like.dtype
@@ -426,7 +544,10 @@ class HostStore16(HostStore):
         k = int(frames.shape[0]) // self.n
         dst = self._host_buffer(key, frames)[first:first + k]
         packed = torch.empty(frames.shape, dtype=self.dtype, device=frames.device)
-        ops.pack16([_contiguous(frames)], [packed], self.dtype)      # on the compute stream, behind the producer
+        if self._counts is None:
+            ops.pack16([_contiguous(frames)], [packed], self.dtype)      # on the compute stream, behind the producer
+        else:
+            ops.pack16_census([_contiguous(frames)], [packed], self.dtype, self._census_row(key, frames))
         ready = torch.cuda.Event()
         ready.record(self._main())
         self.side.wait_event(ready)
@@ -465,9 +586,15 @@ class HostStore16(HostStore):
         self.peak_window_items = max(self.peak_window_items, len(self._window))
 
 
-def make_store(cache: str, n: int, t: int, device, dtype=None):
-    """dtype=None: the fp32 stores.  "fp16" / "bf16" (`check_cache_dtype`): the stores that hold the feature keys in 16 bits."""
+def make_store(cache: str, n: int, t: int, device, dtype=None, *, census=False):
+    """dtype=None: the fp32 stores.  "fp16" / "bf16" (`check_cache_dtype`): the stores that hold the feature keys in 16 bits.
+    census=True (a 16-bit store only: the fp32 stores round nothing and take no census): the store counts what its packs did,
+    `store.census()`.  census=False: every launch is the one it was."""
     host = check_cache(cache) == "host"
     if check_cache_dtype(dtype) is None:
+        if census:
+            raise ValueError("make_store: census=True without a 16-bit dtype: the fp32 stores round nothing")
         return (HostStore if host else DeviceStore)(n, t, device)
-    return (HostStore16 if host else DeviceStore16)(n, t, device, dtype)
+    if not census:
+        return (HostStore16 if host else DeviceStore16)(n, t, device, dtype)
+    return (HostStore16 if host else DeviceStore16)(n, t, device, dtype, census=True)

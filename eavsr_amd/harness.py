@@ -1022,7 +1022,7 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
                   cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
                   tile_overlap: Optional[int] = None, ensemble=None, temporal=None, temporal_flow: Optional[str] = None, niqe=None,
-                  niqe_crop: Optional[int] = None, cache_dtype=None) -> Dict:
+                  niqe_crop: Optional[int] = None, cache_dtype=None, cache_check: Optional[str] = None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -1101,7 +1101,16 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     the same card) and half the bytes over the link with cache="host"; it composes with everything above.  The frames are NOT the
     fp32 cache's bit for bit; which dtype is better for quality is not known here (no trained weights exist in this project).  None:
     `opt.cache_dtype` of a model wrapper, else EAVSR_CACHE_DTYPE=fp16|bf16 (`eavsrp_model.cache_dtype_option`), else off: no launch
-    and no byte differs from a run without it.  The result carries 'cache_dtype': None, "fp16" or "bf16"."""
+    and no byte differs from a run without it.  The result carries 'cache_dtype': None, "fp16" or "bf16".
+
+    The census of that cache (addendum), opt-in beside `cache_dtype`: `cache_check` = "report" / "raise" / "bf16" is
+    `forward_long`'s -- the packs count what the rounding did per feature key; "report" reads the counts when a window has ended,
+    "raise" refuses a window that overflowed or held inf / NaN before any of its frames is written (`framestore.CacheRangeError`),
+    "bf16" runs an fp16 window that overflowed again on a bf16 cache, window by window.  None: `opt.cache_check` of a model wrapper,
+    else EAVSR_CACHE_CHECK=report|raise|bf16 (`eavsrp_model.cache_check_option`), else off: no launch and no byte differs, and the
+    result has neither field.  With a check the network's `cache_census` is cleared at entry and returned as 'cache_census' (one
+    entry per `forward_long` call: window, tile, mode), with 'cache_range' = `framestore.census_summary` of it: the largest |x| any
+    key of any window held, the totals of 'overflow', 'nonfinite', 'flushed' and 'subnormal', and how many windows fell back."""
     from . import ops
     from .segments import (check_pad, check_tile, find_cuts, keep_starts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
                            tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP,
@@ -1111,6 +1120,11 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         from .eavsrp_model import cache_dtype_option
         cache_dtype = cache_dtype_option(getattr(model, "opt", None))
     cache_dtype = check_cache_dtype(cache_dtype)
+    from .framestore import check_cache_check
+    if cache_check is None:
+        from .eavsrp_model import cache_check_option
+        cache_check = cache_check_option(getattr(model, "opt", None))
+    cache_check = check_cache_check(cache_check, cache_dtype)
     if ensemble is None:      # a bad spec is refused here, before a file is read
         modes = ensemble_options(getattr(model, "opt", None))
     elif isinstance(ensemble, str):
@@ -1304,7 +1318,12 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
             scene_bounds[:] = keep_starts(t, starts, min_scene)
-        if cache_dtype is not None:
+        if cache_check is not None:
+            net.cache_census = []
+            net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
+                               segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink,
+                               cache_check=cache_check)
+        elif cache_dtype is not None:
             net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
                                segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
         elif modes == (0,):
@@ -1319,6 +1338,9 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
            "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
            "segments": plan, "scene_starts": starts, "tiles": tiles, "ensemble": modes, "cache_dtype": cache_dtype}
+    if cache_check is not None:
+        from .framestore import census_summary
+        out.update(cache_census=net.cache_census, cache_range=census_summary(net.cache_census))
     frame_temporal = None
     if temporal is not None:
         rows = {key: [[None] * t for _ in range(n)] for key in ("ewarp", "tof", "valid")}

@@ -1952,7 +1952,8 @@ def _cache16_lists(who: str, srcs, dsts, src_dtype, dst_dtype):
     return srcs, dsts
 
 
-def _cache16_run(who: str, entry: str, srcs, dsts, code: int):
+def _cache16_run(who: str, entry: str, srcs, dsts, code: int, extra=()):
+    """`extra`: the entry point's arguments between the dtype code and the stream (the census record)"""
     st = None
     for a, b in cache16_batches(len(srcs)):
         part = [(s, d) for s, d in zip(srcs[a:b], dsts[a:b])]
@@ -1962,7 +1963,7 @@ def _cache16_run(who: str, entry: str, srcs, dsts, code: int):
         st = _stream(part[0][0]) if st is None else st
         sl, dl = _ptr_array([s for s, _ in part]), _ptr_array([d for _, d in part])
         nl = (C.c_int64 * len(part))(*[s.numel() for s, _ in part])
-        _launch(who, 0.0, 6.0 * total, part[0][0], lambda: getattr(lib(), entry)(sl, dl, nl, len(part), code, st), who)
+        _launch(who, 0.0, 6.0 * total, part[0][0], lambda: getattr(lib(), entry)(sl, dl, nl, len(part), code, *extra, st), who)
     return dsts
 
 
@@ -1975,6 +1976,50 @@ def pack16(srcs: Sequence[Tensor], dsts: Sequence[Tensor], dtype) -> List[Tensor
     dt = cache16_dtype(dtype)
     srcs, dsts = _cache16_lists("pack16", srcs, dsts, torch.float32, dt)
     return _cache16_run("pack16", "eavsr_pack16", srcs, dsts, _CACHE16_CODE[dt])
+
+
+CENSUS_SLOTS = ("max_abs", "nonfinite", "overflow", "flushed", "subnormal")      # csrc/cache16_census.h: the record's five words
+
+
+def pack16_census(srcs: Sequence[Tensor], dsts: Sequence[Tensor], dtype, census: Tensor) -> List[Tensor]:
+    """`pack16` -- the same lists, checks, launches and 16-bit result, bit for bit -- that also counts what the rounding did (DESIGN 7n,
+    addendum).  `census`: an int64 device tensor of five elements, contiguous, on the sources' device (typically a row of a larger
+    tensor), that every launch ADDS into -- the caller zeroes it -- in the order of CENSUS_SLOTS: the largest finite |x| as its fp32
+    bits, the non-finite inputs, the finite inputs rounded to +-inf, the finite non-zero inputs rounded to +-0, the subnormal
+    results.  `census_record` turns a row read back into numbers.  Integer max and add: two calls give identical records.  A wrong
+    dtype, shape or device is refused before anything is launched.  Returns `dsts`."""
+    dt = cache16_dtype(dtype)
+    if not isinstance(census, torch.Tensor):
+        raise TypeError(f"pack16_census: census: expected a tensor, got {type(census)}")
+    if census.dtype != torch.int64 or tuple(census.shape) != (len(CENSUS_SLOTS),) or not census.is_contiguous():
+        raise ValueError(f"pack16_census: census: a contiguous int64 tensor of {len(CENSUS_SLOTS)} elements, got {census.dtype} "
+                         f"{tuple(census.shape)}{'' if census.is_contiguous() else ', not contiguous'}")
+    srcs, dsts = _cache16_lists("pack16_census", srcs, dsts, torch.float32, dt)
+    if not census.is_cuda:
+        raise RuntimeError(f"pack16_census: census is on {census.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if srcs and census.device != srcs[0].device:
+        raise ValueError(f"pack16_census: census on {census.device}, the segments on {srcs[0].device}")
+    cp = C.c_void_p(census.data_ptr())
+    return _cache16_run("pack16_census", "eavsr_pack16_census", srcs, dsts, _CACHE16_CODE[dt], (cp,))
+
+
+def census_record(row, elements: int, dtype) -> Dict:
+    """A census row read back from the device (five integers, `pack16_census`) as numbers -- pure host code: 'elements' (the
+    caller's count of what was packed), 'dtype' ("fp16" / "bf16"), 'max_abs' as a Python float (the largest finite |x| that went in;
+    0.0 where none did) and the four counts 'nonfinite', 'overflow', 'flushed', 'subnormal'"""
+    import struct
+    dt = cache16_dtype(dtype)
+    vals = [int(v) for v in (row.tolist() if hasattr(row, "tolist") else row)]
+    if len(vals) != len(CENSUS_SLOTS):
+        raise ValueError(f"census_record: a row of {len(CENSUS_SLOTS)} integers, got {len(vals)}")
+    if isinstance(elements, bool) or not isinstance(elements, int) or elements < 0:
+        raise ValueError(f"census_record: elements {elements!r}: a non-negative integer")
+    if not 0 <= vals[0] < 0x7F800000 or any(not 0 <= v <= elements for v in vals[1:]):
+        raise ValueError(f"census_record: {vals} is no census of {elements} elements")
+    out = {"elements": elements, "dtype": next(k for k, v in CACHE16_DTYPES.items() if v == dt),
+           "max_abs": struct.unpack("<f", struct.pack("<I", vals[0]))[0]}
+    out.update(zip(CENSUS_SLOTS[1:], vals[1:]))
+    return out
 
 
 def unpack16(srcs: Sequence[Tensor], dsts: Sequence[Tensor]) -> List[Tensor]:

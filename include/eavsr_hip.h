@@ -813,6 +813,19 @@ int eavsr_blend_dihedral_f32(float* acc, const float* sr, const float* wy, const
 int eavsr_cache16_max_segments(void);
 int eavsr_pack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype, void* stream);
 int eavsr_unpack16(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype, void* stream);
+/* eavsr_pack16_census (added to ABI 32, nothing above changes): eavsr_pack16 -- the same lists, checks, accesses and 16-bit result --
+ * that also counts what the rounding did.  census: five uint64 in DEVICE memory, 8-byte aligned, that the launch ADDS into (the caller
+ * zeroes them; several launches may share one record).  With u an element's fp32 bits, a = u & 0x7FFFFFFF and o its 16-bit result:
+ *   census[0] max_abs    max of a over the finite elements (a < 0x7F800000), as the integer: reinterpret its low 32 bits as a float
+ *   census[1] nonfinite  elements with a >= 0x7F800000 (inf or NaN going in)
+ *   census[2] overflow   finite elements with (o & 0x7FFF) == 0x7C00 (fp16) / 0x7F80 (bf16): +-inf coming out
+ *   census[3] flushed    finite elements with a != 0 and (o & 0x7FFF) == 0: +-0 coming out
+ *   census[4] subnormal  elements with 0 < (o & 0x7FFF) < 0x0400 (fp16) / 0x0080 (bf16)
+ * The number of elements is the caller's to keep.  Integer max and add: two calls give identical records.  One reduction per workgroup
+ * (cross-lane moves, 160 bytes of LDS), then at most one atomic max / add per non-zero slot per workgroup, at most 2048 workgroups.
+ * NULL census: -1; a census that is not 8-byte aligned: -2; everything else as eavsr_pack16. */
+int eavsr_pack16_census(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype,
+                        uint64_t* census, void* stream);
 /* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
  * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
  * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
