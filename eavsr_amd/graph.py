@@ -5,10 +5,12 @@ time to enqueue them against 370 ms of device time (tools/gpu_enqueue_time.py). 
 next bound once the kernels get faster, and it is host time that eight ranks on one node compete for.  A captured HIP
 graph replays the same launches in about a millisecond of host time.
 
-Every kernel of libeavsr_hip.so is launched on `torch.cuda.current_stream()` and allocates nothing itself, so the standard
+Every kernel of libeavsr_hip.so is launched on `torch.cuda.current_stream()` and allocates nothing itself -- with one
+exception, `png_unfilter` on rows wider than its LDS row (csrc/png_decode.hip, kLdsPixels), which takes its scratch row from
+hipMallocAsync / hipFreeAsync in the order of that same stream and is not part of any captured path -- so the standard
 `torch.cuda.graph` capture works unchanged: outputs and temporaries live in the graph's private memory pool, the input
 is a static buffer that `__call__` copies into.  One-time work (weight packing, hipFuncSetAttribute) happens in the
-warm-up runs before the capture.
+warm-up runs before the capture.  tests/test_hip_stream_order.py holds every pipeline op to this contract on its own.
 """
 from __future__ import annotations
 
@@ -42,6 +44,9 @@ class GraphedForward:
             for _ in range(self.warmup):        # packs weights, sets kernel attributes, warms the allocator
                 self.module(self.static_in)
         torch.cuda.current_stream(self.static_in.device).wait_stream(side)
+        # The derived weights of the warm-up are complete from here on.  The capture relies on it: while a stream captures,
+        # WeightCache.lookup waits for nothing (a dependency may not cross a capture boundary), so this synchronisation is what
+        # orders the captured launches behind the pack kernels of the warm-up's side stream.
         torch.cuda.synchronize(self.static_in.device)
         self.graph = torch.cuda.CUDAGraph()
         # thread_local: a collective library's watchdog thread (RCCL, when a process group exists) must not invalidate the capture
