@@ -288,7 +288,10 @@ template <bool BF16> __device__ __forceinline__ float cp_from_h16(unsigned short
 template <bool BF16> __device__ __forceinline__ float cp_round_h16(float v) {
   if (BF16) {
     const unsigned u = __builtin_bit_cast(unsigned, v);
-    const unsigned r = (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;      // round to nearest even (finite inputs)
+    // total, as cache16.hip's rounding is: a NaN stays a (quiet) NaN -- the carry of the rounding add would turn a NaN with a
+    // small payload into an infinity and one with a large payload into a zero of the other sign; infinities pass through
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return __builtin_bit_cast(float, (u | 0x00400000u) & 0xFFFF0000u);
+    const unsigned r = (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;      // round to nearest even
     return __builtin_bit_cast(float, r);
   }
   return (float)(_Float16)v;
@@ -463,7 +466,12 @@ __global__ __launch_bounds__(1024) void ca_scale_pre_kernel(const float* __restr
     float v = w1_v * mean[tid & 63];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((tid & 63) == 0) hid[hj] = fmaxf(v + b1_v, 0.f);
+    // (a select: fmaxf would turn a NaN mean -- a sample whose sums hold +inf and -inf -- into a hidden unit of 0 and a finite
+    // attention, where CALayer's ReLU keeps the NaN)
+    if ((tid & 63) == 0) {
+      const float u = v + b1_v;
+      hid[hj] = !(u <= 0.f) ? u : 0.f;
+    }
   }
   __syncthreads();
   if (tid < C) {

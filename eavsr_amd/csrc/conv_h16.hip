@@ -337,7 +337,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_h16_kernel(H16Args a) {
                       const unsigned short xs_ = (unsigned short)(xq[r][m][qd][e >> 1] >> (16 * (e & 1)));
                       v = fmaf(v, sq4[m][qd][e], from_h16<BF16>(xs_));
                     }
-                    if (ACT == 1) v = fmaxf(v, 0.f);
+                    // ReLU as a select, not a max: v_max_f32 returns its other operand for a NaN, so fmaxf(NaN, 0) is +0 where
+                    // torch.relu keeps the NaN (common.h, eavsr_act); -inf, -0 and every negative value give +0
+                    if (ACT == 1) v = !(v <= 0.f) ? v : 0.f;
                     if (ACT == 2) v = fmaxf(v, v * slope);
                     pk[e] = to_h16<BF16>(v);
                     if (SUMS) csum[m][4 * qd + e] += ok ? from_h16<BF16>(pk[e]) : 0.f;   // the 16-bit value the next layer reads
@@ -420,7 +422,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_h16_kernel(H16Args a) {
 #pragma unroll
                       for (int e = 0; e < 4; ++e) {
                         float v = acc[r][m][4 * qd + e] + bq4[m][qd][e];
-                        if (ACT == 1) v = fmaxf(v, 0.f);
+                        if (ACT == 1) v = !(v <= 0.f) ? v : 0.f;
                         if (ACT == 2) v = fmaxf(v, v * slope);
                         csum[m][4 * qd + e] = okx ? from_h16<BF16>(to_h16<BF16>(v)) : 0.f;
                       }
@@ -694,7 +696,7 @@ __global__ __launch_bounds__(256) void nhwc_h16_to_nchw_f32_kernel(const unsigne
       const int ch = e >> 6, p = e & 63;
       if (c0 + ch < c && p0 + p < hw) {
         const size_t o = ((size_t)bn * c + c0 + ch) * hw + p0 + p;
-        out[o] = tile[ch][p] + (residual ? residual[o] : 0.f);
+        out[o] = residual ? tile[ch][p] + residual[o] : tile[ch][p];      // (no `+ 0.f`: it would turn -0 into +0)
       }
     }
     __syncthreads();

@@ -46,7 +46,7 @@ constexpr int HW_U4 = HSTEPS * 2 * 64;             // 640 units = 10 pieces
 constexpr int HW_SEGS = HW_U4 / 64;                // 10
 constexpr int HNPIECE = HWIN_SEGS + HW_SEGS;       // 25
 constexpr int HP_IT = (HNPIECE + 7) / 8;           // 4
-constexpr size_t HLDS_BYTES = (2 * (size_t)HWIN_U4 + 2 * (size_t)HW_U4) * 16 + 64 * 4;   // 51,456
+constexpr size_t HLDS_BYTES = (2 * (size_t)HWIN_U4 + 2 * (size_t)HW_U4) * 16 + 64 * 4 + 16;   // 51,472 (the last 16: a zero unit)
 
 struct IL16Args {
   const void* xil;       // [n][cin/8][h][w][8] 16-bit
@@ -96,6 +96,10 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
   u32x4* s_win = reinterpret_cast<u32x4*>(smem16);                 // [2][HWIN_U4]
   u32x4* s_w = s_win + 2 * HWIN_U4;                                // [2][HW_U4]
   float* s_bias = reinterpret_cast<float*>(s_w + 2 * HW_U4);       // [64]
+  // one 16-byte unit of zeros: a corner whose bilinear weight is 0 is read from HERE, not from the window -- 0 * inf would be NaN,
+  // so a sample at an integer position NEXT to a non-finite pixel would poison an output that a plain convolution (which this
+  // kernel is at zero offsets) never lets that pixel reach.  An address select per corner; the blend itself is unchanged.
+  const u32x4* s_zero = reinterpret_cast<const u32x4*>(s_bias + 64);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -209,6 +213,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
     const int co = blockIdx.y * 64 + tid;
     s_bias[tid] = (a.bias && co < a.cout) ? a.bias[co] : 0.f;
   }
+  if (tid == 64) *const_cast<u32x4*>(s_zero) = u32x4{0u, 0u, 0u, 0u};
   __syncthreads();
   f32x16 acc[2];
   auto init_acc = [&]() __attribute__((always_inline)) {
@@ -273,7 +278,10 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
       w1 = hm * hw; w2 = hm * lw; w3 = lm * hw; w4 = lm * lw;
       slow_steps |= (live && !in_win) ? (1u << s) : 0u;
       const u32x4* q = win + (fast ? (int)(__umul24((unsigned)ry, (unsigned)HPW) + (unsigned)rx) : 0);
-      cr[0] = q[0]; cr[1] = q[1]; cr[2] = q[HPW]; cr[3] = q[HPW + 1];
+      cr[0] = *(w1 != 0.f ? q : s_zero);
+      cr[1] = *(w2 != 0.f ? q + 1 : s_zero);
+      cr[2] = *(w3 != 0.f ? q + HPW : s_zero);
+      cr[3] = *(w4 != 0.f ? q + HPW + 1 : s_zero);
     };
     auto blend = [&](u32x4& bop) __attribute__((always_inline)) {
 #pragma unroll
@@ -351,6 +359,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
 #pragma unroll
           for (int k4 = 0; k4 < 4; ++k4) {
             const u32x4 cv = xg[(size_t)cy[k4 >> 1] * w + cx[k4 & 1]];
+            if (cw[k4] == 0.f) continue;      // (a corner at weight 0 is not read: see s_zero)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
               float e0, e1;

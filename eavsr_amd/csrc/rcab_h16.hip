@@ -448,7 +448,10 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
             const f32x4 b4 = *reinterpret_cast<const f32x4*>(s_bias + m1 * 32 + 8 * qd + 4 * half);
             unsigned short pk[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pk[e] = r_to_h16<BF16>(fmaxf(acc1[u][4 * qd + e] + b4[e], 0.f));
+            for (int e = 0; e < 4; ++e) {      // (ReLU as a select: a NaN stays a NaN, as in conv_h16.hip's epilogue)
+              const float v1 = acc1[u][4 * qd + e] + b4[e];
+              pk[e] = r_to_h16<BF16>(!(v1 <= 0.f) ? v1 : 0.f);
+            }
             const unsigned d0 = ((unsigned)pk[0] | ((unsigned)pk[1] << 16)) & keep, d1 = ((unsigned)pk[2] | ((unsigned)pk[3] << 16)) & keep;
             if (pv) {
               typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
