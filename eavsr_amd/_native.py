@@ -235,6 +235,8 @@ SIGNATURES = {
     "eavsr_lpips_maxpool3s2_f32": (C.c_int, [vp, vp, i64, i32, i32, vp]),
     "eavsr_lpips_tap_partials": (i32, [i32, i32]),
     "eavsr_lpips_tap_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    # output at any target size: the antialiased bicubic resize of fp32 frames (csrc/resize_aa.hip; addition to ABI 32)
+    "eavsr_resize_aa_f32": (C.c_int, [vp, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, vp]),
 }
 
 # Entry points of the LAB build only (`python -m eavsr_amd.build --lab`; the header's EXPERIMENTAL section): bound when the

@@ -33,8 +33,9 @@ FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-fno-gpu-rdc",
 
 # per-source additions.  temporal.hip defines its metric operation by operation, every fp32 product and sum rounded on
 # its own: no contraction into fused multiply-adds anywhere in that file (the later flag wins over FLAGS' -ffp-contract=fast).
-# niqe.hip likewise, in fp64: numpy restates the local mean, the deviation and the normalised map bit for bit
-PER_FILE_FLAGS = {"temporal.hip": ["-ffp-contract=off"], "niqe.hip": ["-ffp-contract=off"]}
+# niqe.hip likewise, in fp64: numpy restates the local mean, the deviation and the normalised map bit for bit;
+# resize_aa.hip likewise, in fp32: numpy restates both passes of the resize bit for bit
+PER_FILE_FLAGS = {"temporal.hip": ["-ffp-contract=off"], "niqe.hip": ["-ffp-contract=off"], "resize_aa.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

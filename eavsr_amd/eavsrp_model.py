@@ -983,6 +983,8 @@ def long_clip_options(opt=None):
     ensemble_options(opt)        # likewise: opt.ensemble, read by EAVSRPModel.forward and harness.super_resolve
     cache_dtype_option(opt)      # likewise: opt.cache_dtype, read by EAVSRPModel.forward and harness.super_resolve
     cache_check_option(opt)      # likewise: opt.cache_check, read beside it
+    from .resize import out_size_option
+    out_size_option(opt)         # likewise: opt.out_size, read by EAVSRPModel.forward and harness.super_resolve
     return fc, cc
 
 
@@ -1069,6 +1071,12 @@ class EAVSRPModel:
         self.cache_check = cache_check_option(opt)
         if not self.isTrain:      # (training reads neither: an environment set for inference runs does not stop it)
             FS.check_cache_check(self.cache_check, self.cache_dtype)
+        # opt.out_size (not among the reference's options): the SR frames resized to any target size, outside training
+        if self.isTrain and getattr(opt, "out_size", None) is not None:
+            raise ValueError("opt.out_size: the resize of the SR frames is an inference option (resize.resize_frames has no backward); "
+                             "training compares with the HR frames at the network's own size")
+        from .resize import out_size_option
+        self.out_size = None if self.isTrain else out_size_option(opt)      # (training reads neither the option nor the environment)
         self.png_encoder = png_encoder_option(opt)
         # opt.pad_frames (not among the reference's options): frames of any size outside training (EAVSRP.forward_long(pad=...))
         from .segments import pad_option
@@ -1201,6 +1209,9 @@ class EAVSRPModel:
                 self.data_sr_seq = self.netEAVSRP.forward_long(self.data_lr_seq, frame_chunk=self.frame_chunk, cache=cache)
         else:
             self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
+        if self.out_size is not None:      # (never under isTrain) what `harness.evaluate` scores and `save_visuals` writes
+            from .resize import resize_frames
+            self.data_sr_seq = resize_frames(self.data_sr_seq, self.out_size)
         self.data_sr = self.data_sr_seq[:, self.idx]
         end = time.time()
         if not self.isfirst:

@@ -1017,12 +1017,36 @@ def scene_changes(frames, chunk: int = 64, device=None):
     return torch.cat(hists, 0), torch.cat(sads, 0)
 
 
+def resize_frames(frames, size):
+    """The "Bicubic" row of an SR table: frames in the layouts `super_resolve` takes -- uint8 (t, 3, h, w) / (t, h, w, 3) or fp32 in
+    [0, 1] (t, C, h, w), with or without a leading n, on the device -- resized to size = (H, W) or "HxW" by `resize.resize_frames`
+    (MATLAB's antialiased bicubic `imresize`) -> fp32 in the same arrangement of planes, (.., C, H, W).  uint8 frames go
+    through `ops.u8_to_f32` first, so the result is the fp32 path on v / 255 -- NOT MATLAB's uint8 path, which computes in double on
+    0 .. 255 and rounds to a byte; nothing is clamped here."""
+    from . import ops
+    from .resize import check_out_size, resize_frames as _resize_frames
+    size = check_out_size(tuple(size) if isinstance(size, list) else size, "resize_frames: size")
+    if size is None:
+        raise ValueError("resize_frames: size=None: (rows, columns) or 'HxW'")
+    if not isinstance(frames, torch.Tensor) or frames.dim() not in (4, 5):
+        raise ValueError("resize_frames: frames is a (t, 3, h, w) tensor (uint8: also (t, h, w, 3)), optionally with a leading n")
+    if not frames.is_cuda:
+        raise RuntimeError(f"resize_frames: tensor is on {frames.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    if frames.dtype == torch.uint8:
+        lead = tuple(frames.shape[:-3])
+        x = ops.u8_to_f32(frames.reshape((-1,) + tuple(frames.shape[-3:])))
+        return _resize_frames(x.view(lead + tuple(x.shape[1:])), size)
+    if not frames.is_floating_point():
+        raise ValueError(f"resize_frames: frames is uint8 or floating point, got {frames.dtype}")
+    return _resize_frames(frames.to(torch.float32), size)
+
+
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
                   frame_chunk: Optional[int] = None, cache: str = "device", lpips=None, png_encoder: Optional[str] = None,
                   png_decoder: Optional[str] = None, max_frames: Optional[int] = None, overlap: int = DEFAULT_OVERLAP, cuts=None,
                   cut_thresholds=None, min_scene: int = 2, pad: Optional[str] = None, tile=None,
                   tile_overlap: Optional[int] = None, ensemble=None, temporal=None, temporal_flow: Optional[str] = None, niqe=None,
-                  niqe_crop: Optional[int] = None, cache_dtype=None, cache_check: Optional[str] = None) -> Dict:
+                  niqe_crop: Optional[int] = None, cache_dtype=None, cache_check: Optional[str] = None, out_size=None) -> Dict:
     """Frames in, frames out: a whole scene through `EAVSRP.forward_long`, one chunk of frames at a time.
 
     `model` is a model wrapper (EAVSRPModel / EAVSRPx2Model) or the network itself.  `frames` is the scene: a list of PNG paths
@@ -1110,8 +1134,20 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     else EAVSR_CACHE_CHECK=report|raise|bf16 (`eavsrp_model.cache_check_option`), else off: no launch and no byte differs, and the
     result has neither field.  With a check the network's `cache_census` is cleared at entry and returned as 'cache_census' (one
     entry per `forward_long` call: window, tile, mode), with 'cache_range' = `framestore.census_summary` of it: the largest |x| any
-    key of any window held, the totals of 'overflow', 'nonfinite', 'flushed' and 'subnormal', and how many windows fell back."""
+    key of any window held, the totals of 'overflow', 'nonfinite', 'flushed' and 'subnormal', and how many windows fell back.
+
+    Output at any target size, opt-in: `out_size` = (H, W) or "1080x1920" resizes every SR chunk to that size as the sink's
+    first statement (`resize.resize_frames`: MATLAB's antialiased bicubic `imresize`, one HIP op) -- after the `pad` crop, the tile
+    blend and the ensemble mean, because it acts on what the sink is handed.  Every consumer sees the resized frames: the files of both
+    PNG encoders, PSNR / SSIM / LPIPS against `hr` -- which is now expected at `out_size` --, NIQE, and the temporal columns, whose
+    flows are computed at that size.  None: `opt.out_size` of a model wrapper, else EAVSR_OUT_SIZE=HxW (`resize.out_size_option`),
+    else off: no launch and no byte differs, and the result has no such field.  Set, the result carries 'out_size': (H, W).  The
+    values have not been compared with MATLAB or any package, and the fp32 path is not MATLAB's uint8 path (eavsr_amd/resize.py)."""
     from . import ops
+    from .resize import check_out_size, out_size_option, resize_frames as _resize_frames
+    if out_size is None:      # a bad value is refused here, before a file is read
+        out_size = out_size_option(getattr(model, "opt", None))
+    out_size = check_out_size(out_size, "super_resolve: out_size")
     from .segments import (check_pad, check_tile, find_cuts, keep_starts, pad_option, parse_tile, plan_segments, plan_tiles, segment_options,
                            tile_options, DEFAULT_HIST_THRESHOLD, DEFAULT_SAD_THRESHOLD, DEFAULT_TILE_OVERLAP,
                            check_ensemble, ensemble_options, parse_ensemble)
@@ -1273,6 +1309,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         held.update(next=first + k, sr=sr[:, -1:].clone(), hr=None if ref is None else ref[:, -1:].clone())
 
     def sink(first, sr):
+        if out_size is not None:      # every consumer below sees the resized frames
+            sr = _resize_frames(sr, out_size)
         k = int(sr.shape[1])
         c, hh, ww = (int(v) for v in sr.shape[2:])
         flat = sr.reshape(n * k, c, hh, ww)
@@ -1301,6 +1339,9 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
             host = rgb8[:k].cpu()      # clip 0, as save_visuals
             for j in range(k):
                 written.append(write_png(host[j], os.path.join(out_dir, _frame_name(names, first + j)), hwc=True))
+
+    # the resize reads strides: a cropped chunk (`pad`) is handed over as the view it is, not copied first
+    sink.takes_views = out_size is not None
 
     torch.cuda.synchronize(device)
     torch.cuda.reset_peak_memory_stats(device)
@@ -1338,6 +1379,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     out = {"frames": n * t, "seconds": seconds, "frames_per_s": n * t / seconds if seconds > 0 else math.nan,
            "peak_bytes": int(torch.cuda.max_memory_allocated(device)), "written": written,
            "segments": plan, "scene_starts": starts, "tiles": tiles, "ensemble": modes, "cache_dtype": cache_dtype}
+    if out_size is not None:
+        out["out_size"] = out_size
     if cache_check is not None:
         from .framestore import census_summary
         out.update(cache_census=net.cache_census, cache_range=census_summary(net.cache_census))

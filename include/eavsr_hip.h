@@ -997,6 +997,21 @@ int eavsr_niqe_half_f64(const double* in, double* out, const int32_t* row_idx, c
                         const int32_t* col_idx, const double* col_w, int32_t col_taps, const int32_t* col_lo, int32_t span, int32_t N,
                         int32_t H, int32_t W, int32_t h, int32_t w, void* stream);
 
+/* ---- f5: output at any target size (csrc/resize_aa.hip; added to ABI 32, nothing above changes) ------------------------------
+ * eavsr_resize_aa_f32: the separable antialiased resize of N x C fp32 planes of H x W to oh x ow from tables on the device -- the tables of
+ *   MATLAB's bicubic `imresize` as eavsr_amd/resize.py axis_tables builds them.  Sample (n, c, y, x) of the source is
+ *   src[n stride_n + c stride_c + y stride_h + x] (strides in elements, >= 0; the last stride is 1).  Rows first, then columns:
+ *     t[o, x] = acc over k = 0 .. row_taps - 1, in that order, of:  acc = 0.0f;  if row_w[o, k] != 0: acc = acc + row_w[o, k] src[row_idx[o, k], x]
+ *     out[o, p] = the same along x on t with col_idx / col_w (ow, col_taps)
+ *   every product and sum rounded to fp32 on its own (no fused multiply-add); a tap of weight zero is skipped, never multiplied, so a
+ *   non-finite sample reaches exactly the outputs whose non-zero taps read it.  Nothing is clamped.  Indices outside the plane are
+ *   clamped into it.  out: (N, C, oh, ow) contiguous.  tmp: N C oh ((W + 6) & ~3) floats, 16-byte aligned (the row pass).
+ *   Two launches on `stream`, no atomics: two calls agree bit for bit.
+ *   NULL pointer: -1.  A size < 1 or a side above 2^24, taps outside 1..64, a negative stride, misaligned pointers: -2. */
+int eavsr_resize_aa_f32(const float* src, int64_t stride_n, int64_t stride_c, int64_t stride_h, int32_t N, int32_t C, int32_t H, int32_t W,
+                        const int32_t* row_idx, const float* row_w, int32_t row_taps, const int32_t* col_idx, const float* col_w,
+                        int32_t col_taps, float* tmp, float* out, int32_t oh, int32_t ow, void* stream);
+
 /* ============================================================================================
  * EXPERIMENTAL -- exported by the LAB build only (`python -m eavsr_amd.build --lab`, -DEAVSR_LAB=1; eavsr_lab_build() == 1).
  * Schedules that were built, measured against the stable ones above and retired; kept because DESIGN.md / docs/history quote
