@@ -27,6 +27,8 @@ ARCH = "gfx950"
 # v_pk_mul_f32, which beside MFMAs are slower than the two plain instructions (MI355X_MICROARCH.md, "price of one filler beside
 # MFMAs").  Measured: DCNv2 84-88 -> 77-78 us per 2 x 64 x 180 x 320 launch; the whole library 219.3 -> 217.7 ms per step
 # (tools/visits/r4_d.sh, r4_t.sh).  The packed instructions the kernels WANT are written as inline assembly (conv_wino6.hip).
+# No -ffast-math / -fno-signed-zeros: flow_warp.hip adds +0.f to its corner sums so that a pixel without a valid corner is +0.0
+# (DESIGN 7p); a build that ignores the sign of zero folds that addition away.  tests/test_hip_sampler_domain.py checks the bits.
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-ffp-contract=fast", "-fno-slp-vectorize"]
 

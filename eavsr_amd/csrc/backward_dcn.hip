@@ -20,6 +20,7 @@ struct Samp {
 
 __device__ __forceinline__ Samp make_samp(float py, float px, int h, int w) {
   Samp s;
+  py = eavsr_sample_pos(py, h); px = eavsr_sample_pos(px, w);
   s.in = py > -1.f && px > -1.f && py < (float)h && px < (float)w;
   const float fy0 = floorf(py), fx0 = floorf(px);
   s.lh = py - fy0; s.lw = px - fx0; s.hh = 1.f - s.lh; s.hw = 1.f - s.lw;

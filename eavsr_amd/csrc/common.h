@@ -102,6 +102,13 @@ __device__ __forceinline__ void eavsr_stagger_priority(int wave) {
 // (networks.py:314), evaluated by the same instructions wherever it runs (the DCNv2 sampler or the epilogue of the 5x5 heads)
 __device__ __forceinline__ float eavsr_sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
+// Sampler domain ("Sampler domain"): one axis of a DCNv2 sampling position, brought into [-2, size + 1] before anything
+// is derived from it.  fmaxf returns its other operand for a NaN, so a non-finite position becomes -2 or size + 1: finite, outside
+// the validity gate -1 < p < size with both of its corners outside the image, hence a sample that contributes exactly 0 -- instead
+// of the fraction inf - inf = NaN, which survives a multiplication by a zero mask.  The float-to-int conversion of its floor is then
+// in range on every path and no index arithmetic after it can overflow.  A position inside [-2, size + 1] keeps its bits.
+__device__ __forceinline__ float eavsr_sample_pos(float p, int size) { return fminf(fmaxf(p, -2.f), (float)size + 1.f); }
+
 __device__ __forceinline__ float eavsr_mul_legacy(float a, float b) {
   float r;
   asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));

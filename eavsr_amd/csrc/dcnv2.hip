@@ -119,8 +119,8 @@ __global__ __launch_bounds__(256, 4) void dcnv2_kernel(DcnArgs a) {
     for (int j = 0; j < TAPS_PER_THREAD; ++j) {
       const int tap = tap0 + 2 * j;
       const int ti = tap / 3, tj = tap - 3 * ti;
-      const float py = (float)(gy - 1 + ti) + oy[j];
-      const float px = (float)(gx - 1 + tj) + ox[j];
+      const float py = eavsr_sample_pos((float)(gy - 1 + ti) + oy[j], h);
+      const float px = eavsr_sample_pos((float)(gx - 1 + tj) + ox[j], w);
       const bool in = pix_ok && tap < DKK && py > -1.f && px > -1.f && py < (float)h && px < (float)w;
       const float fy0 = floorf(py), fx0 = floorf(px);
       const float lh = py - fy0, lw = px - fx0;
@@ -342,8 +342,8 @@ __global__ __launch_bounds__(256, 3) void dcnv2_grp_kernel(DcnArgs a) {
   auto setup = [&](int j) __attribute__((always_inline)) {
     const int tap = tap0 + 2 * j;
     const int ti = tap / 3, tj = tap - 3 * ti;
-    const float py = (float)(gy - 1 + ti) + oy[j];
-    const float px = (float)(gx - 1 + tj) + ox[j];
+    const float py = eavsr_sample_pos((float)(gy - 1 + ti) + oy[j], h);
+    const float px = eavsr_sample_pos((float)(gx - 1 + tj) + ox[j], w);
     const bool in = pix_ok && py > -1.f && px > -1.f && py < (float)h && px < (float)w;
     const float fy0 = floorf(py), fx0 = floorf(px);
     const float lh = py - fy0, lw = px - fx0;
@@ -386,8 +386,8 @@ __global__ __launch_bounds__(256, 3) void dcnv2_grp_kernel(DcnArgs a) {
         const float fy = ld_b(offb, (2u * (unsigned)tap * uplane + pix) * 4u);
         const float fx = ld_b(offb, ((2u * (unsigned)tap + 1u) * uplane + pix) * 4u);
         const float fm = ld_b(mkb, ((unsigned)tap * uplane + pix) * 4u);
-        const float py = (float)(gy - 1 + ti) + fy;
-        const float px = (float)(gx - 1 + tj) + fx;
+        const float py = eavsr_sample_pos((float)(gy - 1 + ti) + fy, h);
+        const float px = eavsr_sample_pos((float)(gx - 1 + tj) + fx, w);
         const float fy0 = floorf(py), fx0 = floorf(px);
         const float lh = py - fy0, lw = px - fx0;
         const float hh = 1.f - lh, hw = 1.f - lw;

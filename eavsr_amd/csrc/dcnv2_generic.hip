@@ -48,8 +48,8 @@ __global__ __launch_bounds__(128) void dcnv2_generic_kernel(GArgs a) {
       const int g = c / cpg;
       if (g != cur_g) {   // new deformable group: sampling position of this tap
         cur_g = g;
-        const float py = (float)(oy * a.sh - a.ph + ki * a.dh) + offb[(size_t)(g * 2 * K + 2 * k) * howo];
-        const float pxf = (float)(ox * a.sw - a.pw + kj * a.dw) + offb[(size_t)(g * 2 * K + 2 * k + 1) * howo];
+        const float py = eavsr_sample_pos((float)(oy * a.sh - a.ph + ki * a.dh) + offb[(size_t)(g * 2 * K + 2 * k) * howo], a.h);
+        const float pxf = eavsr_sample_pos((float)(ox * a.sw - a.pw + kj * a.dw) + offb[(size_t)(g * 2 * K + 2 * k + 1) * howo], a.w);
         const bool in = py > -1.f && pxf > -1.f && py < (float)a.h && pxf < (float)a.w;
         const float m = in ? mkb[(size_t)(g * K + k) * howo] : 0.f;
         const float fy0 = floorf(py), fx0 = floorf(pxf);

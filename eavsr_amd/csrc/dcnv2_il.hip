@@ -387,12 +387,12 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
         dy = ca[s]; dx = cb[s]; m = cm[s];
       }
       const bool live = pix_ok && ((s < ISTEPS - 1) || kg == 0);
-      const float py = (fgy + ryk) + dy;
-      const float px = (fgx + rxk) + dx;
+      const float py = eavsr_sample_pos((fgy + ryk) + dy, h);
+      const float px = eavsr_sample_pos((fgx + rxk) + dx, w);
       const float fy0 = floorf(py), fx0 = floorf(px);
       const float lh = py - fy0, lw = px - fx0;
       const float hh = 1.f - lh, hw = 1.f - lw;
-      // v_cvt_i32_f32 saturates (and maps NaN to 0): wild offsets stay defined and simply fail the window test
+      // (py, px lie in [-2, size + 1]: the conversion is in range; wild offsets fail the window test or read the window's zeros)
       const int ry = (int)fy0 - (y0 - IPY0), rx = (int)fx0 - (x0 - IPX0);
       const bool in_win = (unsigned)ry <= (unsigned)(IPH - 2) && (unsigned)rx <= (unsigned)(IPW - 2);
       const bool fast = live && in_win;
@@ -561,8 +561,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
             dx = ld_b(offb, ((2u * (unsigned)tap + 1u) * uplane + pix) * 4u);
             m = ld_b(mkb, ((unsigned)tap * uplane + pix) * 4u);
           }
-          const float py = (fgy + ryt) + dy;
-          const float px = (fgx + rxt) + dx;
+          const float py = eavsr_sample_pos((fgy + ryt) + dy, h);
+          const float px = eavsr_sample_pos((fgx + rxt) + dx, w);
           if (!(py > -1.f && px > -1.f && py < (float)h && px < (float)w)) m = 0.f;     // validity gate (flagged lanes pass it)
           const float fy0 = floorf(py), fx0 = floorf(px);
           const float lh = py - fy0, lw = px - fx0;

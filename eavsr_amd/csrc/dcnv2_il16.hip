@@ -265,8 +265,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
         dy = ca[s]; dx = cb[s]; m = cm[s];
       }
       const bool live = pix_ok && ((s < HSTEPS - 1) || kg == 0);
-      const float py = (fgy + ryk) + dy;
-      const float px = (fgx + rxk) + dx;
+      const float py = eavsr_sample_pos((fgy + ryk) + dy, h);
+      const float px = eavsr_sample_pos((fgx + rxk) + dx, w);
       const float fy0 = floorf(py), fx0 = floorf(px);
       const float lh = py - fy0, lw = px - fx0;
       const float hh = 1.f - lh, hw = 1.f - lw;
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
             dx = ld_b16v(reinterpret_cast<const float*>(ob + (size_t)(2 * tap + 1) * pl4), pix * 4u);
             m = ld_b16v(reinterpret_cast<const float*>(mb + (size_t)tap * pl4), pix * 4u);
           }
-          const float py = (fgy + ryt) + dy, px = (fgx + rxt) + dx;
+          const float py = eavsr_sample_pos((fgy + ryt) + dy, h), px = eavsr_sample_pos((fgx + rxt) + dx, w);
           if (!(py > -1.f && px > -1.f && py < (float)h && px < (float)w)) m = 0.f;
           const float fy0 = floorf(py), fx0 = floorf(px);
           const float lh = py - fy0, lw = px - fx0;

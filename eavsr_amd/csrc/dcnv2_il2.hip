@@ -122,7 +122,7 @@ __device__ __forceinline__ f32x16 j_mfma(const u32x4& a, const u32x4& b, const f
 // the same in-window decision, so the products and sums are spelled out: no contraction choice is left to the compiler)
 template <int HEADS>
 __device__ __forceinline__ void j_position(const float (&t)[6], float dyx, float dxx, float ry, float rx, float fgy, float fgx,
-                                           float& py, float& px) {
+                                           int h, int w, float& py, float& px) {
   float dy, dx;
   if (HEADS) {   // (T . R)[:,k] - R[:,k] + t   (matmul, subtract, add: networks.py:304-311)
     dy = (__builtin_fmaf(t[1], rx, __fmul_rn(t[0], ry)) - ry) + t[4];
@@ -131,8 +131,8 @@ __device__ __forceinline__ void j_position(const float (&t)[6], float dyx, float
     dy = dyx;
     dx = dxx;
   }
-  py = (fgy + ry) + dy;
-  px = (fgx + rx) + dx;
+  py = eavsr_sample_pos((fgy + ry) + dy, h);
+  px = eavsr_sample_pos((fgx + rx) + dx, w);
 }
 
 __device__ __forceinline__ float j_sigmoid(float x) { return eavsr_sigmoid_fast(x); }
@@ -405,12 +405,12 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) t[j] = !HEADS ? 0.f : (u < 4 ? tfA[j] : (u > 4 ? tfB[j] : (kg ? tfB[j] : tfA[j])));
     float py, px;
-    j_position<HEADS>(t, pa[u], pb[u], ryk, rxk, c.fgy, c.fgx, py, px);
+    j_position<HEADS>(t, pa[u], pb[u], ryk, rxk, c.fgy, c.fgx, h, w, py, px);
     const float m = HEADS == 1 ? j_sigmoid(pm[u]) : pm[u];
     const float fy0 = floorf(py), fx0 = floorf(px);
     const float lh = py - fy0, lw = px - fx0;
     const float hh = 1.f - lh, hw = 1.f - lw;
-    // v_cvt_i32_f32 saturates (and maps NaN to 0): wild offsets stay defined and simply fail the window test
+    // (py, px lie in [-2, size + 1]: the conversion is in range; wild offsets fail the window test or read the window's zeros)
     const int ry = (int)fy0 - c.wy0, rx = (int)fx0 - c.wx0;
     // lanes whose corners leave the window, as a lane mask straight from the two compares (a ballot of the bool costs two more
     // vector instructions)

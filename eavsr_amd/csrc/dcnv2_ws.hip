@@ -381,8 +381,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
           dy = ca[r][t]; dx = cb[r][t]; m = cm[r][t];
         }
         const bool live = (r == 0 ? ok0 : ok1) && tap_ok;
-        const float py = ((float)(y0 + 2 * pr + r) + ryk) + dy;
-        const float px = ((float)(x0 + l31) + rxk) + dx;
+        const float py = eavsr_sample_pos(((float)(y0 + 2 * pr + r) + ryk) + dy, h);
+        const float px = eavsr_sample_pos(((float)(x0 + l31) + rxk) + dx, w);
         const float fy0 = floorf(py), fx0 = floorf(px);
         const float lh = py - fy0, lw = px - fx0;
         const float hh = 1.f - lh, hw = 1.f - lw;
@@ -435,8 +435,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
             } else {
               dy = ca[r][t]; dx = cb[r][t]; m = cm[r][t];
             }
-            const float py = ((float)(y0 + 2 * pr + r) + ryk) + dy;
-            const float px = ((float)(x0 + l31) + rxk) + dx;
+            const float py = eavsr_sample_pos(((float)(y0 + 2 * pr + r) + ryk) + dy, h);
+            const float px = eavsr_sample_pos(((float)(x0 + l31) + rxk) + dx, w);
             const bool gate = py > -1.f && px > -1.f && py < (float)h && px < (float)w;   // false for NaN
             const float fy0 = floorf(py), fx0 = floorf(px);
             const float lh = py - fy0, lw = px - fx0;

@@ -185,8 +185,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
   };
   auto setup = [&](int s, Pos& ps, const float* pst) __attribute__((always_inline)) {
     const bool tap_ok = (s < XSTEPS - 1) || kgrp == 0;   // tap 9 does not exist
-    const float py = fyb[s] + oy[s];
-    const float px = fxb[s] + ox[s];
+    const float py = eavsr_sample_pos(fyb[s] + oy[s], h);
+    const float px = eavsr_sample_pos(fxb[s] + ox[s], w);
     const bool in = pix_ok && tap_ok && py > -1.f && px > -1.f && py < (float)h && px < (float)w;
     const float fy0 = floorf(py), fx0 = floorf(px);
     const float lh = py - fy0, lw = px - fx0;
@@ -318,8 +318,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
         if (mine) {
           const unsigned tap = (unsigned)min(2 * t + kgrp, XK - 1);
           const int ti = (int)tap / 3, tj = (int)tap - 3 * ti;
-          const float py = (float)(gy - 1 + ti) + ld_b(offb, (2u * tap * uplane + pix) * 4u);
-          const float px = (float)(gx - 1 + tj) + ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
+          const float py = eavsr_sample_pos((float)(gy - 1 + ti) + ld_b(offb, (2u * tap * uplane + pix) * 4u), h);
+          const float px = eavsr_sample_pos((float)(gx - 1 + tj) + ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u), w);
           const float m = ld_b(mkb, (tap * uplane + pix) * 4u);
           const float fy0 = floorf(py), fx0 = floorf(px);
           const float lh = py - fy0, lw = px - fx0;

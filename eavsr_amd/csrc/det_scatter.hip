@@ -150,7 +150,8 @@ __global__ __launch_bounds__(256) void dcn_det_sample_kernel(const float* __rest
   if (p >= hw) return;
   const int gy = p / w, gx = p - gy * w;
   const size_t oi = ((size_t)sg * 18 + 2 * tap) * hw + p;
-  const float py = (float)(gy - 1 + tap / 3) + offset[oi], px = (float)(gx - 1 + tap % 3) + offset[oi + hw];
+  const float py = eavsr_sample_pos((float)(gy - 1 + tap / 3) + offset[oi], h);
+  const float px = eavsr_sample_pos((float)(gx - 1 + tap % 3) + offset[oi + hw], w);
   const bool in = py > -1.f && px > -1.f && py < (float)h && px < (float)w;
   const float fy0 = floorf(py), fx0 = floorf(px);
   const float lh = py - fy0, lw = px - fx0, hh = 1.f - lh, hwt = 1.f - lw;

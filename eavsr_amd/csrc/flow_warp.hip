@@ -84,7 +84,10 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(
     v += p[i_ne] * w_ne;
     v += p[i_sw] * w_sw;
     v += p[i_se] * w_se;
-    op[(size_t)cc * plane] = v;
+    // -0 + +0 = +0: a pixel with no valid corner is +0.0 whatever the sign of the values its clamped indices read; every other sum
+    // keeps its bits (the products and their contraction into fused multiply-adds are the expression above, untouched).  Holds while
+    // the build keeps signed zeros (build.py FLAGS: no -ffast-math, no -fno-signed-zeros), else the addition is folded away.
+    op[(size_t)cc * plane] = v + 0.f;
   }
 }
 
@@ -171,7 +174,7 @@ __global__ __launch_bounds__(256) void flow_warp_pair_kernel(
         t += l[e][1] * w_ne;
         t += l[e][2] * w_sw;
         t += l[e][3] * w_se;
-        v[e] = t;
+        v[e] = t + 0.f;      // (+0.0 without a valid corner, as in the channel loop below)
       }
       const size_t unit = (((size_t)bn * (c / 8) + (c0 / 8 + o)) * h + py) * w + px;
       if (b_il8 == 1) {
@@ -205,7 +208,10 @@ __global__ __launch_bounds__(256) void flow_warp_pair_kernel(
     v += p[i_ne] * w_ne;
     v += p[i_sw] * w_sw;
     v += p[i_se] * w_se;
-    op[(size_t)cc * plane] = v;
+    // -0 + +0 = +0: a pixel with no valid corner is +0.0 whatever the sign of the values its clamped indices read; every other sum
+    // keeps its bits (the products and their contraction into fused multiply-adds are the expression above, untouched).  Holds while
+    // the build keeps signed zeros (build.py FLAGS: no -ffast-math, no -fno-signed-zeros), else the addition is folded away.
+    op[(size_t)cc * plane] = v + 0.f;
   }
 }
 
@@ -218,8 +224,10 @@ __device__ __forceinline__ float reflect_coord(float in, int twice_low, int twic
   const float span = (float)(twice_high - twice_low) / 2.f;
   in = fabsf(in - mn);
   const float extra = fmodf(in, span);
-  const int flips = (int)floorf(in / span);
-  return (flips % 2 == 0) ? extra + mn : span - extra + mn;
+  // the parity of the flip count in float: no float-to-int conversion that a wild position could take out of range (a count
+  // >= 2^24 is even as a float; the value there is not pinned -- DESIGN.md, "Sampler domain")
+  const float flips = floorf(in / span);
+  return (fmodf(flips, 2.f) == 0.f) ? extra + mn : span - extra + mn;
 }
 
 __global__ __launch_bounds__(256) void flow_warp_generic_kernel(
@@ -287,7 +295,10 @@ __global__ __launch_bounds__(256) void flow_warp_generic_kernel(
     v += p[i_ne] * w_ne;
     v += p[i_sw] * w_sw;
     v += p[i_se] * w_se;
-    op[(size_t)cc * plane] = v;
+    // -0 + +0 = +0: a pixel with no valid corner is +0.0 whatever the sign of the values its clamped indices read; every other sum
+    // keeps its bits (the products and their contraction into fused multiply-adds are the expression above, untouched).  Holds while
+    // the build keeps signed zeros (build.py FLAGS: no -ffast-math, no -fno-signed-zeros), else the addition is folded away.
+    op[(size_t)cc * plane] = v + 0.f;
   }
 }
 

@@ -222,8 +222,10 @@ __global__ __launch_bounds__(256) void pwc_backwarp_kernel(const float* __restri
   const float fx = fp[0] * fmul, fy = fp[(long)fh * fw] * fmul;
   const float gx = (-1.f + (float)(2 * xx + 1) / (float)w) + fx / (((float)w - 1.f) / 2.f);
   const float gy = (-1.f + (float)(2 * y + 1) / (float)h) + fy / (((float)h - 1.f) / 2.f);
-  const float ix = ((gx + 1.f) * (float)w - 1.f) / 2.f;
-  const float iy = ((gy + 1.f) * (float)h - 1.f) / 2.f;
+  // clamped before the int conversion, as flow_warp does: every position outside [-4, size + 4] has all four corners outside the
+  // image, as its clamped value has, and a NaN becomes -4 (fmaxf returns its other operand): mask 0 and out 0, not NaN x 0
+  const float ix = fminf(fmaxf(((gx + 1.f) * (float)w - 1.f) / 2.f, -4.f), (float)w + 4.f);
+  const float iy = fminf(fmaxf(((gy + 1.f) * (float)h - 1.f) / 2.f, -4.f), (float)h + 4.f);
   const float x0f = floorf(ix), y0f = floorf(iy);
   const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
   const float wnw = (x0f + 1.f - ix) * (y0f + 1.f - iy), wne = (ix - x0f) * (y0f + 1.f - iy);
