@@ -8,8 +8,11 @@
 //
 // Arithmetic (as dcnv2_il.hip, NPROD = 6): every fp32 operand is split EXACTLY into three bf16 terms (hi = trunc_bf16(x),
 // mid = trunc_bf16(x - hi), lo = x - hi - mid; hi + mid + lo == x bit for bit), products of bf16 numbers are exact in fp32, the
-// six partial products down to 2^-16 of the result are accumulated in fp32 and the three below 2^-23 (mid*lo, lo*mid, lo*lo)
-// are dropped: at most 2 * 2^-24 relative per product -- one fp32 rounding.  No operand is rounded to 16 bits.
+// six partial products down to 2^-16 of the result are accumulated in fp32 and the three below them (mid*lo, lo*mid, lo*lo) are
+// dropped.  Under truncation |mid| < 2^-7 |x| and |lo| < 2^-15 |x|: mid*lo and lo*mid are each below 2^-22 of x*w, the three
+// together below 2^-21 = 8 * 2^-24 (NOT "2^-23, one fp32 rounding", as this comment used to say: x = w = 0x3F80FFFF drops
+// 2^-21.02) -- the size of four roundings to nearest, per product, all of the product's sign.  No operand is rounded to 16 bits.
+// The contract and its tests: DESIGN.md 4a, tests/product_probe.py.
 // v_mfma_f32_32x32x16_bf16 does 16 k in 32 cycles where v_mfma_f32_32x32x2_f32 does 2 k in 64: six of them are 2.67x the fp32 rate.
 //
 // Unlike conv_x9.hip (3x3, split in registers per use) the input is split ONCE per value, on its way into LDS: a 7x7 tap window

@@ -14,8 +14,9 @@
 //     (128 B/clk) -- half the LDS time of the sampler -- and the 8 values a lane needs for its MFMA B operand
 //     (k = 8 channels of one tap) arrive already in k order.  The window DMA moves whole 1536-byte window rows.
 //   * PRODUCTS: NPROD = 9 is the exact bf16x9 contraction of round 1 (every fp32 operand split exactly into three
-//     bf16 terms, all nine partial products); NPROD = 6 drops the three products below 2^-23 of the result
-//     (mid*lo, lo*mid, lo*lo): per product that is at most 2 * 2^-24 relative, the size of ONE fp32 rounding, and a
+//     bf16 terms, all nine partial products); NPROD = 6 drops the three smallest products
+//     (mid*lo, lo*mid, lo*lo): each of the first two is below 2^-22 of x*w, the three together below 2^-21 = 8 * 2^-24
+//     relative per product (not 2^-23 / one fp32 rounding, as this comment used to say), and a
 //     third less matrix work.  Both are fp32-faithful; tests compare both with an fp64 evaluation.
 //   * persistent workgroups over a flattened (tile, group) sequence: the window / weight DMA of the next tile's first
 //     group runs under the last group of the current one.

@@ -994,7 +994,7 @@ def dcnv2_il(x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], wei
     """DCNv2 (3x3, stride 1, pad 1) on an IL8 input.  heads=False: `offset_or_heads` / `mask` as mmcv's offset (n,18D,h,w)
     and mask (n,9D,h,w).  heads=True: `offset_or_heads` is the (n,15D,h,w) output of AdaptBlockOffset's three 5x5 heads and
     the kernel applies networks.py:302-315 (affine -> offsets, sigmoid) itself.  nprod: 9 = exact bf16x9, 6 = the three
-    products below 2^-23 dropped."""
+    smallest products dropped (together below 2^-21 of each product x * w: DESIGN.md 4a)."""
     x_il8 = _chk(x_il8, "x_il8")
     n, oct_, h, w, e = x_il8.shape
     if e != 8:
@@ -1196,7 +1196,8 @@ def dcnv2_il16(x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], w
 # How DCNv2 runs (fp32 tensors in and out in every mode):
 #   "il6" (default) = the round-2 hot-path kernel eavsr_dcnv2_il_f32: IL8 input layout, both fp32 operands split exactly into
 #              three bf16 terms, the six partial products that matter on the bf16 MFMA, fp32 accumulation (the three dropped
-#              products are < 2^-23 of the result each: one fp32 rounding).  Inside MultiAdSTN (inference) it is fed by the
+#              products are < 2^-21 of their product x * w together, mid*lo and lo*mid < 2^-22 each: eight units of 2^-24, not
+#              "one fp32 rounding" -- DESIGN.md 4a, tests/product_probe.py).  Inside MultiAdSTN (inference) it is fed by the
 #              paired warp (IL8 output) and by the predictor's head channels directly (affine -> offsets and the mask sigmoid
 #              happen in the kernel); a plain modulated_deform_conv2d call converts its NCHW input first.
 #   "il9"    = the same kernel with all nine partial products (exact operands, only the fp32 accumulation rounds)

@@ -127,8 +127,8 @@ int eavsr_pack_dcn_weight_x9(const float* weight, void* weight_x9, int32_t cout,
  *           1: `offset_or_heads` is the (n, 15*dg, h, w) output of AdaptBlockOffset's three 5x5 convolutions
  *              (transform g*4+{0..3}, translation 4dg + g*2+{0,1}, mask logits 6dg + g*9+k) and the kernel applies
  *              networks.py:302-315 itself (offset = T.R - R + t, mask = sigmoid): de_offset / mask never exist in HBM.
- *   nprod   9: exact bf16x9 contraction; 6: the three partial products below 2^-23 of the result are dropped
- *           (error per product <= one fp32 rounding).
+ *   nprod   9: exact bf16x9 contraction; 6: the three smallest partial products (mid*lo, lo*mid, lo*lo) are dropped:
+ *           together below 2^-21 of each product x * w.
  * weight_x9 from eavsr_pack_dcn_weight_x9.  Requires (cin/dg) % 8 == 0, 16-byte aligned x_il8; any h, w. */
 int eavsr_nchw_to_il8_f32(const float* x, float* out_il8, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
 int eavsr_dcnv2_il_f32(const float* x_il8, const float* offset_or_heads, const float* mask, const void* weight_x9,

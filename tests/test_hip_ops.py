@@ -1240,8 +1240,8 @@ def test_dcnv2_il2_takes_masks_activated_by_the_heads_convolution(ops, cuda):
 
 
 def test_dcnv2_il_error_against_fp64(ops, cuda):
-    """x9 keeps every partial product (exact operands, fp32 accumulation); x6 drops the three products below 2^-23 of the
-    result.  Against an fp64 evaluation both must be as accurate as the native fp32-MFMA kernel."""
+    """x9 keeps every partial product (exact operands, fp32 accumulation); x6 drops the three products below 2^-21 of
+    each product together (tests/product_probe.py).  Against an fp64 evaluation both must be as accurate as the native fp32-MFMA kernel."""
     x, off, mask, wt, b = _dcn_inputs(2, 64, 32, 64, 64, 8, 1.5, seed=10)
     x = x * 3.0 + 0.5
     ref64 = O.dcnv2(x.double(), off.double(), mask.double(), wt.double(), b.double(), 1, 1, 1, 1, 8)
