@@ -161,12 +161,10 @@ _dgrad_cache = WeightCache()
 
 
 def _dgrad_weight(ws, c0: int, cs: int) -> Tensor:
-    hit = _dgrad_cache.lookup(ws, (c0, cs))
-    if hit is not None:
-        return hit
-    W = ws[0] if len(ws) == 1 else torch.cat(ws, 0)
-    wt = W.detach()[:, c0:c0 + cs].flip(2, 3).transpose(0, 1).contiguous()   # (cs, cout, k, k)
-    return _dgrad_cache.store(ws, (c0, cs), wt)
+    def make():
+        W = ws[0] if len(ws) == 1 else torch.cat(ws, 0)
+        return W.detach()[:, c0:c0 + cs].flip(2, 3).transpose(0, 1).contiguous()   # (cs, cout, k, k)
+    return _dgrad_cache.derive(ws, (c0, cs), make)
 
 
 def _train_precision(ws, srcs) -> str:
@@ -307,11 +305,9 @@ _dcn_wt_cache = WeightCache()
 
 def _dcn_wt(weight: Tensor) -> Tensor:
     """(cin * 9, cout, 1, 1): the DCNv2 weight as the 1x1 convolution that maps dOut to the column gradients; once per weight version"""
-    hit = _dcn_wt_cache.lookup((weight,))
-    if hit is not None:
-        return hit
     cout, cin = int(weight.shape[0]), int(weight.shape[1])
-    return _dcn_wt_cache.store((weight,), None, weight.detach().reshape(cout, cin * 9).t().contiguous().view(cin * 9, cout, 1, 1))
+    return _dcn_wt_cache.derive((weight,), None,
+                                lambda: weight.detach().reshape(cout, cin * 9).t().contiguous().view(cin * 9, cout, 1, 1))
 
 
 class _DcnFn(Function):

@@ -10,7 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -296,29 +296,102 @@ def flow_warp_single(x: Tensor, flow: Tensor, flow2: Optional[Tensor] = None, il
 # ------------------------------------------------------------------------------------------
 # packed conv weights (cached per parameter version)
 # ------------------------------------------------------------------------------------------
-pack_cache = WeightCache()
+# One cache per form, under the name tests and tools know it by.  The exact bf16-split forms (_conv7_pack_cache) and the one-plane
+# forms of the bf16 training mode (_bf16_pack_cache) never share one, whatever the mode was when either was packed.
+pack_cache, _smallco_pack_cache, _conv7_pack_cache, _bf16_pack_cache = WeightCache(), WeightCache(), WeightCache(), WeightCache()
+_h16g_pack_cache, _h16x1_pack_cache, _il2_pack_cache, _il16_pack_cache = WeightCache(), WeightCache(), WeightCache(), WeightCache()
+_x9_pack_cache, _wino_pack_cache, _lpips_pack_cache, _h16_pack_cache = WeightCache(), WeightCache(), WeightCache(), WeightCache()
+_h16_pack5_cache, _pwc_pack_cache = WeightCache(), WeightCache()
+
+
+class _Form(NamedTuple):
+    """One packed form of a conv weight.  The entry points are written with their scalar arguments, "name cout cin k code" (`k` the
+    kernel size, `code` the h16_code of a 16-bit form); a pack entry point takes them between (weight, packed) and the stream."""
+    cache: WeightCache
+    tag: Optional[str]          # what the caller's variant is, and the cache tag: None, "code", "kind", or "dgrad" (True -> the "_dgrad" pack entry point, tag "dgrad")
+    many: Optional[str]         # None: one weight.  A list stacked along cout: "cat" = concatenated for the pack alone, "wcat" = through _cat_weights (cached)
+    shape: Optional[tuple]      # accepted (cout, cin, k) of a square kernel, each None (any), a number or a container of numbers; None: not checked here
+    size: Union[str, int]       # the entry point that sizes the buffer, or the element count itself
+    in_bytes: bool              # `size` counts bytes (else elements of `dtype`)
+    dtype: Optional[torch.dtype]      # of the buffer; None: the 16-bit type of `code`
+    pack: str
+    error: Optional[str]        # the NotImplementedError of a weight outside `shape` or of a size <= 0 ({s}: its shape); None: nothing is checked
+    chk: Optional[Callable] = _chk    # the weight's own check: _chk, _lp (no copy), None (checked by the caller)
+
+
+_S3 = (None, None, 3)
+_FORMS = {
+    "f32": _Form(pack_cache, None, "cat", (None, None, None), "eavsr_packed_weight_elems cout cin k", False, torch.float32,
+                 "eavsr_pack_conv_weight_f32 cout cin k", "conv weight shape {s} unsupported (square kernels only)"),
+    "smallco": _Form(_smallco_pack_cache, None, "wcat", None, "eavsr_smallco_packed_elems cout cin", False, torch.float32,
+                     "eavsr_pack_smallco_weight cout cin", None),
+    "x6": _Form(_conv7_pack_cache, "dgrad", "wcat", None, "eavsr_conv_weight_x6_bytes k cout cin", True, torch.uint8,
+                "eavsr_pack_conv_weight_x6 k cout cin", None),
+    "bf16x1": _Form(_bf16_pack_cache, "dgrad", "wcat", None, "eavsr_conv_weight_bf16x1_bytes k cout cin", True, torch.uint8,
+                    "eavsr_pack_conv_weight_bf16x1 k cout cin", None),
+    "h16g": _Form(_h16g_pack_cache, "code", "wcat", None, "eavsr_conv3x3_h16g_weight_bytes cout cin", True, torch.uint8,
+                  "eavsr_pack_conv3x3_h16g cout cin code", None),
+    "h16x1": _Form(_h16x1_pack_cache, "code", "wcat", None, "eavsr_conv_weight_h16x1_bytes k cout cin", True, torch.uint8,
+                   "eavsr_pack_conv_weight_h16x1 k cout cin code", None),
+    "il2": _Form(_il2_pack_cache, None, None, _S3, "eavsr_dcn_weight_il2_bytes cout cin", True, torch.int32,
+                 "eavsr_pack_dcn_weight_il2 cout cin", "il2 weight shape {s} unsupported"),
+    "il16": _Form(_il16_pack_cache, "code", None, _S3, "eavsr_dcn_il16_weight_bytes cout cin", True, torch.int32,
+                  "eavsr_pack_dcn_il16_weight cout cin code", "dcnv2_il16 weight shape {s} unsupported (3x3 only)"),
+    "x9": _Form(_x9_pack_cache, None, "cat", _S3, "eavsr_dcn_weight_x9_bytes cout cin", True, torch.int32,
+                "eavsr_pack_dcn_weight_x9 cout cin", "bf16x9 weight shape {s} unsupported (the bf16x9 kernels are 3x3)"),
+    "wino_f2": _Form(_wino_pack_cache, "kind", "cat", _S3, "eavsr_wino_weight_elems cout cin", False, torch.float32,
+                     "eavsr_pack_conv_weight_wino cout cin", "winograd weight shape {s} unsupported"),
+    "wino_f4": _Form(_wino_pack_cache, "kind", "cat", _S3, "eavsr_wino4_weight_elems cout cin", False, torch.float32,
+                     "eavsr_pack_conv_weight_wino4 cout cin", "winograd weight shape {s} unsupported"),
+    "wino_f5": _Form(_wino_pack_cache, "kind", "cat", (None, None, 5), "eavsr_wino4_weight_elems cout cin", False, torch.float32,
+                     "eavsr_pack_conv_weight_wino5x5 cout cin", "winograd weight shape {s} unsupported"),
+    "lpips": _Form(_lpips_pack_cache, None, None, (None, None, None), "eavsr_lpips_conv_weight_elems cout cin k", False, torch.float32,
+                   "eavsr_lpips_pack_conv_f32 cout cin k", "lpips_conv: weight shape {s} unsupported", lambda t, name: _lp(t, name)),
+    "h16": _Form(_h16_pack_cache, "code", None, (64, 64, 3), 64 * 576, False, None,
+                 "eavsr_pack_conv3x3_c64_h16 code", "the 16-bit backbone kernel is the 3x3 64->64 convolution"),
+    "h16_5x5": _Form(_h16_pack5_cache, "code", None, (range(129), 64, 5), "eavsr_conv5x5_c64_h16_weight_bytes", True, None,
+                     "eavsr_pack_conv5x5_c64_h16 cout code", "the 16-bit heads kernel is the 5x5 convolution 64 -> (<= 128) channels", None),
+    "pwc": _Form(_pwc_pack_cache, None, None, _S3, "eavsr_pwc_conv3x3_weight_elems cout cin", False, torch.float32,
+                 "eavsr_pwc_pack_conv3x3_f32 cout cin", "pwc_conv3x3: weight shape {s} unsupported (3x3 only)"),
+}
+
+
+def _packed(form: str, weights, variant=None):
+    """The packed form `form` of a weight (of a list of them where the form takes one), cached per weight objects and versions and
+    verified by identity: on a miss the weight is checked, the library sizes the buffer and its pack kernel fills it on the
+    weight's device and current stream, right in front of the store."""
+    f = _FORMS[form]
+    sources = weights if f.many else (weights,)
+    tag = ("dgrad" if variant else None) if f.tag == "dgrad" else variant
+
+    def make():
+        w = sources[0] if len(sources) == 1 else _cat_weights(sources) if f.many == "wcat" else torch.cat([x.detach() for x in sources], 0)
+        w = w if f.chk is None else f.chk(w.detach(), "weight")
+        s = tuple(int(x) for x in w.shape)
+        if f.error is not None and not (len(s) == 4 and s[2] == s[3] and all(
+                p is None or (x == p if isinstance(p, int) else x in p) for p, x in zip(f.shape, s))):
+            raise NotImplementedError(f.error.format(s=s))
+        v = {"cout": s[0], "cin": s[1], "k": s[-1], "code": variant}
+        size, (pack, *pack_args) = f.size, f.pack.split()
+        if isinstance(size, str):
+            name, *args = size.split()
+            sized = dict(v, cout=s[1], cin=s[0]) if tag == "dgrad" else v      # as the input-gradient convolution's (cin, cout, k, k) weight
+            size = int(getattr(lib(), name)(*[sized[a] for a in args]))
+            if f.error is not None and size <= 0:
+                raise NotImplementedError(f.error.format(s=s))
+        if tag == "dgrad":
+            pack += "_dgrad"      # transposed and flipped by the pack kernel itself: no materialised copy
+        dtype = _H16_TORCH[variant] if f.dtype is None else f.dtype
+        packed = torch.empty(size // dtype.itemsize if f.in_bytes else size, device=w.device, dtype=dtype)
+        with _DeviceOf(w):
+            N.check(getattr(lib(), pack)(_p(w), _p(packed), *[v[a] for a in pack_args], _stream(w)), pack[len("eavsr_"):])
+        return packed
+    return f.cache.derive(sources, tag, make)
 
 
 def _packed_f32(weights: Sequence[Tensor]) -> Tensor:
-    """the packed form of a conv weight (or of several stacked along cout) for eavsr_conv2d_f32; cached per weight objects and versions"""
-    hit = pack_cache.lookup(weights)
-    if hit is not None:
-        return hit
-    w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
-    w = _chk(w.detach(), "weight")
-    cout, cin, kh, kw = w.shape
-    if kh != kw:
-        raise NotImplementedError("square kernels only")
-    elems = lib().eavsr_packed_weight_elems(cout, cin, kh)
-    if elems <= 0:
-        raise NotImplementedError(f"conv weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_conv_weight_f32(_p(w), _p(packed), cout, cin, kh, _stream(w)), "pack_conv_weight")
-    return pack_cache.store(weights, None, packed)
-
-
-pack_cache.get = _packed_f32      # tools/ call it by this name: ops.pack_cache.get(weights)
+    """the packed form of a conv weight (or of several stacked along cout) for eavsr_conv2d_f32"""
+    return _packed("f32", weights)
 
 
 def _cat_bias(biases: Sequence[Optional[Tensor]]) -> Optional[Tensor]:
@@ -333,10 +406,7 @@ _bias_cache = WeightCache()
 def _bias_of(biases: Sequence[Optional[Tensor]]) -> Optional[Tensor]:
     if len(biases) == 1:
         return None if biases[0] is None else _chk(biases[0].detach(), "bias")
-    hit = _bias_cache.lookup(biases)
-    if hit is not None:
-        return hit
-    return _bias_cache.store(biases, None, _chk(_cat_bias(biases), "bias"))
+    return _bias_cache.derive(biases, None, lambda: _chk(_cat_bias(biases), "bias"))
 
 
 _wcat_cache = WeightCache()
@@ -346,10 +416,7 @@ def _cat_weights(weights: Sequence[Tensor]) -> Tensor:
     """cat(weights, 0) in the original layout, cached per (object, version) like the packed weights"""
     if len(weights) == 1:
         return _chk(weights[0].detach(), "weight")
-    hit = _wcat_cache.lookup(weights)
-    if hit is not None:
-        return hit
-    return _wcat_cache.store(weights, None, _chk(torch.cat([w.detach() for w in weights], 0), "weight"))
+    return _wcat_cache.derive(weights, None, lambda: _chk(torch.cat([w.detach() for w in weights], 0), "weight"))
 
 
 # Small-cout 3x3 convolutions (64 -> 6 / 18 -> 2 heads of the pyramid levels, conv_last): eavsr_conv3x3_smallco_lite_f32 wherever the
@@ -358,20 +425,11 @@ def _cat_weights(weights: Sequence[Tensor]) -> Tensor:
 # the step 240.0 -> 236.8 ms (DESIGN.md 4k).  EAVSR_SMALLCO=classic: round 2's 112-184-register kernels (the A/B reference).
 SMALLCO_LITE = os.environ.get("EAVSR_SMALLCO", "lite") != "classic"
 SMALLCO_LITE_MIN_TILES = 0
-_smallco_pack_cache = WeightCache()
 
 
 def _packed_smallco(weights: Sequence[Tensor]) -> Tensor:
-    """[ci][kx][block] form of a small-cout 3x3 weight (eavsr_pack_smallco_weight); cached per weight objects and versions"""
-    hit = _smallco_pack_cache.lookup(weights)
-    if hit is not None:
-        return hit
-    w = _chk(_cat_weights(weights).detach(), "weight")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    packed = torch.empty(lib().eavsr_smallco_packed_elems(cout, cin), device=w.device, dtype=torch.float32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_smallco_weight(_p(w), _p(packed), cout, cin, _stream(w)), "pack_smallco_weight")
-    return _smallco_pack_cache.store(weights, None, packed)
+    """[ci][kx][block] form of a small-cout 3x3 weight (eavsr_pack_smallco_weight)"""
+    return _packed("smallco", weights)
 
 
 # 7x7 convolutions (SPyNet's basic module) and the 5x5 heads of the predictor: "bf16x6" = eavsr_conv_f32x6 (fp32 operands split
@@ -379,29 +437,13 @@ def _packed_smallco(weights: Sequence[Tensor]) -> Tensor:
 # eavsr_conv2d_f32; 5x5: F(2x2,5x5)).  A/B switches.
 CONV7_MODE = os.environ.get("EAVSR_CONV7", "bf16x6")
 CONV5_MODE = os.environ.get("EAVSR_CONV5", "bf16x6")
-_conv7_pack_cache = WeightCache()
-
-
-def _packed_conv(cache, nbytes_fn: str, pack_fn: str, weights: Sequence[Tensor], dgrad: bool) -> Tensor:
-    """what _packed_conv_x6 and _packed_conv3_bf16 share: the library's byte count / pack / dgrad pack entry points by name"""
-    tag = "dgrad" if dgrad else None
-    hit = cache.lookup(weights, tag)
-    if hit is not None:
-        return hit
-    w = _chk(_cat_weights(weights).detach(), "weight")
-    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
-    name = pack_fn + ("_dgrad" if dgrad else "")
-    packed = torch.empty(getattr(lib(), nbytes_fn)(k, *((cin, cout) if dgrad else (cout, cin))), device=w.device, dtype=torch.uint8)
-    with _DeviceOf(w):
-        N.check(getattr(lib(), "eavsr_" + name)(_p(w), _p(packed), k, cout, cin, _stream(w)), name)
-    return cache.store(weights, tag, packed)
 
 
 def _packed_conv_x6(weights: Sequence[Tensor], dgrad: bool = False) -> Tensor:
     """A-operand form of a 7x7 / 5x5 / 3x3 weight (eavsr_pack_conv_weight_x6); cached per weight objects and versions.
     dgrad=True: the form of the INPUT-GRADIENT convolution of the (single) forward weight -- transposed and flipped by the pack
     kernel itself (eavsr_pack_conv_weight_x6_dgrad), no materialised copy."""
-    return _packed_conv(_conv7_pack_cache, "eavsr_conv_weight_x6_bytes", "pack_conv_weight_x6", weights, dgrad)
+    return _packed("x6", weights, dgrad)
 
 
 # The opt-in bf16 training mode (networks.set_train_precision / EAVSR_TRAIN_PRECISION): "fp32" (the default: every convolution
@@ -434,14 +476,10 @@ def deterministic_active() -> bool:
     return DETERMINISTIC or torch.are_deterministic_algorithms_enabled()
 
 
-# bf16 training mode: the one-plane packed forms (eavsr_pack_conv_weight_bf16x1*), a cache of their own -- never confused with the
-# exact forms of _conv7_pack_cache, whatever the mode was when either was packed
-_bf16_pack_cache = WeightCache()
-
-
 def _packed_conv3_bf16(weights: Sequence[Tensor], dgrad: bool = False) -> Tensor:
-    """_packed_conv_x6 for eavsr_conv3x3_bf16x1s: every value rounded once to bf16 (nearest even), one plane"""
-    return _packed_conv(_bf16_pack_cache, "eavsr_conv_weight_bf16x1_bytes", "pack_conv_weight_bf16x1", weights, dgrad)
+    """_packed_conv_x6 for eavsr_conv3x3_bf16x1s (the bf16 training mode): every value rounded once to bf16 (nearest even), one
+    plane (eavsr_pack_conv_weight_bf16x1*); in _bf16_pack_cache, never among the exact forms"""
+    return _packed("bf16x1", weights, dgrad)
 
 
 def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None) -> int:
@@ -450,8 +488,8 @@ def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None)
     form at its first use: what the training step calls once, in front of its forward (540 launches of 4.7 us on its one dependent
     chain otherwise).  precision (default: TRAIN_PRECISION, the mode the training convolutions run in): "bf16" packs the one-plane
     forms of the bf16 training mode instead (eavsr_pack_conv_weight_bf16x1_multi).  Returns the number of forms packed."""
-    bf16 = check_precision(TRAIN_PRECISION if precision is None else precision) == "bf16"
-    cache = _bf16_pack_cache if bf16 else _conv7_pack_cache
+    f = _FORMS["bf16x1" if check_precision(TRAIN_PRECISION if precision is None else precision) == "bf16" else "x6"]
+    cache, nbytes_fn, multi = f.cache, f.size.split()[0], f.pack.split()[0] + "_multi"
     todo = []
     for w in weights:
         if tuple(w.shape) != (64, 64, 3, 3) or not w.is_cuda or not w.is_contiguous() or w.dtype != torch.float32:
@@ -462,17 +500,14 @@ def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None)
     if not todo:
         return 0
     dev = todo[0][0].device
-    nbytes = int(lib().eavsr_conv_weight_bf16x1_bytes(3, 64, 64) if bf16 else lib().eavsr_conv_weight_x6_bytes(3, 64, 64))
+    nbytes = int(getattr(lib(), nbytes_fn)(3, 64, 64))
     store = torch.empty((len(todo), nbytes), device=dev, dtype=torch.uint8)
     cnt = len(todo)
     srcs = (C.c_void_p * cnt)(*[w.detach().data_ptr() for w, _ in todo])
     dsts = (C.c_void_p * cnt)(*[store[i].data_ptr() for i in range(cnt)])
     trs = (C.c_int32 * cnt)(*[int(dg) for _, dg in todo])
     with _DeviceOf(todo[0][0]):
-        if bf16:
-            N.check(lib().eavsr_pack_conv_weight_bf16x1_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_bf16x1_multi")
-        else:
-            N.check(lib().eavsr_pack_conv_weight_x6_multi(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), "pack_conv_weight_x6_multi")
+        N.check(getattr(lib(), multi)(srcs, dsts, trs, cnt, 3, 64, _stream(todo[0][0])), multi[len("eavsr_"):])
     for i, (w, dg) in enumerate(todo):
         cache.store((w,), "dgrad" if dg else None, store[i])
     return cnt
@@ -483,7 +518,6 @@ def prepack_conv3_x6(weights: Sequence[Tensor], precision: Optional[str] = None)
 # type (fp32 NCHW in and out).  Set by networks.set_backbone_dtype (EAVSR_CONV3_16BIT=0 keeps these convolutions fp32: A/B switch).
 CONV3_H16 = None
 CONV3_H16_ENABLED = os.environ.get("EAVSR_CONV3_16BIT", "1") == "1"
-_h16g_pack_cache = WeightCache()
 
 
 def set_conv3_h16(dtype) -> None:
@@ -494,33 +528,16 @@ def set_conv3_h16(dtype) -> None:
 
 
 def _packed_h16g(weights: Sequence[Tensor], code: int) -> Tensor:
-    hit = _h16g_pack_cache.lookup(weights, code)
-    if hit is not None:
-        return hit
-    w = _chk(_cat_weights(weights).detach(), "weight")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    packed = torch.empty(int(lib().eavsr_conv3x3_h16g_weight_bytes(cout, cin)), device=w.device, dtype=torch.uint8)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_conv3x3_h16g(_p(w), _p(packed), cout, cin, code, _stream(w)), "pack_conv3x3_h16g")
-    return _h16g_pack_cache.store(weights, code, packed)
+    return _packed("h16g", weights, code)
 
 
 # SPyNet's 7x7 layers with >= 16 output channels in the 16-bit modes (one operand plane of csrc/conv_x6.hip); EAVSR_CONV7_16BIT=0
 # keeps them on the exact bf16x6 form (A/B switch)
 CONV7_H16_ENABLED = os.environ.get("EAVSR_CONV7_16BIT", "1") == "1"
-_h16x1_pack_cache = WeightCache()
 
 
 def _packed_h16x1(weights: Sequence[Tensor], code: int) -> Tensor:
-    hit = _h16x1_pack_cache.lookup(weights, code)
-    if hit is not None:
-        return hit
-    w = _chk(_cat_weights(weights).detach(), "weight")
-    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
-    packed = torch.empty(lib().eavsr_conv_weight_h16x1_bytes(k, cout, cin), device=w.device, dtype=torch.uint8)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_conv_weight_h16x1(_p(w), _p(packed), k, cout, cin, code, _stream(w)), "pack_conv_weight_h16x1")
-    return _h16x1_pack_cache.store(weights, code, packed)
+    return _packed("h16x1", weights, code)
 
 
 # ------------------------------------------------------------------------------------------
@@ -587,10 +604,7 @@ _dgrad_w_cache = WeightCache()
 def dgrad_weight(w: Tensor) -> Tensor:
     """(cin, cout, k, k) transposed and flipped copy of a forward weight: the weight of its input-gradient convolution; cached
     per weight object and version"""
-    hit = _dgrad_w_cache.lookup((w,))
-    if hit is not None:
-        return hit
-    return _dgrad_w_cache.store((w,), None, w.detach().flip(2, 3).transpose(0, 1).contiguous())
+    return _dgrad_w_cache.derive((w,), None, lambda: w.detach().flip(2, 3).transpose(0, 1).contiguous())
 
 
 class BorderPieces:
@@ -989,6 +1003,28 @@ def to_il8(x: Tensor) -> Tensor:
     return out
 
 
+def _dcn_il_args(op: str, x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], weight: Tensor, bias: Optional[Tensor],
+                 deform_groups: int, heads: bool):
+    """what `dcnv2_il` and `dcnv2_il16` ask of their arguments beyond the input's dtype (checked by the caller): the IL8 shape, the
+    weight's channels, offset / mask or heads against it; (n, cin, h, w, cout, D, offset_or_heads, mask, bias) as the launch takes them"""
+    n, oct_, h, w, e = x_il8.shape
+    if e != 8:
+        raise ValueError(f"{op}: input must be IL8 (n, c/8, h, w, 8)")
+    cin, cout, D = oct_ * 8, int(weight.shape[0]), int(deform_groups)
+    if tuple(weight.shape[1:]) != (cin, 3, 3):
+        raise ValueError(f"{op}: weight / input channel mismatch")
+    oh = _chk(offset_or_heads, "offset_or_heads")
+    if heads:
+        if tuple(oh.shape) != (n, 15 * D, h, w):
+            raise ValueError(f"{op}: heads shape {tuple(oh.shape)} != {(n, 15 * D, h, w)}")
+        mask = None
+    else:
+        mask = _chk(mask, "mask")
+        if tuple(oh.shape) != (n, 18 * D, h, w) or tuple(mask.shape) != (n, 9 * D, h, w):
+            raise ValueError(f"{op}: offset / mask shape")
+    return n, cin, h, w, cout, D, oh, mask, None if bias is None else _chk(bias.detach(), "bias")
+
+
 def dcnv2_il(x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], weight: Tensor, bias: Optional[Tensor],
              deform_groups: int, nprod: int = 6, heads: bool = False, mask_activated: bool = False) -> Tensor:
     """DCNv2 (3x3, stride 1, pad 1) on an IL8 input.  heads=False: `offset_or_heads` / `mask` as mmcv's offset (n,18D,h,w)
@@ -996,24 +1032,7 @@ def dcnv2_il(x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], wei
     the kernel applies networks.py:302-315 (affine -> offsets, sigmoid) itself.  nprod: 9 = exact bf16x9, 6 = the three
     smallest products dropped (together below 2^-21 of each product x * w: DESIGN.md 4a)."""
     x_il8 = _chk(x_il8, "x_il8")
-    n, oct_, h, w, e = x_il8.shape
-    if e != 8:
-        raise ValueError("dcnv2_il: input must be IL8 (n, c/8, h, w, 8)")
-    cin = oct_ * 8
-    cout = int(weight.shape[0])
-    if tuple(weight.shape[1:]) != (cin, 3, 3):
-        raise ValueError("dcnv2_il: weight / input channel mismatch")
-    oh = _chk(offset_or_heads, "offset_or_heads")
-    D = int(deform_groups)
-    if heads:
-        if tuple(oh.shape) != (n, 15 * D, h, w):
-            raise ValueError(f"dcnv2_il: heads shape {tuple(oh.shape)} != {(n, 15 * D, h, w)}")
-        mask = None
-    else:
-        mask = _chk(mask, "mask")
-        if tuple(oh.shape) != (n, 18 * D, h, w) or tuple(mask.shape) != (n, 9 * D, h, w):
-            raise ValueError("dcnv2_il: offset / mask shape")
-    b = None if bias is None else _chk(bias.detach(), "bias")
+    n, cin, h, w, cout, D, oh, mask, b = _dcn_il_args("dcnv2_il", x_il8, offset_or_heads, mask, weight, bias, deform_groups, heads)
     if heads and _dcn_probe is not None:
         _dcn_probe.append(dcn_offset_stats(oh, D))
     impl = DCN_IL_IMPL
@@ -1106,44 +1125,13 @@ def set_dcn_il_impl(impl: str) -> None:
     DCN_IL_IMPL = impl
 
 
-_il2_pack_cache = WeightCache()
-
-
 def _packed_dcn_il2(weight: Tensor) -> Tensor:
-    """Pre-split (3 x bf16) weight slab of a 3x3 DCNv2 weight in the pair-step order of eavsr_dcnv2_il2_f32; cached per weight
-    object and version, verified by identity."""
-    hit = _il2_pack_cache.lookup((weight,))
-    if hit is not None:
-        return hit
-    w = _chk(weight.detach(), "weight")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    nbytes = lib().eavsr_dcn_weight_il2_bytes(cout, cin)
-    if nbytes <= 0 or tuple(w.shape[2:]) != (3, 3):
-        raise NotImplementedError(f"il2 weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.int32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_dcn_weight_il2(_p(w), _p(packed), cout, cin, _stream(w)), "pack_dcn_weight_il2")
-    return _il2_pack_cache.store((weight,), None, packed)
-
-
-_il16_pack_cache = WeightCache()
+    """Pre-split (3 x bf16) weight slab of a 3x3 DCNv2 weight in the pair-step order of eavsr_dcnv2_il2_f32"""
+    return _packed("il2", weight)
 
 
 def _packed_il16(weight: Tensor, code: int) -> Tensor:
-    hit = _il16_pack_cache.lookup((weight,), code)
-    if hit is not None:
-        return hit
-    w = _chk(weight.detach(), "weight")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    if tuple(w.shape[2:]) != (3, 3):
-        raise NotImplementedError("dcnv2_il16 is 3x3")
-    nbytes = lib().eavsr_dcn_il16_weight_bytes(cout, cin)
-    if nbytes <= 0:
-        raise NotImplementedError(f"dcnv2_il16 weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.int32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_dcn_il16_weight(_p(w), _p(packed), cout, cin, code, _stream(w)), "pack_dcn_il16_weight")
-    return _il16_pack_cache.store((weight,), code, packed)
+    return _packed("il16", weight, code)
 
 
 def to_il8_h16(x: Tensor, dtype) -> Tensor:
@@ -1165,23 +1153,8 @@ def dcnv2_il16(x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], w
     """DCNv2 (3x3, stride 1, pad 1) on a 16-bit IL8 input (bf16 / fp16 samples and weights, fp32 blend and accumulation,
     fp32 output); arguments as `dcnv2_il`."""
     x_il8 = _chk_h16(x_il8, "x_il8")
-    n, oct_, h, w, e = x_il8.shape
-    if e != 8:
-        raise ValueError("dcnv2_il16: input must be IL8 (n, c/8, h, w, 8)")
+    n, cin, h, w, cout, D, oh, mask, b = _dcn_il_args("dcnv2_il16", x_il8, offset_or_heads, mask, weight, bias, deform_groups, heads)
     code = h16_code(x_il8.dtype)
-    cin, cout, D = oct_ * 8, int(weight.shape[0]), int(deform_groups)
-    if tuple(weight.shape[1:]) != (cin, 3, 3):
-        raise ValueError("dcnv2_il16: weight / input channel mismatch")
-    oh = _chk(offset_or_heads, "offset_or_heads")
-    if heads:
-        if tuple(oh.shape) != (n, 15 * D, h, w):
-            raise ValueError(f"dcnv2_il16: heads shape {tuple(oh.shape)} != {(n, 15 * D, h, w)}")
-        mask = None
-    else:
-        mask = _chk(mask, "mask")
-        if tuple(oh.shape) != (n, 18 * D, h, w) or tuple(mask.shape) != (n, 9 * D, h, w):
-            raise ValueError("dcnv2_il16: offset / mask shape")
-    b = None if bias is None else _chk(bias.detach(), "bias")
     wp = _packed_il16(weight, code)
     out = torch.empty((n, cout, h, w), device=x_il8.device, dtype=torch.float32)
     st = _stream(out)
@@ -1215,27 +1188,9 @@ def set_dcn_mode(mode: str) -> None:
     DCN_MODE = mode
 
 
-_x9_pack_cache = WeightCache()
-
-
 def _packed_x9(weights: Sequence[Tensor]) -> Tensor:
-    """Pre-split (3 x bf16) weight slab of a 3x3 weight -- or of several stacked along cout -- for the bf16x9 kernels;
-    cached per weight objects and versions, verified by identity (as pack_cache)."""
-    hit = _x9_pack_cache.lookup(weights)
-    if hit is not None:
-        return hit
-    w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
-    w = _chk(w.detach(), "weight")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    if tuple(w.shape[2:]) != (3, 3):
-        raise NotImplementedError("bf16x9 kernels are 3x3")
-    nbytes = lib().eavsr_dcn_weight_x9_bytes(cout, cin)
-    if nbytes <= 0:
-        raise NotImplementedError(f"bf16x9 weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.int32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_dcn_weight_x9(_p(w), _p(packed), cout, cin, _stream(w)), "pack_dcn_weight_x9")
-    return _x9_pack_cache.store(weights, None, packed)
+    """Pre-split (3 x bf16) weight slab of a 3x3 weight -- or of several stacked along cout -- for the bf16x9 kernels"""
+    return _packed("x9", weights)
 
 
 def _packed_dcn_x9(weight: Tensor) -> Tensor:
@@ -1297,30 +1252,13 @@ def modes(conv: Optional[str] = None, dcn: Optional[str] = None, dcn_il_impl: Op
         set_dcn_il_impl(prev[2])
 
 
-_wino_pack_cache = WeightCache()
-
-
 def _packed_wino(weights: Sequence[Tensor], four: bool = False, kind: Optional[str] = None) -> Tensor:
     """G g G^T of a conv weight (or of several stacked along cout); kind "f2" = F(2x2, 3x3), "f4" = F(4x4, 3x3),
-    "f5" = F(2x2, 5x5); cached per weight objects and versions."""
+    "f5" = F(2x2, 5x5)"""
     kind = kind or ("f4" if four else "f2")
     if kind == "f2":
         require_lab("Winograd F(2x2,3x3)")
-    hit = _wino_pack_cache.lookup(weights, kind)
-    if hit is not None:
-        return hit
-    w = weights[0] if len(weights) == 1 else torch.cat([x.detach() for x in weights], 0)
-    w = _chk(w.detach(), "weight")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    elems = (lib().eavsr_wino_weight_elems if kind == "f2" else lib().eavsr_wino4_weight_elems)(cout, cin)
-    if elems <= 0 or tuple(w.shape[2:]) != ((5, 5) if kind == "f5" else (3, 3)):
-        raise NotImplementedError(f"winograd weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
-    with _DeviceOf(w):
-        fn = getattr(lib(), {"f2": "eavsr_pack_conv_weight_wino", "f4": "eavsr_pack_conv_weight_wino4",
-                             "f5": "eavsr_pack_conv_weight_wino5x5"}[kind])
-        N.check(fn(_p(w), _p(packed), cout, cin, _stream(w)), "pack_conv_weight_wino")
-    return _wino_pack_cache.store(weights, kind, packed)
+    return _packed("wino_" + kind, weights, kind)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2318,9 +2256,6 @@ def png_unfilter(rows: Tensor, c: int, channels: int = 3, out: Optional[Tensor] 
 # ------------------------------------------------------------------------------------------
 # LPIPS (AlexNet), the report's third column  (psnr_total.py:27-35; csrc/lpips.hip)
 # ------------------------------------------------------------------------------------------
-_lpips_pack_cache = WeightCache()
-
-
 def _lp(t: Tensor, name: str, dim: Optional[int] = 4) -> Tensor:
     """an fp32 contiguous GPU tensor, taken as it is: the LPIPS entry points copy nothing"""
     if not isinstance(t, torch.Tensor):
@@ -2337,20 +2272,8 @@ def _lp(t: Tensor, name: str, dim: Optional[int] = 4) -> Tensor:
 
 
 def _packed_lpips_conv(weight: Tensor) -> Tensor:
-    """[k^2][cin padded to 4][cout] form of a (cout, cin, k, k) weight for eavsr_lpips_conv1_f32 / eavsr_lpips_conv_f32; cached per
-    weight object and version, verified by identity."""
-    hit = _lpips_pack_cache.lookup((weight,))
-    if hit is not None:
-        return hit
-    w = _lp(weight.detach(), "weight")
-    cout, cin, k, k2 = (int(v) for v in w.shape)
-    elems = lib().eavsr_lpips_conv_weight_elems(cout, cin, k) if k == k2 else -1
-    if elems <= 0:
-        raise NotImplementedError(f"lpips_conv: weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_lpips_pack_conv_f32(_p(w), _p(packed), cout, cin, k, _stream(w)), "lpips_pack_conv")
-    return _lpips_pack_cache.store((weight,), None, packed)
+    """[k^2][cin padded to 4][cout] form of a (cout, cin, k, k) weight for eavsr_lpips_conv1_f32 / eavsr_lpips_conv_f32"""
+    return _packed("lpips", weight)
 
 
 def lpips_conv1(sr: Tensor, hr: Tensor, weight: Tensor, bias: Tensor, shift: Tensor, scl: Tensor, scale: float = 255.0) -> Tensor:
@@ -3008,21 +2931,8 @@ def from_nhwc_h16(x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
     return out
 
 
-_h16_pack_cache = WeightCache()
-
-
 def _packed_h16(weight: Tensor, code: int) -> Tensor:
-    hit = _h16_pack_cache.lookup((weight,), code)
-    if hit is not None:
-        return hit
-    w = _chk(weight.detach(), "weight")
-    if tuple(w.shape) != (64, 64, 3, 3):
-        raise NotImplementedError("the 16-bit backbone kernel is the 3x3 64->64 convolution")
-    packed = torch.empty(64 * 576, device=w.device, dtype=_H16_TORCH[code])
-    st = _stream(w)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pack_conv3x3_c64_h16(_p(w), _p(packed), code, st), "pack_conv3x3_c64_h16")
-    return _h16_pack_cache.store((weight,), code, packed)
+    return _packed("h16", weight, code)
 
 
 def conv3x3_c64_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], relu: bool = False, chan_partial: bool = False,
@@ -3186,20 +3096,19 @@ def _packed_h16_ps2(weight: Tensor, bias: Optional[Tensor], code: int):
     """(256, 64, 3, 3) weight of a conv + PixelShuffle(2) stage -> four packed 64 -> 64 matrices (slice k = 2 dy + dx: the output
     channels 4 c + k as channel c) and the bias in the same order (4 x 64)"""
     sources = (weight,) if bias is None else (weight, bias)
-    hit = _h16_ps_cache.lookup(sources, code)
-    if hit is not None:
-        return hit
-    w = _chk(weight.detach(), "weight")
-    if tuple(w.shape) != (256, 64, 3, 3):
-        raise NotImplementedError("the 16-bit pixel-shuffle stage is the 3x3 64 -> 256 convolution")
-    sl = w.view(64, 4, 64, 3, 3).permute(1, 0, 2, 3, 4).contiguous()      # [k][c][ci][3][3]
-    packed = torch.empty(4, 64 * 576, device=w.device, dtype=_H16_TORCH[code])
-    st = _stream(w)
-    with _DeviceOf(w):
-        for k in range(4):
-            N.check(lib().eavsr_pack_conv3x3_c64_h16(_p(sl[k]), _p(packed[k]), code, st), "pack_conv3x3_c64_h16")
-    b4 = None if bias is None else _chk(bias.detach(), "bias").view(64, 4).t().contiguous()
-    return _h16_ps_cache.store(sources, code, (packed, b4))
+
+    def make():
+        w = _chk(weight.detach(), "weight")
+        if tuple(w.shape) != (256, 64, 3, 3):
+            raise NotImplementedError("the 16-bit pixel-shuffle stage is the 3x3 64 -> 256 convolution")
+        sl = w.view(64, 4, 64, 3, 3).permute(1, 0, 2, 3, 4).contiguous()      # [k][c][ci][3][3]
+        packed = torch.empty(4, 64 * 576, device=w.device, dtype=_H16_TORCH[code])
+        st = _stream(w)
+        with _DeviceOf(w):
+            for k in range(4):
+                N.check(lib().eavsr_pack_conv3x3_c64_h16(_p(sl[k]), _p(packed[k]), code, st), "pack_conv3x3_c64_h16")
+        return packed, None if bias is None else _chk(bias.detach(), "bias").view(64, 4).t().contiguous()
+    return _h16_ps_cache.derive(sources, code, make)
 
 
 def conv3x3_c64_h16_act(x: Tensor, weight: Tensor, bias: Optional[Tensor], act: Optional[str] = None, slope: float = 0.0,
@@ -3234,10 +3143,9 @@ def conv3x3_c64to3_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], residu
     n, h, w, c = x.shape
     if c != 64 or tuple(weight.shape) != (3, 64, 3, 3):
         raise NotImplementedError("the 16-bit conv_last kernel is the 3x3 64 -> 3 convolution")
-    wt = _h16_last_cache.lookup((weight,), x.dtype)
-    if wt is None:      # [ky][kx][8-channel block][co][8 channels], rounded to the activation type (scalar loads in the kernel)
-        wt = _h16_last_cache.store((weight,), x.dtype,
-                                   _chk(weight.detach(), "weight").view(3, 8, 8, 3, 3).permute(3, 4, 1, 0, 2).contiguous().to(x.dtype))
+    # [ky][kx][8-channel block][co][8 channels], rounded to the activation type (scalar loads in the kernel)
+    wt = _h16_last_cache.derive((weight,), x.dtype,
+                                lambda: _chk(weight.detach(), "weight").view(3, 8, 8, 3, 3).permute(3, 4, 1, 0, 2).contiguous().to(x.dtype))
     b = None if bias is None else _chk(bias.detach(), "bias")
     r = None if residual is None else _chk(residual, "residual")
     if r is not None and tuple(r.shape) != (n, 3, h, w):
@@ -3251,21 +3159,9 @@ def conv3x3_c64to3_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], residu
     return out
 
 
-_h16_pack5_cache = WeightCache()
-
-
 def _packed5_h16(wcat: Tensor, code: int) -> Tensor:
     """(cout, 64, 5, 5) fp32 (a parameter or the cached concatenation of several) -> the 16-bit MFMA-fragment order"""
-    hit = _h16_pack5_cache.lookup((wcat,), code)
-    if hit is not None:
-        return hit
-    if wcat.dim() != 4 or tuple(wcat.shape[1:]) != (64, 5, 5) or wcat.shape[0] > 128:
-        raise NotImplementedError("the 16-bit heads kernel is the 5x5 convolution 64 -> (<= 128) channels")
-    packed = torch.empty(int(lib().eavsr_conv5x5_c64_h16_weight_bytes()) // 2, device=wcat.device, dtype=_H16_TORCH[code])
-    st = _stream(wcat)
-    with _DeviceOf(wcat):
-        N.check(lib().eavsr_pack_conv5x5_c64_h16(_p(wcat), _p(packed), int(wcat.shape[0]), code, st), "pack_conv5x5_c64_h16")
-    return _h16_pack5_cache.store((wcat,), code, packed)
+    return _packed("h16_5x5", wcat, code)
 
 
 def conv5x5_c64_h16(x: Tensor, weights, biases) -> Tensor:
@@ -3342,26 +3238,9 @@ def _out_or_new(out: Optional[Tensor], shape, like: Tensor, name: str) -> Tuple[
     return out, _batch_stride(out, name)
 
 
-_pwc_pack_cache = WeightCache()
-
-
 def _packed_pwc_conv3x3(weight: Tensor) -> Tensor:
-    """[9][cin even][cout padded] form of a (cout, cin, 3, 3) weight for eavsr_pwc_conv3x3_f32; cached per weight object and
-    version, verified by identity."""
-    hit = _pwc_pack_cache.lookup((weight,))
-    if hit is not None:
-        return hit
-    w = _chk(weight.detach(), "weight")
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-        raise NotImplementedError(f"pwc_conv3x3: weight shape {tuple(w.shape)} (3x3 only)")
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    elems = lib().eavsr_pwc_conv3x3_weight_elems(cout, cin)
-    if elems <= 0:
-        raise NotImplementedError(f"pwc_conv3x3: weight shape {tuple(w.shape)} unsupported")
-    packed = torch.empty(elems, device=w.device, dtype=torch.float32)
-    with _DeviceOf(w):
-        N.check(lib().eavsr_pwc_pack_conv3x3_f32(_p(w), _p(packed), cout, cin, _stream(w)), "pwc_pack_conv3x3")
-    return _pwc_pack_cache.store((weight,), None, packed)
+    """[9][cin even][cout padded] form of a (cout, cin, 3, 3) weight for eavsr_pwc_conv3x3_f32"""
+    return _packed("pwc", weight)
 
 
 def pwc_conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, stride: int = 1, dilation: int = 1,

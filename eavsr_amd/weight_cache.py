@@ -96,3 +96,11 @@ class WeightCache:
             order = [stream.cuda_stream, on_device[0].device, event, set()]
         d[key] = (tuple(weakref.ref(t, lambda _r: d.pop(key, None)) for t in sources), value, order)
         return value
+
+    def derive(self, sources, tag, make):
+        """`lookup(sources, tag)`, or on a miss `store(sources, tag, make())`: `make` derives the value on the current stream and
+        the store's event is recorded right behind it, with nothing in between.  If `make` raises, nothing is stored."""
+        hit = self.lookup(sources, tag)
+        if hit is not None:
+            return hit
+        return self.store(sources, tag, make())

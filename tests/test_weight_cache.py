@@ -110,3 +110,62 @@ def test_clear_and_snapshot():
     c.clear()
     assert len(c) == 0 and c.lookup((a,)) is None
     assert len(snap) == 1 and next(iter(snap.values()))[1] is value      # a snapshot keeps what it saw
+
+
+def _counting(values):
+    """make() for derive: hands out `values` in turn and counts its calls"""
+    calls = []
+
+    def make():
+        calls.append(len(calls))
+        return values[len(calls) - 1]
+    return make, calls
+
+
+def test_derive_makes_once_on_a_miss_and_never_on_a_hit():
+    c, a, b = WeightCache(), _param(3), _param(3)
+    first = object()
+    make, calls = _counting([first, object()])
+    assert c.derive([a, b], None, make) is first and calls == [0]
+    assert c.lookup([a, b]) is first                                     # the returned object is the stored one
+    assert c.derive([a, b], None, make) is first and c.derive((a, b), None, make) is first
+    assert calls == [0] and len(c) == 1
+
+
+def test_derive_makes_again_after_a_version_bump_and_under_another_tag():
+    c, a = WeightCache(), _param(3)
+    values = [object(), object(), object()]
+    make, calls = _counting(values)
+    assert c.derive((a,), None, make) is values[0]
+    assert c.derive((a,), "f4", make) is values[1] and len(calls) == 2   # another tag: a form of its own
+    assert c.derive((a,), None, make) is values[0] and c.derive((a,), "f4", make) is values[1] and len(calls) == 2
+    _bump(a)
+    assert c.derive((a,), None, make) is values[2] and len(calls) == 3
+    assert len(c) == 1 and c.lookup((a,)) is values[2]                   # the stale version went under every tag
+
+
+def test_derive_looks_up_first_and_stores_right_behind_make(monkeypatch):
+    c, a = WeightCache(), _param(3)
+    order = []
+    lookup, store = c.lookup, c.store
+    monkeypatch.setattr(c, "lookup", lambda *k: (order.append("lookup"), lookup(*k))[1])
+    monkeypatch.setattr(c, "store", lambda *k: (order.append("store"), store(*k))[1])
+    value = c.derive((a,), 1, lambda: order.append("make") or "v")
+    assert value == "v" and order == ["lookup", "make", "store"]
+    assert c.derive((a,), 1, lambda: order.append("make") or "w") == "v" and order == ["lookup", "make", "store", "lookup"]
+
+
+def test_a_raising_make_stores_nothing_and_propagates():
+    c, a, b = WeightCache(), _param(3), _param(3)
+    c.store((b,), None, "b")
+
+    def make():
+        raise NotImplementedError("unsupported shape")
+    try:
+        c.derive((a,), None, make)
+    except NotImplementedError as e:
+        assert "unsupported shape" in str(e)
+    else:
+        raise AssertionError("derive swallowed the exception of make()")
+    assert len(c) == 1 and c.lookup((a,)) is None and c.lookup((b,)) == "b"
+    assert c.derive((a,), None, lambda: "a") == "a" and len(c) == 2       # nothing poisoned: the next derivation goes through

@@ -15,7 +15,7 @@ n, h, w = 4, 180, 320
 x = torch.randn(n, 64, h, w, device=dev)
 wt = torch.randn(64, 64, 3, 3, device=dev) * 0.05
 b = torch.randn(64, device=dev) * 0.1
-wp = ops.pack_cache.get([wt])
+wp = ops._packed_f32([wt])
 out = torch.empty(n, 64, h, w, device=dev)
 d = N.ConvDesc()
 d.src[0] = x.data_ptr(); d.src_c[0] = 64; d.n_src = 1; d.ksize = 3

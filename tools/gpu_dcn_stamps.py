@@ -18,7 +18,7 @@ mask = torch.rand(n, 72, h, w, device=dev)
 wt = torch.randn(64, 64, 3, 3, device=dev) * 0.05
 b = torch.randn(64, device=dev) * 0.1
 ref = ops.modulated_deform_conv2d(x, off, mask, wt, b, 1, 1, 1, 1, 8)
-wp = ops.pack_cache.get([wt])
+wp = ops._packed_f32([wt])
 out = torch.empty_like(ref)
 p = lambda t: C.c_void_p(t.data_ptr())
 stamps = (C.c_ulonglong * 16)()
