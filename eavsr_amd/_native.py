@@ -214,6 +214,10 @@ SIGNATURES = {
     "eavsr_pack16": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     "eavsr_unpack16": (C.c_int, [vp, vp, vp, i32, i32, vp]),
     "eavsr_pack16_census": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),      # pack16 + the five counts of what the rounding did
+    # the range census of the 16-bit backbone modes: stored words / fp32 values as rounded (csrc/range16.hip; additions to ABI 32)
+    "eavsr_range16_words": (C.c_int, [vp, vp, i32, i32, vp, vp]),
+    "eavsr_range16_as_rounded": (C.c_int, [vp, vp, i32, i32, vp, vp]),
+    "eavsr_range16_stamp": (C.c_int, [vp, vp, C.c_uint64, vp]),
     # training batches from device-resident 8-bit frames (csrc/batch.hip; addition to ABI 32)
     "eavsr_gather_pairs_u8": (C.c_int, [vp] * 6 + [i32] * 9 + [vp]),
     # LR frames from full-size frames: cv2.resize INTER_CUBIC on bytes (csrc/resize_cubic.hip; addition to ABI 32)

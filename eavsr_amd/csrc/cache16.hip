@@ -23,6 +23,7 @@
 //             cache16_census.h's; with the switch off nothing of it is compiled and pack16 is the kernel it was.
 #include "common.h"
 #include "cache16_census.h"
+#include "round16.h"
 
 #include <stdint.h>
 
@@ -79,22 +80,8 @@ __device__ __forceinline__ void store_quad(float* p, int align, float4 v) {
   }
 }
 
-template <int BF16>
-__device__ __forceinline__ uint32_t round16(float x) {
-  if (BF16) {
-    const uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;      // NaN: torch's
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;             // nearest even; the carry out of the mantissa is the overflow to inf
-  }
-  const _Float16 h = (_Float16)x;
-  return (uint32_t)__builtin_bit_cast(uint16_t, h);
-}
-
-template <int BF16>
-__device__ __forceinline__ float widen16(uint32_t b) {
-  if (BF16) return __uint_as_float(b << 16);
-  return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
-}
+using round16_ns::round16;      // (round16.h: shared with the range census of the 16-bit backbone, range16.hip)
+using round16_ns::widen16;
 
 // where scalar item j (0 <= j < n - 8 nvec) of a segment lies: the head's elements, then the tail's
 __device__ __forceinline__ int64_t scalar_index(int64_t j, const Cut& c) { return j < c.head ? j : j + 8 * c.nvec; }

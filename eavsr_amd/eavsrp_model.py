@@ -206,6 +206,8 @@ class EAVSRP(nn.Module):
             raise NotImplementedError("EAVSRP exists for x4 (eavsrp_model) and x2 (eavsrpx2_model)")
         # one entry per `forward_long` call that ran under a `cache_check` (addendum); the caller clears it
         self.cache_census = []
+        # one entry per `forward` / `forward_long` call that ran under a `networks.backbone_check` (addendum); likewise
+        self.backbone_census = []
 
         self.spynet = SPyNet(pretrained=spynet_pretrained)
         for p in self.spynet.parameters():
@@ -246,6 +248,18 @@ class EAVSRP(nn.Module):
 
     # -- forward ---------------------------------------------------------------------------
     def forward(self, lrs):
+        chk = None if N.BACKBONE_CHECK is None else N.active_backbone_check()
+        if chk is None:
+            return self._forward(lrs)
+        # under a `networks.backbone_check` (addendum): the same launches, each 16-bit one counted; the counts are read
+        # before anything is returned ("raise" / "bf16") or once behind the last launch ("report")
+        win = N.BackboneWindow(*chk, dict(frames=int(lrs.shape[1]), size=tuple(int(v) for v in lrs.shape[3:]), device=lrs.device),
+                               self.__dict__.setdefault("backbone_census", []))
+        out = win.stages(lambda: self._forward(lrs))
+        win.close()
+        return out
+
+    def _forward(self, lrs):
         n, t, c, h, w = lrs.shape
         assert h >= 64 and w >= 64, (
             'The height and width of inputs should be at least 64, '
@@ -259,9 +273,11 @@ class EAVSRP(nn.Module):
             ops.prepack_conv3_x6([p_ for p_ in self.parameters() if p_.requires_grad and p_.dim() == 4 and tuple(p_.shape) == (64, 64, 3, 3)])
         # frame-major input so that every per-frame slice (of the input, the features, the flows) is contiguous
         lr_tm = lrs.transpose(0, 1).reshape(t * n, c, h, w)
+        ops.range_mark("spynet")
         with torch.no_grad():
             flows_forward, flows_backward = self.compute_flow(lrs, lr_tm)
 
+        ops.range_mark("encoder")
         f1 = self.encoder(lr_tm)                                   # :216
         f2, f4 = AG.pyramid(f1)                                    # :218-220
         feats: Dict[str, List[Tensor]] = {
@@ -338,8 +354,10 @@ class EAVSRP(nn.Module):
         if not AG.needs_grad(flows, feats["spatial"][0], list(backbone.parameters())):
             stacked = flows.new_empty(len(feats["spatial"]) * n, self.n_feats, h, w)
         # inference, fp32: the predictors of every time step first, in batched launches; the loop keeps warp + DCNv2 (`sample`)
+        ops.range_mark(module_name + ".predict")      # (a census; the hoist applies to fp32 only today: nothing is counted under it)
         pred = self._predict_branch(align, feats, flows, backward) if (HOIST_PREDICTORS and t > 0) else None
         for i, idx in enumerate(frame_idx):
+            ops.range_mark(module_name)      # (a census: every time step counts into the rows of the first)
             cur = [feats[k][mapping_idx[idx]] for k in _PYR]
             if i > 0 and pred is not None:
                 off1, heads1, off2, heads2 = pred
@@ -395,6 +413,7 @@ class EAVSRP(nn.Module):
     def _upsample_tm(self, srcs, lq_tm):
         """the tail on frame-major tensors: srcs = `spatial` and the four branches (rows, 64, h, w), lq_tm (rows, 3, h, w) ->
         (rows, 3, s h, s w).  `upsample` runs it on all t n rows, `forward_long` on a chunk of frames."""
+        ops.range_mark("tail")
         hr = self.reconstruction(srcs)
         tail16 = (N.BACKBONE_DTYPE is not None and TAIL_IN_16BIT and self.n_feats == 64 and
                   not AG.needs_grad(hr, lq_tm, list(self.upsample1.parameters()) + list(self.conv_hr.parameters()) +
@@ -543,11 +562,13 @@ class EAVSRP(nn.Module):
                 m = int(seq.shape[0]) - n      # rows of this chunk's pairs: (frame j, frame j + 1), j = first .. first + m / n - 1
                 if m > 0:
                     lrs_1, lrs_2 = seq[:m], seq[n:]
+                    ops.range_mark("spynet")
                     with ops.route_batch(pin(2 * n * (t - 1))):
                         both = self.spynet(torch.cat([lrs_1, lrs_2], 0), torch.cat([lrs_2, lrs_1], 0))
                     first = a if last is None else a - 1
                     store.put_range("flow_backward", first, both[:m])
                     store.put_range("flow_forward", first, both[m:])
+                ops.range_mark("encoder")
                 with ops.route_batch(pin(t * n)):
                     f1 = self.encoder(lr_c)
                     f2, f4 = AG.pyramid(f1)
@@ -581,9 +602,11 @@ class EAVSRP(nn.Module):
                 if ci + 1 < len(tail):      # (host cache: the next chunk's copies overlap this chunk's kernels)
                     for key in keys:
                         store.prefetch_range(key, *tail[ci + 1])
-                with ops.route_batch(pin_tail(t * n)):
-                    sr = self._upsample_tm(tensors[:-1], tensors[-1])
-                del tensors
+                def run_tail(tensors=tensors):
+                    with ops.route_batch(pin_tail(t * n)):
+                        return self._upsample_tm(tensors[:-1], tensors[-1])
+                sr = run_tail() if win is None else win.tail(a, run_tail)
+                del tensors, run_tail
                 sr = sr.view(b - a, n, *sr.shape[1:]).transpose(0, 1)
                 if transform is not None:      # where mode k has moved the frame's samples to, inside its (transposed: s W x s H) SR frame
                     r0, r1, c0, c1 = valid_region(transform, h, w, *(size or (h, w)), self.scale)
@@ -601,10 +624,38 @@ class EAVSRP(nn.Module):
                 del sr
             return out
 
+        win = None
+        if N.BACKBONE_CHECK is not None and N.active_backbone_check() is not None:
+            # under a `networks.backbone_check` (addendum): stages 1-2 and every chunk's tail run as `BackboneWindow`
+            # orders them.  `checked_window` owns a `framestore.StoreBox`: a window that falls back drops the store of its fp16
+            # attempt and fills a fresh one IN the box, so the cache census, `finish` and stage 3 all act on the store that was used
+            win = N.BackboneWindow(*N.active_backbone_check(), dict(frames=t, size=(h, w), device=device),
+                                   self.__dict__.setdefault("backbone_census", []))
+            make0, fill0, drain0 = make, fill, drain
+
+            def make(dtype, census):
+                return FS.StoreBox(lambda: make0(dtype, census))
+
+            def fill(box):
+                def run():
+                    return fill0(box.store)
+
+                def again():
+                    box.renew()      # (the fp16 attempt's store goes before the bf16 run's is taken)
+                    return fill0(box.store)
+                return win.stages(run, again)
+
+            def drain(box, branches):
+                return drain0(box.store, branches)
+
+        def finish(out):
+            if win is not None:
+                win.close()
+            return out
         if cache_check is None:      # make, fill, drain, finish
-            return FS.checked_window(make, fill, drain, cache_dtype, None, None, None)
-        return FS.checked_window(make, fill, drain, cache_dtype, cache_check, dict(frames=t, size=(h, w)),
-                                 self.__dict__.setdefault("cache_census", []))
+            return finish(FS.checked_window(make, fill, drain, cache_dtype, None, None, None))
+        return finish(FS.checked_window(make, fill, drain, cache_dtype, cache_check, dict(frames=t, size=(h, w)),
+                                        self.__dict__.setdefault("cache_census", [])))
 
     def forward_segments(self, lrs, segments, frame_chunk=None, cache="device", sink=None):
         """A clip of any length as a sequence of `forward_long` calls: for every (start, stop, emit_start, emit_stop) of
@@ -854,10 +905,12 @@ class EAVSRP(nn.Module):
         # `propagate`.  A chunked run asked for activations that do not grow with t and the host cache keeps a window of frames on
         # the device: both stay with the per-step form
         pred = None
+        ops.range_mark(module_name + ".predict")
         if hoist and HOIST_PREDICTORS and getattr(store, "hoists", store.cache == "device") and t > 1:
             pred = self._predict_rows(align, [store.get_range(k, 0, t) for k in _PYR], store.get_range(fkey, 0, t - 1), n, backward)
         for i, idx in enumerate(order):
             store.step(i)
+            ops.range_mark(module_name)
             cur = [store.get(k, idx) for k in _PYR]
             if i == 0:
                 feat_prop = cur[0].new_zeros(cur[0].shape[0], self.n_feats, *cur[0].shape[2:])
@@ -983,6 +1036,7 @@ def long_clip_options(opt=None):
     ensemble_options(opt)        # likewise: opt.ensemble, read by EAVSRPModel.forward and harness.super_resolve
     cache_dtype_option(opt)      # likewise: opt.cache_dtype, read by EAVSRPModel.forward and harness.super_resolve
     cache_check_option(opt)      # likewise: opt.cache_check, read beside it
+    backbone_check_option(opt)   # likewise: opt.backbone_check, read by EAVSRPModel.forward and harness.super_resolve (addendum)
     from .resize import out_size_option
     out_size_option(opt)         # likewise: opt.out_size, read by EAVSRPModel.forward and harness.super_resolve
     return fc, cc
@@ -1008,6 +1062,32 @@ def cache_check_option(opt=None):
             raise ValueError(f"{who}={value!r}: 'report', 'raise', 'bf16' or None")
         return one_of(FS.CACHE_CHECKS, "'report', 'raise', 'bf16' or None")(value, who)
     return read_option(opt, "cache_check", "EAVSR_CACHE_CHECK", from_opt, choices)
+
+
+def backbone_check_option(opt=None):
+    """None, "report", "raise" or "bf16": the range census of the 16-bit backbone (`networks.set_backbone_check`, DESIGN 3.6 addendum)
+    -- `opt.backbone_check`, falling back to the environment where the options do not carry it
+    (EAVSR_BACKBONE_CHECK=report|raise|bf16), None -- no census -- where neither does.  The spelling alone is checked here; that a
+    check needs a 16-bit backbone, and "bf16" an fp16 one, is refused where the call is made (`networks.check_backbone_check`).  Not
+    among the reference's options."""
+    from .segments import one_of, read_option
+
+    def from_opt(value, who):
+        if not isinstance(value, str):
+            raise ValueError(f"{who}={value!r}: 'report', 'raise', 'bf16' or None")
+        return one_of(N.BACKBONE_CHECKS, "'report', 'raise', 'bf16' or None")(value, who)
+    return read_option(opt, "backbone_check", "EAVSR_BACKBONE_CHECK", from_opt, one_of(N.BACKBONE_CHECKS, "report, raise or bf16"))
+
+
+def wrapper_backbone_check(opt, is_train: bool):
+    """`EAVSRPModel.backbone_check`: `backbone_check_option(opt)` outside training; under `isTrain` an `opt.backbone_check` is refused
+    and None is returned otherwise -- training reads neither the option nor the environment (`networks.active_backbone_check`
+    likewise ignores a mode that only the environment set while gradients are enabled)"""
+    if is_train:
+        if getattr(opt, "backbone_check", None) is not None:
+            raise ValueError("opt.backbone_check: the census belongs to the 16-bit backbone, an inference mode (networks.set_backbone_dtype)")
+        return None
+    return backbone_check_option(opt)
 
 
 def cache_dtype_option(opt=None):
@@ -1071,6 +1151,8 @@ class EAVSRPModel:
         self.cache_check = cache_check_option(opt)
         if not self.isTrain:      # (training reads neither: an environment set for inference runs does not stop it)
             FS.check_cache_check(self.cache_check, self.cache_dtype)
+        # opt.backbone_check (not among the reference's options): the range census of the 16-bit backbone modes (addendum)
+        self.backbone_check = wrapper_backbone_check(opt, self.isTrain)
         # opt.out_size (not among the reference's options): the SR frames resized to any target size, outside training
         if self.isTrain and getattr(opt, "out_size", None) is not None:
             raise ValueError("opt.out_size: the resize of the SR frames is an inference option (resize.resize_frames has no backward); "
@@ -1176,6 +1258,11 @@ class EAVSRPModel:
         self.epoch = epoch
 
     def forward(self):
+        if getattr(self, "backbone_check", None) is not None and N.BACKBONE_CHECK is None and not (self.isTrain and self.netEAVSRP.training):
+            # opt.backbone_check: this method once more under the check (a mode set on the module itself stays as it is).  Every call
+            # below leads to EAVSRP.forward / forward_long, which count; one entry of `netEAVSRP.backbone_census` per window
+            with N.backbone_check(self.backbone_check), torch.no_grad():
+                return self.forward()
         if self.isTrain and self.netEAVSRP.training:
             self.data_sr_seq = self.netEAVSRP(self.data_lr_seq)
             self.data_sr = self.data_sr_seq[:, self.idx]

@@ -184,6 +184,27 @@ def checked_window(make, fill, drain, cache_dtype, cache_check, about: Dict, log
     return out
 
 
+class StoreBox:
+    """What `checked_window` owns where a caller may have to fill a window twice (`EAVSRP.forward_long` under a
+    `networks.backbone_check` that falls back): `store` is the store in use, `renew()` finishes and drops it and makes a fresh one
+    with the same arguments -- the old store's memory goes before the new one's is taken.  `census` and `finish` are the store's in
+    use, so the cache census describes the features that stage 3 read."""
+
+    def __init__(self, make):
+        self._make, self.store = make, make()
+
+    def renew(self) -> None:
+        self.store.finish()
+        self.store = None
+        self.store = self._make()
+
+    def census(self):
+        return self.store.census()
+
+    def finish(self) -> None:
+        self.store.finish()
+
+
 def census_summary(log: Sequence[Dict]) -> Dict:
     """one line over the entries of `EAVSRP.cache_census`: the largest |x| any key of any window held, the totals of its counts, and
     how many windows fell back to bf16 (the counts of a window that fell back are its fp16 attempt's, 'keys')"""

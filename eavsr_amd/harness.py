@@ -13,6 +13,7 @@ feeds `{'lr_seq', 'hr_seq', 'fname'}` dicts exactly as the reference's does.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import struct
@@ -887,6 +888,9 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
         lpips = build_lpips(os.fspath(lpips), device=model.device)
     frame_lpips: List[float] = []
     model.eval()
+    checked_net = getattr(model, "netEAVSRP", None) if getattr(model, "backbone_check", None) is not None else None
+    if checked_net is not None:
+        checked_net.backbone_census = []
     psnr: List[float] = []
     ssim: List[float] = []
     written: List[str] = []
@@ -967,6 +971,9 @@ def evaluate(model, items: Iterable[Dict], calc_psnr_flag: bool = True, calc_ssi
             out["frame_niqe"] = frame_niqe
         if temporal is not None:
             out.update(frame_ewarp=frame_temporal["ewarp"], frame_tof=frame_temporal["tof"], frame_valid=frame_temporal["valid"])
+    if checked_net is not None:      # opt.backbone_check (addendum): one entry per window of every item, and the one line
+        from .networks import range_summary
+        out.update(backbone_census=checked_net.backbone_census, backbone_range=range_summary(checked_net.backbone_census))
     return out
 
 
@@ -1039,6 +1046,18 @@ def resize_frames(frames, size):
     if not frames.is_floating_point():
         raise ValueError(f"resize_frames: frames is uint8 or floating point, got {frames.dtype}")
     return _resize_frames(frames.to(torch.float32), size)
+
+
+@contextlib.contextmanager
+def _backbone_checked(mode, net):
+    """the body's forwards under `networks.backbone_check(mode)`, the network's `backbone_census` cleared first; None: nothing"""
+    if mode is None:
+        yield
+        return
+    from . import networks
+    net.backbone_census = []
+    with networks.backbone_check(mode):
+        yield
 
 
 def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: Optional[Sequence] = None,
@@ -1161,6 +1180,14 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
         from .eavsrp_model import cache_check_option
         cache_check = cache_check_option(getattr(model, "opt", None))
     cache_check = check_cache_check(cache_check, cache_dtype)
+    # the range census of the 16-bit backbone (addendum): `networks.set_backbone_check`'s mode, else `opt.backbone_check` of
+    # a model wrapper, else EAVSR_BACKBONE_CHECK; refused here, before a file is read, as every call below would refuse it
+    from . import networks as _networks
+    backbone_check = _networks.BACKBONE_CHECK
+    if backbone_check is None:
+        from .eavsrp_model import backbone_check_option
+        backbone_check = backbone_check_option(getattr(model, "opt", None))
+    backbone_check = _networks.check_backbone_check(backbone_check, _networks.BACKBONE_DTYPE)
     if ensemble is None:      # a bad spec is refused here, before a file is read
         modes = ensemble_options(getattr(model, "opt", None))
     elif isinstance(ensemble, str):
@@ -1359,20 +1386,21 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
                 starts = list(cuts or [])
             plan = plan_segments(t, starts, max_frames, overlap, min_scene)
             scene_bounds[:] = keep_starts(t, starts, min_scene)
-        if cache_check is not None:
-            net.cache_census = []
-            net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
-                               segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink,
-                               cache_check=cache_check)
-        elif cache_dtype is not None:
-            net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
-                               segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
-        elif modes == (0,):
-            net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
-                              frame_chunk=frame_chunk, cache=cache, sink=sink)
-        else:
-            net.forward_ensemble(lrs, ensemble=modes, tile=tile, overlap=tile_overlap, segments=plan if segmented else None, pad=pad,
-                                 frame_chunk=frame_chunk, cache=cache, sink=sink)
+        with _backbone_checked(backbone_check, net):
+            if cache_check is not None:
+                net.cache_census = []
+                net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
+                                   segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink,
+                                   cache_check=cache_check)
+            elif cache_dtype is not None:
+                net.forward_cached(lrs, cache_dtype, ensemble=None if modes == (0,) else modes, tile=tile, overlap=tile_overlap,
+                                   segments=plan if segmented else None, pad=pad, frame_chunk=frame_chunk, cache=cache, sink=sink)
+            elif modes == (0,):
+                net.forward_video(lrs, segments=plan if segmented else None, tile=tile, tile_overlap=tile_overlap, pad=pad,
+                                  frame_chunk=frame_chunk, cache=cache, sink=sink)
+            else:
+                net.forward_ensemble(lrs, ensemble=modes, tile=tile, overlap=tile_overlap, segments=plan if segmented else None, pad=pad,
+                                     frame_chunk=frame_chunk, cache=cache, sink=sink)
     write_pending()
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
@@ -1384,6 +1412,8 @@ def super_resolve(model, frames, out_dir: Optional[str] = None, hr=None, names: 
     if cache_check is not None:
         from .framestore import census_summary
         out.update(cache_census=net.cache_census, cache_range=census_summary(net.cache_census))
+    if backbone_check is not None:      # one entry per window / tile / mode, and the one line over them
+        out.update(backbone_census=net.backbone_census, backbone_range=_networks.range_summary(net.backbone_census))
     frame_temporal = None
     if temporal is not None:
         rows = {key: [[None] * t for _ in range(n)] for key in ("ewarp", "tof", "valid")}

@@ -512,6 +512,193 @@ def backbone_dtype(dtype):
         set_backbone_dtype(prev)
 
 
+# ---- the range census of the 16-bit modes (addendum) ----------------------------------------------------------------
+# None (the default: every launch and byte is what it was), "report", "raise" or "bf16": set_backbone_check / backbone_check /
+# EAVSR_BACKBONE_CHECK / opt.backbone_check.  While one is set, every launch of a 16-bit op counts what it rounds (ops._launch,
+# ops.RangeCensus) and EAVSRP.forward / forward_long read the counts as `BackboneWindow` orders it.
+BACKBONE_CHECKS = ("report", "raise", "bf16")
+
+
+def check_backbone_check(mode, dtype="unknown", who: str = "backbone_check"):
+    """`mode` beside the backbone dtype it would run with (left out: the spelling alone): None | "report" (count, read when the call
+    ends) | "raise" (read before anything leaves, refuse a window that holds inf / NaN or overflowed) | "bf16" (likewise, and run such
+    a window of an fp16 backbone again in bf16).  Refused: anything else, a check without a 16-bit backbone, "bf16" where the
+    backbone is not fp16, any check with the one-launch RCAB of the lab build (its intermediate never leaves LDS)."""
+    if mode is None:
+        return None
+    if not isinstance(mode, str) or mode not in BACKBONE_CHECKS:
+        raise ValueError(f"{who} {mode!r}: None, 'report', 'raise' or 'bf16'")
+    if dtype == "unknown":
+        return mode
+    if dtype is None:
+        raise ValueError(f"{who} {mode!r} without a 16-bit backbone (set_backbone_dtype('fp16' / 'bf16')): the census is taken where "
+                         "activations are rounded to 16 bits")
+    if mode == "bf16" and ops.h16_code(dtype) != ops.h16_code("fp16"):
+        raise ValueError(f"{who} 'bf16' with the {dtype!r} backbone: the fallback is from an fp16 backbone")
+    if RCAB_H16_FUSED:
+        raise ValueError(f"{who} {mode!r} with RCAB_H16_FUSED: the one-launch RCAB keeps its intermediate in LDS, where nothing can "
+                         "count it (set_rcab_h16_fused(False))")
+    return mode
+
+
+BACKBONE_CHECK = check_backbone_check(_os.environ.get("EAVSR_BACKBONE_CHECK") or None, who="EAVSR_BACKBONE_CHECK")
+# where the mode came from: "env" (read above: an environment set for inference runs does not stop training -- a call under autograd
+# ignores it) or "call" (set_backbone_check / backbone_check: such a call under autograd is refused)
+_BACKBONE_CHECK_FROM = "env"
+
+
+def set_backbone_check(mode) -> None:
+    """None | "report" | "raise" | "bf16": the range census of the 16-bit backbone (`check_backbone_check`), for every EAVSRP.forward /
+    forward_long call from here on.  Checked against the backbone dtype of the moment here, and again at every call."""
+    global BACKBONE_CHECK, _BACKBONE_CHECK_FROM
+    BACKBONE_CHECK = check_backbone_check(mode, BACKBONE_DTYPE, "set_backbone_check")
+    _BACKBONE_CHECK_FROM = "call"
+
+
+@_contextlib.contextmanager
+def backbone_check(mode):
+    """`with networks.backbone_check("report"): sr = net(x)` -- the check for the body only; the previous setting is restored on exit,
+    also when the body raises."""
+    global BACKBONE_CHECK, _BACKBONE_CHECK_FROM
+    prev = BACKBONE_CHECK, _BACKBONE_CHECK_FROM
+    set_backbone_check(mode)
+    try:
+        yield
+    finally:
+        BACKBONE_CHECK, _BACKBONE_CHECK_FROM = prev
+
+
+def _short_dtype(dtype) -> str:
+    return "fp16" if ops.h16_code(dtype) == 1 else "bf16"
+
+
+def active_backbone_check():
+    """(mode, backbone dtype as "fp16" / "bf16") of a call that starts now, or None without a check (or with one that only the
+    environment set, under autograd: training reads neither the option nor the environment) -- the refusals of
+    `check_backbone_check`, and of a check under gradients or, where it synchronises, under stream capture"""
+    if BACKBONE_CHECK is None or (_BACKBONE_CHECK_FROM == "env" and torch.is_grad_enabled()):
+        return None
+    mode = check_backbone_check(BACKBONE_CHECK, BACKBONE_DTYPE)
+    if torch.is_grad_enabled():
+        raise ValueError(f"backbone_check {mode!r} under autograd: the census belongs to the 16-bit inference modes (torch.no_grad())")
+    if mode != "report" and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise ValueError(f"backbone_check {mode!r} under stream capture: it reads the census back, which synchronises ('report' does not)")
+    return mode, _short_dtype(BACKBONE_DTYPE)
+
+
+def tripped(sites) -> List[dict]:
+    """the sites that hold a non-finite word or rounded a finite value to inf, in the order in which they first did ('tripped_at',
+    the census's count of launches: time steps share rows, so a later step's input may trip a site that is earlier in call order)"""
+    return sorted((s for s in sites if s["nonfinite"] > 0 or s["overflow"] > 0), key=lambda s: s.get("tripped_at", 0))
+
+
+class BackboneRangeError(ValueError):
+    """a window (or a chunk of its tail) whose activations do not fit the 16-bit backbone (`backbone_check("raise")`); `entry` is the
+    call's census entry, `site` the site that tripped first IN TIME (`tripped`: the smallest 'tripped_at'; time steps share rows, so a
+    later step's poisoned input trips sites that are earlier in call order than the one that left the range)"""
+
+    def __init__(self, entry: dict, where: str):
+        self.entry, self.site = entry, tripped(entry["sites"])[0]
+        s = self.site
+        super().__init__(f"{entry['asked']} backbone out of range in {where} of a window of {entry['frames']} frames of "
+                         f"{entry['size'][0]} x {entry['size'][1]} -- first at {s['site']}: max |x| {s['max_abs']:.6g}, "
+                         f"{s['nonfinite']} non-finite, {s['overflow']} overflowed of {s['elements']} "
+                         f"({len(tripped(entry['sites']))} sites in all; nothing of it has reached the sink; "
+                         "backbone_check('bf16') runs such a window in bf16)")
+
+
+class BackboneWindow:
+    """The order of one checked EAVSRP call -- pure host code over callables, as `framestore.checked_window`.  `stages(run)` runs
+    stages 1-2 of `forward_long` (or the whole of `forward`), `tail(first_frame, run)` one chunk of stage 3, `close()` ends the call
+    and appends its entry to `log`.  `open_census(dtype)` makes the object the launches count into (its `read()` returns the sites so
+    far, cumulatively, and is the one synchronisation); `counting(census)` and `as_dtype(dtype)` are context managers: the
+    launches of the body count into `census` / run under that backbone dtype.
+    "report": one census for the whole call, read in `close`.  "raise" / "bf16": read behind `stages` and behind every `tail`, before
+    its result is returned -- so before the sink sees it.  Where new counts of non-finite or overflowed elements have appeared:
+    "raise" appends the entry and raises `BackboneRangeError`; "bf16" runs `run` again under `as_dtype("bf16")` (counted into a second,
+    bf16 census: 'sites_used') -- behind `stages` the rest of the call stays in bf16 ('fallback'), behind a `tail` that chunk alone
+    ('tail_fallback' gains its first frame).  Which site tripped first is the census's to say: every site's record carries
+    'tripped_at', the count of counting launches at which its row first held inf / NaN or an overflow (`ops.RangeCensus`, the
+    one-lane stamp launch behind every count); `tripped` orders by it."""
+
+    def __init__(self, mode: str, dtype: str, about: dict, log: list, open_census=None, counting=None, as_dtype=None):
+        self.mode, self.log = mode, log
+        self.open_census = open_census or (lambda dt: ops.RangeCensus(dt, about.get("device", "cuda")))
+        self.counting, self.as_dtype = counting or ops.range_census, as_dtype or backbone_dtype
+        self.entry = dict(asked=dtype, used=dtype, fallback=False, tail_fallback=[],
+                          **{k: v for k, v in about.items() if k != "device"}, sites=None)
+        self.census, self.census_used, self._bad = self.open_census(dtype), None, 0
+
+    def _new_trips(self) -> bool:
+        self.entry["sites"] = self.census.read()
+        bad = sum(s["nonfinite"] + s["overflow"] for s in self.entry["sites"])
+        new, self._bad = bad > self._bad, bad
+        return new
+
+    def _in_bf16(self, run):
+        if self.census_used is None:
+            self.census_used = self.open_census("bf16")
+        with self.as_dtype("bf16"), self.counting(self.census_used):
+            return run()
+
+    def _refuse(self, where: str):
+        self.log.append(self.entry)
+        raise BackboneRangeError(self.entry, where)
+
+    def stages(self, run, rerun=None):
+        """`rerun`: what runs in bf16 where `run` tripped (`forward_long`: the same stages on a fresh store); None: `run` again"""
+        self.entry.update(used=self.entry["asked"], fallback=False)      # (a window that is filled twice starts again)
+        with self.counting(self.census):
+            out = run()
+        if self.mode == "report" or not self._new_trips():
+            return out
+        if self.mode == "raise":
+            self._refuse("stages 1-2")
+        del out
+        self.entry.update(used="bf16", fallback=True)
+        return self._in_bf16(rerun or run)
+
+    def tail(self, first_frame: int, run):
+        if self.entry["fallback"]:
+            return self._in_bf16(run)
+        with self.counting(self.census):
+            out = run()
+        if self.mode == "report" or not self._new_trips():
+            return out
+        if self.mode == "raise":
+            self._refuse(f"the tail of the chunk at frame {first_frame}")
+        del out
+        self.entry["tail_fallback"].append(int(first_frame))
+        return self._in_bf16(run)
+
+    def close(self):
+        if self.mode == "report":
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                # a captured call launches nothing yet: the entry keeps the census, `entry['pending'].read()` after a replay
+                self.entry["pending"] = self.census
+            else:
+                self.entry["sites"] = self.census.read()
+        if self.census_used is not None:
+            self.entry["sites_used"] = self.census_used.read()
+        self.log.append(self.entry)
+        return self.entry
+
+
+def range_summary(log) -> dict:
+    """one line over the entries of `EAVSRP.backbone_census`: the worst site (the smallest headroom; the first one that tripped
+    where one did), its largest |x| and headroom, the totals of the counts, and the windows that fell back"""
+    sites = [s for e in log for s in (e["sites"] or [])]
+    # ('tripped_at' counts from 1 in every window's census: the first window that tripped, then the first site in it)
+    bad = next((tripped(e["sites"]) for e in log if e["sites"] and tripped(e["sites"])), [])
+    worst = bad[0] if bad else min(sites, key=lambda s: s["headroom"], default=None)
+    out = {"windows": len(log), "worst_site": None if worst is None else worst["site"],
+           "max_abs": 0.0 if worst is None else worst["max_abs"], "headroom": float("inf") if worst is None else worst["headroom"],
+           "fallbacks": [i for i, e in enumerate(log) if e["fallback"]],
+           "tail_fallbacks": [(i, f) for i, e in enumerate(log) for f in e["tail_fallback"]]}
+    out.update({k: sum(s[k] for s in sites) for k in ("nonfinite", "overflow", "subnormal")})
+    return out
+
+
 TRAIN_PRECISIONS = ops.TRAIN_PRECISIONS
 
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import re as _re
 from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
@@ -160,8 +161,24 @@ class profile:
         _prof = None
 
 
-def _launch(name: str, flops: float, nbytes: float, t: Tensor, fn, what: str):
-    """Run `fn()` (a C-ABI call returning an int status) on t's device and check it."""
+# The range census of the 16-bit backbone modes (addendum): None, or the `RangeCensus` that every launch of a 16-bit op
+# counts into while a `networks.backbone_check` is on.  `_launch` is the one place that reads it.
+RANGE16: Optional["RangeCensus"] = None
+
+
+def _launch(name: str, flops: float, nbytes: float, t: Tensor, fn, what: str, stored=None, rounded=None):
+    """Run `fn()` (a C-ABI call returning an int status) on t's device and check it.
+    What an op of the 16-bit modes rounds, declared where it launches: `stored` -- the 16-bit tensors the launch writes, counted behind
+    it (`range16_words`); `rounded` -- (fp32 tensors, dtype) that its kernel rounds on the way in, counted in front of it
+    (`range16_as_rounded`); `stored=()` says that a 16-bit op rounds nothing the census could see.  Read only while RANGE16 is set,
+    which then refuses a 16-bit launch (`RangeCensus.is_16bit`) that declares neither."""
+    if RANGE16 is not None and not name.startswith("range16"):
+        # (a site is named after `what`, the entry point: several of them share one profile name)
+        return RANGE16.around(what, stored, rounded, lambda: _launch_plain(name, flops, nbytes, t, fn, what))
+    return _launch_plain(name, flops, nbytes, t, fn, what)
+
+
+def _launch_plain(name: str, flops: float, nbytes: float, t: Tensor, fn, what: str):
     with _DeviceOf(t):
         if _prof is None:
             code = fn()
@@ -258,7 +275,8 @@ def flow_warp_pair(xa: Tensor, xb: Tensor, flow: Tensor, flow2: Optional[Tensor]
     st = _stream(xa)
     _launch("flow_warp_pair", 16.0 * n * c * h * w, 4.0 * n * h * w * (4 * c + 2 + (2 if flow2 is not None else 0)), xa,
             lambda: lib().eavsr_flow_warp_pair_f32(_p(xa), _p(xb), _p(flow), _p(flow2), _p(outa), _p(outb), n, c, h, w,
-                                                   mode | (N.WARP_PAIR_BORDER if pad else 0), st), "flow_warp_pair")
+                                                   mode | (N.WARP_PAIR_BORDER if pad else 0), st), "flow_warp_pair",
+            stored=(outb,) if isinstance(b_il8, str) else None)
     return outa, outb
 
 
@@ -289,7 +307,8 @@ def flow_warp_single(x: Tensor, flow: Tensor, flow2: Optional[Tensor] = None, il
     # (recorded under the kernel's name: both forms launch flow_warp_pair_kernel)
     _launch("flow_warp_pair", 8.0 * n * c * h * w,
             4.0 * n * h * w * (2 * c + 2 + (2 if flow2 is not None else 0)), x,
-            lambda: lib().eavsr_flow_warp_single_f32(_p(x), _p(flow), _p(flow2), _p(out), n, c, h, w, mode, pad, st), "flow_warp_single")
+            lambda: lib().eavsr_flow_warp_single_f32(_p(x), _p(flow), _p(flow2), _p(out), n, c, h, w, mode, pad, st), "flow_warp_single",
+            stored=(out,) if isinstance(il8, str) else None)
     return out
 
 
@@ -900,7 +919,9 @@ def conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequence
         d.ca_scale, d.ca_x, d.ca_out = _p(ca[0]), _p(ca[1]), _p(xs)
     st = _stream(out)
     flops, nbytes = _conv_cost(n, h, w, k, cin, cout, l_res is not None, 1 if ca is None else 3 if ca_out else 2)
-    _launch(r.name, flops, nbytes, out, lambda: call(lib(), d, _p(wq), aux, st), what)
+    # (the 16-bit routes round their fp32 sources inside the kernel: counted as rounded, in front of the launch, under a census)
+    _launch(r.name, flops, nbytes, out, lambda: call(lib(), d, _p(wq), aux, st), what,
+            rounded=(srcs, CONV3_H16) if fam in ("h16x1", "h16g") else None)
     # ---- the second step of a fallback form
     for step in r.post:
         if step == "plane_sum":
@@ -1144,7 +1165,7 @@ def to_il8_h16(x: Tensor, dtype) -> Tensor:
     out = torch.empty((n, c // 8, h, w, 8), device=x.device, dtype=_H16_TORCH[code])
     st = _stream(x)
     _launch("nchw_to_il8_h16", 0.0, 6.0 * x.numel(), x,
-            lambda: lib().eavsr_nchw_to_il8_h16(_p(x), _p(out), n, c, h, w, code, st), "nchw_to_il8_h16")
+            lambda: lib().eavsr_nchw_to_il8_h16(_p(x), _p(out), n, c, h, w, code, st), "nchw_to_il8_h16", stored=(out,))
     return out
 
 
@@ -1162,7 +1183,7 @@ def dcnv2_il16(x_il8: Tensor, offset_or_heads: Tensor, mask: Optional[Tensor], w
     # algorithmic bytes of the 16-bit DCNv2 as SURVEY 8a counts them: 344 elements x 2 bytes per pixel
     _launch("dcnv2_il16" + ("_heads" if heads else ""), 2.0 * cin * 9 * cout * px, 2.0 * px * (cin + 27 * D + cout), out,
             lambda: lib().eavsr_dcnv2_il16(_p(x_il8), _p(oh), _p(mask), _p(wp), _p(b), _p(out), n, cin, h, w, cout, D, code,
-                                           1 if heads else 0, st), "dcnv2_il16")
+                                           1 if heads else 0, st), "dcnv2_il16", stored=())
     return out
 
 
@@ -1974,6 +1995,205 @@ def unpack16(srcs: Sequence[Tensor], dsts: Sequence[Tensor]) -> List[Tensor]:
     dt = cache16_dtype(srcs[0].dtype)
     srcs, dsts = _cache16_lists("unpack16", srcs, dsts, dt, torch.float32)
     return _cache16_run("unpack16", "eavsr_unpack16", srcs, dsts, _CACHE16_CODE[dt])
+
+
+# ------------------------------------------------------------------------------------------
+# the range census of the 16-bit backbone modes (csrc/range16.hip, DESIGN 3.6 addendum)
+# ------------------------------------------------------------------------------------------
+RANGE16_MAX_ROWS = 4096        # contiguous rows a non-contiguous tensor may be counted through; beyond it the call is refused
+RANGE16_FLAVOURS = ("words", "as_rounded")
+FORMAT_MAX = {"fp16": 65504.0, "bf16": float.fromhex("0x1.fep127")}      # the largest finite value of each format
+
+
+def contiguous_runs(shape: Sequence[int], strides: Sequence[int]) -> Tuple[int, List[int]]:
+    """(run, offsets): a strided tensor as rows of `run` contiguous elements that start `offsets` elements past its first -- pure
+    host code.  The trailing dimensions that lie densely in memory make a row; the leading ones are walked in index order.  Sizes of
+    1 are ignored; an empty tensor has no rows.  Overlapping or negative strides are the caller's to refuse."""
+    dims = [(int(n), int(s)) for n, s in zip(shape, strides) if n != 1]
+    if any(n == 0 for n, _ in dims):
+        return 0, []
+    run = 1
+    while dims and dims[-1][1] == run:
+        run *= dims.pop()[0]
+    offsets = [0]
+    for n, s in dims:
+        offsets = [o + i * s for o in offsets for i in range(n)]
+    return run, offsets
+
+
+def _range16_segments(who: str, tensors, dtype_ok) -> Tuple[List[Tuple[int, int]], int, Optional[Tensor]]:
+    """[(address, elements)] of every contiguous run of the tensors, the elements in all, and the first tensor"""
+    segs, first = [], None
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: tensor {i}: expected a tensor, got {type(t)}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensor {i} is on {t.device}; eavsr_amd runs on the GPU only (no CPU path)")
+        if not dtype_ok(t.dtype):
+            raise ValueError(f"{who}: tensor {i}: dtype {t.dtype}")
+        first = t if first is None else first
+        if t.device != first.device:
+            raise ValueError(f"{who}: tensor {i} on {t.device}, tensor 0 on {first.device}")
+        if any(s < 0 for s in t.stride()):
+            raise ValueError(f"{who}: tensor {i} has a negative stride")
+        run, offsets = contiguous_runs(t.shape, t.stride())
+        if len(offsets) > RANGE16_MAX_ROWS:
+            raise ValueError(f"{who}: tensor {i} ({tuple(t.shape)}, strides {tuple(t.stride())}) is {len(offsets)} contiguous rows of "
+                             f"{run} elements; at most {RANGE16_MAX_ROWS} are counted row by row -- pass a contiguous tensor")
+        if len(offsets) > 1 and len(set(offsets)) * run != t.numel():
+            raise ValueError(f"{who}: tensor {i} overlaps itself (strides {tuple(t.stride())}): an element would be counted twice")
+        es = t.element_size()
+        segs += [(t.data_ptr() + o * es, run) for o in offsets]
+    return segs, sum(n for _, n in segs), first
+
+
+def _range16(who: str, tensors, dtype, census: Tensor, rounded: bool) -> int:
+    dt = cache16_dtype(dtype)
+    if not isinstance(census, torch.Tensor):
+        raise TypeError(f"{who}: census: expected a tensor, got {type(census)}")
+    if census.dtype != torch.int64 or tuple(census.shape) != (len(CENSUS_SLOTS),) or not census.is_contiguous():
+        raise ValueError(f"{who}: census: a contiguous int64 tensor of {len(CENSUS_SLOTS)} elements, got {census.dtype} "
+                         f"{tuple(census.shape)}{'' if census.is_contiguous() else ', not contiguous'}")
+    if not census.is_cuda:
+        raise RuntimeError(f"{who}: census is on {census.device}; eavsr_amd runs on the GPU only (no CPU path)")
+    want = (lambda d: d == torch.float32) if rounded else (lambda d: d == dt)
+    segs, total, first = _range16_segments(who, list(tensors), want)
+    if first is not None and census.device != first.device:
+        raise ValueError(f"{who}: census on {census.device}, the tensors on {first.device}")
+    if total == 0:
+        return 0
+    cp, st, entry = C.c_void_p(census.data_ptr()), _stream(first), "eavsr_" + who
+    for a, b in cache16_batches(len(segs)):
+        part = [s for s in segs[a:b] if s[1]]
+        if not part:
+            continue
+        sl = (C.c_void_p * len(part))(*[p for p, _ in part])
+        nl = (C.c_int64 * len(part))(*[n for _, n in part])
+        _launch(who, 0.0, (4.0 if rounded else 2.0) * sum(n for _, n in part), first,
+                lambda: getattr(lib(), entry)(sl, nl, len(part), _CACHE16_CODE[dt], cp, st), who)
+    return total
+
+
+def range16_words(tensors: Sequence[Tensor], census: Tensor) -> int:
+    """Count the 16-bit words of `tensors` -- fp16 or bf16, all of one dtype, what some kernel has stored -- into `census`
+    (`pack16_census`'s record: five int64 on the tensors' device, ADDED into, slots CENSUS_SLOTS) in one launch per
+    CACHE16_MAX_SEGMENTS contiguous runs (csrc/range16.hip).  An element's fp32 bits are the exact widening of its word: 'max_abs' is
+    the largest finite stored value, 'nonfinite' counts inf / NaN words, 'subnormal' subnormal words; 'overflow' and 'flushed' stay 0.
+    A non-contiguous tensor is counted through its contiguous rows (at most RANGE16_MAX_ROWS; more, or a tensor that overlaps
+    itself, is refused).  Writes nothing but the record.  Returns the number of elements counted: the caller's to keep."""
+    tensors = list(tensors)
+    if not tensors:
+        return 0
+    if not isinstance(tensors[0], torch.Tensor):
+        raise TypeError(f"range16_words: tensor 0: expected a tensor, got {type(tensors[0])}")
+    return _range16("range16_words", tensors, tensors[0].dtype, census, False)
+
+
+def range16_as_rounded(tensors: Sequence[Tensor], dtype, census: Tensor) -> int:
+    """Count the fp32 `tensors` as a kernel that rounds them to `dtype` ("fp16" / "bf16") would leave them: `pack16_census`'s record
+    of the same values -- the same rounding function -- without the store.  Lists, rows, record and return value as `range16_words`."""
+    return _range16("range16_as_rounded", list(tensors), dtype, census, True)
+
+
+def headroom(max_abs: float, dtype) -> float:
+    """the largest finite value of the format over the largest |x| seen: 65504 / max_abs (fp16); inf where nothing but zeros was seen"""
+    name = next(k for k, v in CACHE16_DTYPES.items() if v == cache16_dtype(dtype))
+    if not max_abs >= 0.0:
+        raise ValueError(f"headroom: max_abs {max_abs!r}")
+    return float("inf") if max_abs == 0.0 else FORMAT_MAX[name] / float(max_abs)
+
+
+class RangeCensus:
+    """One census of a checked call: a device tensor of (CAPACITY, 5) int64 rows, zeroed once, and the host's table of sites.  A SITE is
+    (scope, op, flavour, k): the k-th launch of `op` since the scope was last marked (`mark`) -- the model marks a scope at every
+    time step of a branch and at every chunk of a batched stage, so the same position of every time step shares one row; the
+    elements counted per row accumulate here, on the host.  `around` is `_launch`'s hook.  No synchronisation before `read`."""
+    CAPACITY = 1024
+    _16BIT = _re.compile(r"h16|il16")
+
+    def __init__(self, dtype, device):
+        self.dtype = next(k for k, v in CACHE16_DTYPES.items() if v == cache16_dtype(dtype))
+        # (a row: the record's five words, then the tick at which it first held a non-finite or an overflowed element, 0: never)
+        self.rows = torch.zeros((self.CAPACITY, len(CENSUS_SLOTS) + 1), dtype=torch.int64, device=device)
+        self._tick = 0
+        self.sites: List[Dict] = []
+        self._index: Dict[Tuple, int] = {}
+        self._scope, self._seen = "", {}
+
+    @classmethod
+    def is_16bit(cls, name: str) -> bool:
+        """a launch that must say what it rounds: the kernels named after the 16-bit types"""
+        return cls._16BIT.search(name) is not None
+
+    def mark(self, scope: str) -> None:
+        """the launches that follow belong to `scope`, counted from its first position again"""
+        self._scope, self._seen = str(scope), {}
+
+    def _row(self, op: str, flavour: str, elements: int) -> Tensor:
+        k = self._seen.get((op, flavour), 0)
+        self._seen[(op, flavour)] = k + 1
+        key = (self._scope, op, flavour, k)
+        i = self._index.get(key)
+        if i is None:
+            if len(self.sites) >= self.CAPACITY:
+                raise RuntimeError(f"range census: more than {self.CAPACITY} sites in one call")
+            i = self._index[key] = len(self.sites)
+            self.sites.append({"site": f"{self._scope or '-'}/{op}#{k}" + (":in" if flavour == "as_rounded" else ""), "scope": self._scope,
+                               "op": op, "index": k, "flavour": flavour, "elements": 0})
+        self.sites[i]["elements"] += int(elements)
+        return self.rows[i]
+
+    def _count(self, count, row: Tensor) -> None:
+        """one counting call into a site's row, and the stamp behind it (csrc/range16.hip: when the row first left the range)"""
+        count(row[:len(CENSUS_SLOTS)])
+        self._tick += 1
+        rp, sp, tick, st = C.c_void_p(row.data_ptr()), C.c_void_p(row[len(CENSUS_SLOTS):].data_ptr()), self._tick, _stream(row)
+        _launch("range16_stamp", 0.0, 48.0, row, lambda: lib().eavsr_range16_stamp(rp, sp, tick, st), "range16_stamp")
+
+    def around(self, name: str, stored, rounded, launch):
+        if stored is None and rounded is None:
+            if self.is_16bit(name):
+                raise RuntimeError(f"range census: the 16-bit launch {name!r} does not say what it rounds (ops._launch(stored=, rounded=))")
+            return launch()
+        if rounded is not None and len(rounded[0]):
+            tensors, dtype = rounded
+            if cache16_dtype(dtype) != CACHE16_DTYPES[self.dtype]:
+                raise RuntimeError(f"range census of {self.dtype}: {name!r} rounds to {dtype!r}")
+            self._count(lambda r: range16_as_rounded(tensors, dtype, r), self._row(name, "as_rounded", sum(int(t.numel()) for t in tensors)))
+        out = launch()
+        if stored:
+            if any(t.dtype != CACHE16_DTYPES[self.dtype] for t in stored):
+                raise RuntimeError(f"range census of {self.dtype}: {name!r} stored {[t.dtype for t in stored]}")
+            self._count(lambda r: range16_words(stored, r), self._row(name, "words", sum(int(t.numel()) for t in stored)))
+        return out
+
+    def read(self) -> List[Dict]:
+        """the sites in call order (of their first launch), each `census_record`'s fields beside its name and a 'headroom' -- ONE read-back (the host waits)"""
+        rows = self.rows[:len(self.sites)].cpu().tolist() if self.sites else []
+        out = []
+        for site, row in zip(self.sites, rows):
+            rec = census_record(row[:len(CENSUS_SLOTS)], site["elements"], self.dtype)
+            # 'tripped_at': the count of counting launches at which the row first held inf / NaN or an overflow (0: never) -- rows are
+            # shared by time steps, so call order alone does not say which site left the range first
+            out.append({**site, **rec, "headroom": headroom(rec["max_abs"], self.dtype), "tripped_at": int(row[len(CENSUS_SLOTS)])})
+        return out
+
+
+@contextlib.contextmanager
+def range_census(census: Optional[RangeCensus]):
+    """`with ops.range_census(c):` -- the 16-bit launches of the body count into `c` (None: no census); the previous one is restored"""
+    global RANGE16
+    prev, RANGE16 = RANGE16, census
+    try:
+        yield census
+    finally:
+        RANGE16 = prev
+
+
+def range_mark(scope: str) -> None:
+    """name the part of the model whose launches follow (a branch's time step, a chunk of a batched stage): nothing without a census"""
+    if RANGE16 is not None:
+        RANGE16.mark(scope)
 
 
 def frame_change(frames: Tensor, hwc: Optional[bool] = None):
@@ -2910,7 +3130,7 @@ def to_nhwc_h16(x: Tensor, dtype) -> Tensor:
     out = torch.empty((n, h, w, c), device=x.device, dtype=_H16_TORCH[code])
     st = _stream(x)
     _launch("nchw_f32_to_nhwc_h16", 0.0, 6.0 * x.numel(), x,
-            lambda: lib().eavsr_nchw_f32_to_nhwc_h16(_p(x), _p(out), n, c, h * w, code, st), "nchw_f32_to_nhwc_h16")
+            lambda: lib().eavsr_nchw_f32_to_nhwc_h16(_p(x), _p(out), n, c, h * w, code, st), "nchw_f32_to_nhwc_h16", stored=(out,))
     return out
 
 
@@ -2927,7 +3147,7 @@ def from_nhwc_h16(x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
     st = _stream(x)
     _launch("nhwc_h16_to_nchw_f32", 0.0, 6.0 * x.numel(), x,
             lambda: lib().eavsr_nhwc_h16_to_nchw_f32(_p(x), _p(residual), _p(out), n, c, h * w, code, st),
-            "nhwc_h16_to_nchw_f32")
+            "nhwc_h16_to_nchw_f32", stored=())
     return out
 
 
@@ -2959,11 +3179,11 @@ def conv3x3_c64_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], relu: boo
         pieces = BorderPieces(torch.empty((n, 4, stride, 64), device=x.device, dtype=torch.float32), pr.value, pc.value)
         _launch("conv3x3_64to64_h16", 2.0 * 64 * 64 * 9 * px, 2.0 * px * 128, x,
                 lambda: lib().eavsr_conv3x3_c64_h16_b(_p(x), _p(wp), _p(b), _p(out), _p(part), _p(pieces.data), stride, n, h, w,
-                                                      1 if relu else 0, code, st), "conv3x3_c64_h16_b")
+                                                      1 if relu else 0, code, st), "conv3x3_c64_h16_b", stored=(out,))
         return out, part, pieces
     _launch("conv3x3_64to64_h16", 2.0 * 64 * 64 * 9 * px, 2.0 * px * 128, x,
             lambda: lib().eavsr_conv3x3_c64_h16(_p(x), _p(wp), _p(b), _p(out), _p(part), n, h, w, 1 if relu else 0, code, st),
-            "conv3x3_c64_h16")
+            "conv3x3_c64_h16", stored=(out,))
     return (out, part) if chan_partial else out
 
 
@@ -2992,12 +3212,12 @@ def ca_scale_pre_h16(t: Tensor, partial: Tensor, conv_weight: Tensor, conv_bias:
         _launch("ca_scale_pre_h16", 0.0, 4.0 * (partial.numel() + bd.numel()), t,
                 lambda: lib().eavsr_ca_scale_pre_pieces(_p(t), _p(partial), int(partial.shape[1]), _p(bd), border.p_rows, border.p_cols,
                                                         int(bd.shape[2]), _p(cw), _p(cb), _p(w1), _p(b1), _p(w2), _p(b2), _p(scale),
-                                                        n, h, w, cr, code, st), "ca_scale_pre_pieces")
+                                                        n, h, w, cr, code, st), "ca_scale_pre_pieces", stored=())
         return scale
     ws = torch.empty(int(lib().eavsr_ca_scale_pre_ws_floats(n)), device=t.device, dtype=torch.float32)
     _launch("ca_scale_pre_h16", 0.0, 4.0 * partial.numel(), t,
             lambda: lib().eavsr_ca_scale_pre_h16(_p(t), _p(partial), int(partial.shape[1]), _p(cw), _p(cb), _p(w1), _p(b1), _p(w2), _p(b2),
-                                                 _p(scale), _p(ws), n, h, w, cr, code, st), "ca_scale_pre_h16")
+                                                 _p(scale), _p(ws), n, h, w, cr, code, st), "ca_scale_pre_h16", stored=())
     return scale
 
 
@@ -3046,7 +3266,7 @@ def conv3x3_c64_h16_res(x: Tensor, weight: Tensor, bias: Optional[Tensor], skip:
     px = float(n) * h * w
     _launch("conv3x3_64to64_h16", 2.0 * 64 * 64 * 9 * px, 3.0 * px * 128, x,
             lambda: lib().eavsr_conv3x3_c64_h16_res(_p(x), _p(wp), _p(b), _p(out), _p(skip), _p(scale), n, h, w, code, st),
-            "conv3x3_c64_h16_res")
+            "conv3x3_c64_h16_res", stored=(out,))
     return out
 
 
@@ -3084,7 +3304,7 @@ def rcab_convs_h16(x: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: 
     px = float(n) * h * w
     _launch("rcab_convs_h16", 2.0 * 2.0 * 64 * 64 * 9 * px, 2.0 * px * 128, x,
             lambda: lib().eavsr_rcab_convs_h16(_p(x), _p(wp1), _p(bb1), _p(wp2), _p(bb2), _p(out), _p(part), n, h, w, code, st),
-            "rcab_convs_h16")
+            "rcab_convs_h16")      # (no declaration: its intermediate never leaves LDS, a census refuses the launch)
     return (out, part) if chan_partial else out
 
 
@@ -3133,7 +3353,7 @@ def conv3x3_c64_h16_act(x: Tensor, weight: Tensor, bias: Optional[Tensor], act: 
     co = 256 if pixel_shuffle2 else 64
     _launch("conv3x3_64to256_h16_ps2" if pixel_shuffle2 else "conv3x3_64to64_h16", 2.0 * 64 * co * 9 * px, px * (128 + 2 * co), x,
             lambda: lib().eavsr_conv3x3_c64_h16_act(_p(x), _p(wp), _p(b), _p(out), n, h, w, a, float(slope), 1 if pixel_shuffle2 else 0, code, st),
-            "conv3x3_c64_h16_act")
+            "conv3x3_c64_h16_act", stored=(out,))
     return out
 
 
@@ -3155,7 +3375,7 @@ def conv3x3_c64to3_h16(x: Tensor, weight: Tensor, bias: Optional[Tensor], residu
     px = float(n) * h * w
     _launch("conv3x3_64to3_h16", 2.0 * 64 * 3 * 9 * px, px * (128 + 12 + (12 if r is not None else 0)), x,
             lambda: lib().eavsr_conv3x3_c64to3_h16(_p(x), _p(wt), _p(b), _p(r), _p(out), n, h, w, h16_code(x.dtype), st),
-            "conv3x3_c64to3_h16")
+            "conv3x3_c64to3_h16", stored=())
     return out
 
 
@@ -3186,7 +3406,7 @@ def conv5x5_c64_h16(x: Tensor, weights, biases) -> Tensor:
     st = _stream(x)
     px = float(n) * h * w
     _launch(f"conv5x5_64to{cout}_h16", 2.0 * 64 * cout * 25 * px, px * (128 + 4.0 * cout), x,
-            lambda: lib().eavsr_conv5x5_c64_h16(_p(x), _p(wp), _p(b), _p(out), n, h, w, cout, code, st), "conv5x5_c64_h16")
+            lambda: lib().eavsr_conv5x5_c64_h16(_p(x), _p(wp), _p(b), _p(out), n, h, w, cout, code, st), "conv5x5_c64_h16", stored=())
     return out
 
 
@@ -3200,7 +3420,7 @@ def scale_residual_h16(r: Tensor, scale: Tensor, x: Tensor) -> Tensor:
     st = _stream(r)
     _launch("scale_residual_h16", 2.0 * r.numel(), 6.0 * r.numel(), r,
             lambda: lib().eavsr_scale_residual_h16(_p(r), _p(scale), _p(x), _p(out), n, c, h * w, code, st),
-            "scale_residual_h16")
+            "scale_residual_h16", stored=(out,))
     return out
 
 

@@ -826,6 +826,22 @@ int eavsr_unpack16(const void* const* src_list, void* const* dst_list, const int
  * NULL census: -1; a census that is not 8-byte aligned: -2; everything else as eavsr_pack16. */
 int eavsr_pack16_census(const void* const* src_list, void* const* dst_list, const int64_t* n_list, int32_t nseg, int32_t dtype,
                         uint64_t* census, void* stream);
+/* ---- the range census of the 16-bit backbone modes (csrc/range16.hip; added to ABI 32, nothing above changes) -------------------------
+ * What the kernels of the 16-bit modes round to fp16 / bf16, counted into eavsr_pack16_census's record (the same five slots, the same
+ * reduction, the census ADDED into) by a launch that writes nothing else.  A list of contiguous segments per launch, as eavsr_pack16's;
+ * 16-byte loads with scalar heads and tails at any element alignment, 64-bit extents, at most 2048 workgroups.
+ *   eavsr_range16_words       src_list[s]: n_list[s] 16-bit words (2-byte aligned) that a kernel has stored.  u is the exact widening
+ *                             of the word o: max_abs the largest finite stored value, nonfinite the inf / NaN words, subnormal the
+ *                             subnormal words; overflow and flushed stay 0.
+ *   eavsr_range16_as_rounded  src_list[s]: n_list[s] fp32 values (4-byte aligned) that a kernel is about to round.  o is eavsr_pack16's
+ *                             result for the value: the record is eavsr_pack16_census's on the same input.
+ * dtype: EAVSR_CACHE16_FP16 / EAVSR_CACHE16_BF16.  Error codes as eavsr_pack16_census.  Nothing to count: 0, nothing is launched. */
+int eavsr_range16_words(const void* const* src_list, const int64_t* n_list, int32_t nseg, int32_t dtype, uint64_t* census, void* stream);
+int eavsr_range16_as_rounded(const void* const* src_list, const int64_t* n_list, int32_t nseg, int32_t dtype, uint64_t* census,
+                             void* stream);
+/* eavsr_range16_stamp: *stamp = tick where census[1] | census[2] != 0 and *stamp == 0 -- one lane, stream-ordered behind the launches that
+ * counted: when a record that several launches share first held a non-finite or an overflowed element.  tick 0: -2. */
+int eavsr_range16_stamp(const uint64_t* census, uint64_t* stamp, uint64_t tick, void* stream);
 /* ---- training batches from device-resident 8-bit frames (added to ABI 32, nothing above changes) -------------------------------------
  * The reference's training item (data/realvsr_dataset.py:62-94: window, `_crop_patch`; util/util.py:223-248 `augment_basic`;
  * `np.float32(img) / 255`) for a whole batch, LR and HR together, as one launch (csrc/batch.hip).
