@@ -108,7 +108,7 @@ struct W4Args {
   float slope;
   int out_shuffle;        // 2: out is F.pixel_shuffle(conv, 2), (n, cout / 4, 2h, 2w); 0: (n, cout, h, w)
   const float* res_scale; // (n, cout) or NULL: out = residual + res_scale[n][co] * act(conv + bias) (3x3; the RCAB tail as the epilogue)
-  float* border;          // NULL, or [n][4][border_stride][64]: sums of the OUTPUT's four border lines per border tile (desc.border_pieces)
+  float* border;          // NULL, or [n][4][border_stride][64]: sums of act(conv + bias) -- BEFORE the residual, as chan_partial -- over the four border lines, per border tile (desc.border_pieces)
   int border_stride;
 };
 
@@ -909,7 +909,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
         };
         if (has_res) load_rr(0);
         f32x2 cs2[4] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}};
-        // desc.border_pieces (round 6): the sums of the OUTPUT's border lines that fall into this tile -- what eavsr_ca_scale_pre needs
+        // desc.border_pieces (round 6): the sums of act(conv + bias), BEFORE the residual is added (the same values the channel sums add up), over
+        // the border lines that fall into this tile (piece layout: DESIGN.md 4b) -- what eavsr_ca_scale_pre needs
         // beside the plane sums to know the NEXT convolution's channel means before it runs -- as a by-product of the epilogue (was: a
         // launch of its own on every RCAB's dependent chain).  Row 0 / h - 1 of the image: this wave's row dy of the 4-pixel blocks,
         // summed over its 16 lanes; column 0 / w - 1: pixel 0 / 3 of one lane's block, summed over the wave's rows.
@@ -1186,7 +1187,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
 }
 
 // weight (cout, cin, R, R) -> U = G g G^T laid out [cot][cin / 4][xi / 2][c][co ^ 16 (c & 1)][xi & 1] (zero for
-// co >= cout); evaluated in double and rounded once.  G[p] = scale_p * (1, p, p^2, ..) for the points 0, 1, -1, 2, -2
+// co >= cout); evaluated in double and rounded once.  1/6 and 1/24 are not doubles: where the terms of a position cancel, the sum is not 0 but
+// that evaluation's residue (~1e-13 for weights of ~1e3, < 2^-45 of the terms' magnitudes; tests/wino4_contract.py check_pack).  G[p] = scale_p * (1, p, p^2, ..) for the points 0, 1, -1, 2, -2
 // (scales 1/4, -1/6, -1/6, 1/24, 1/24) and the unit vector of the highest power for the point at infinity.
 template <int R>
 __global__ void pack_wino6_kernel(const float* __restrict__ wt, float* __restrict__ out, int cout, int cin, long total) {

@@ -628,7 +628,8 @@ def dgrad_weight(w: Tensor) -> Tensor:
 
 class BorderPieces:
     """what conv2d(.., border=True) leaves beside the per-tile channel sums: `data` (n, 4, stride, 64) -- border 0 / 1 = image row 0 /
-    h - 1 (`p_rows` pieces), 2 / 3 = image column 0 / w - 1 (`p_cols` pieces) of the convolution's OUTPUT (desc.border_pieces)"""
+    h - 1 (`p_rows` pieces of 64 columns), 2 / 3 = image column 0 / w - 1 (`p_cols` pieces of 4 rows) of act(conv + bias), i.e. of what the
+    channel sums add up: the convolution's output BEFORE the residual (desc.border_pieces; DESIGN.md 4b has the layout)"""
     __slots__ = ("data", "p_rows", "p_cols")
 
     def __init__(self, data: Tensor, p_rows: int, p_cols: int):
@@ -824,7 +825,7 @@ def conv2d(srcs: Union[Tensor, Sequence[Tensor]], weight: Union[Tensor, Sequence
            sum_mul: Optional[Tensor] = None, precision: str = "fp32"):
     """conv over the virtual channel-concatenation of `srcs`; `weight` may be a list of weights
     that are concatenated along cout (several heads in one launch).
-    border=True (with chan_partial=True): a last result, the sums of the output's four border lines per border tile
+    border=True (with chan_partial=True): a last result, the sums of act(conv + bias) (before the residual) over the four border lines per border tile
     (`BorderPieces`, for ca_scale_pre(.., border=)) where the grouped F(4x4,3x3) kernel runs, None on every other route.
     res_scale (n, cout) with `residual`: out = residual + res_scale[n, co] * act(conv + bias) -- RCABlock's tail as the epilogue of
     the F(4x4,3x3) kernel (the attention from ca_scale_pre BEFORE the launch); other routes: the convolution, then scale_residual.
