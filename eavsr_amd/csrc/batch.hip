@@ -22,7 +22,7 @@
 //     rows 4l+i at byte (4l + i) * 33 + y = 132 l + const, i.e. dword 33 l + const, bank (l + const) % 32 -- the 32 lanes of a
 //     half (one output row) hit 32 distinct banks, 0 conflicts predicted.  (A dword-multiple stride S puts them on 4 l S/4 % 32:
 //     at most 8 banks.)  The odd stride costs byte writes on the way in.
-#include "common.h"
+#include "pixel.h"
 
 #include <stdint.h>
 
@@ -32,10 +32,6 @@ constexpr int kThreads = 256;
 constexpr int kTX = 128;           // output columns of a tile
 constexpr int kTY = 32;            // output rows of a tile
 constexpr int kStride = kTY + 1;   // bytes per LDS row of the transposed path
-
-__device__ __forceinline__ float unit(uint32_t v) { return (float)v / 255.0f; }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // bytes j = 0..3 of the result: crop[row][hflip ? pw-1-(c0+j) : c0+j], 0 where c0 + j >= pw.  `row` is the byte offset of the crop
 // row's first FRAME column in the store, `left` the crop's first column, `total` the store's size (nothing is read at or past it).

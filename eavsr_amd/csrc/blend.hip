@@ -19,7 +19,7 @@
 // SOURCE, reads its rows along their unit stride into LDS with a row pitch of 65 dwords, and writes (blends) destination rows along
 // THEIR unit stride from LDS columns; with the odd pitch lane l of a row write hits bank (65 r + l) mod 64 and lane l of a column read
 // bank (65 l + c) mod 64: distinct per lane.  The flips move the tile's destination coordinates.  Tiles have tails on both axes.
-#include "common.h"
+#include "pixel.h"
 
 #include <stdint.h>
 
@@ -29,32 +29,6 @@ constexpr int kLanes = 64;      // threadIdx.x: along the row
 constexpr int kRows = 4;        // threadIdx.y: one wave per row
 constexpr int kTile = 64;       // the transposing kernels' square tile
 constexpr int kPitch = 65;      // its row pitch in LDS, dwords: odd
-
-// 4 consecutive floats at p: `align` is 16, 8 or 4, what p is aligned to (uniform over the wave: a property of the row)
-__device__ __forceinline__ float4 load_quad(const float* p, int align) {
-  if (align == 16) return *reinterpret_cast<const float4*>(p);
-  if (align == 8) {
-    const float2 a = *reinterpret_cast<const float2*>(p), b = *reinterpret_cast<const float2*>(p + 2);
-    return make_float4(a.x, a.y, b.x, b.y);
-  }
-  return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-__device__ __forceinline__ void store_quad(float* p, int align, float4 v) {
-  if (align == 16) {
-    *reinterpret_cast<float4*>(p) = v;
-  } else if (align == 8) {
-    *reinterpret_cast<float2*>(p) = make_float2(v.x, v.y);
-    *reinterpret_cast<float2*>(p + 2) = make_float2(v.z, v.w);
-  } else {
-    p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
-  }
-}
-
-__device__ __forceinline__ int align_of(const void* p) {
-  const uintptr_t a = (uintptr_t)p;
-  return (a & 15) == 0 ? 16 : ((a & 7) == 0 ? 8 : 4);
-}
 
 // the quad of a row of `w` samples that a mirrored row shows at x = 4 xv .. 4 xv + 3: samples w - 4 - x .. w - 1 - x, reversed.
 // `tail` = row + (w & 3), where the row's last whole quad counted from its END starts; all quads lie 16 bytes apart from it.

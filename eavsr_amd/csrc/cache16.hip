@@ -21,7 +21,7 @@
 //             non-finite inputs, the overflows to +-inf, the flushes to +-0 and the subnormal results.  The definitions, the lane's
 //             registers and the one reduction per workgroup (cross-lane moves, a few words of LDS, one update per non-zero slot) are
 //             cache16_census.h's; with the switch off nothing of it is compiled and pack16 is the kernel it was.
-#include "common.h"
+#include "pixel.h"
 #include "cache16_census.h"
 #include "round16.h"
 
@@ -53,31 +53,6 @@ __host__ __device__ inline Cut cut_of(const void* p16, int64_t n) {
   if (head > n) head = n;
   const int64_t nvec = (n - head) >> 3;
   return Cut{head, nvec, n - 7 * nvec};      // nvec vectors + (n - 8 nvec) scalar elements
-}
-
-__device__ __forceinline__ int align_of(const void* p) {
-  const uintptr_t a = (uintptr_t)p;
-  return (a & 15) == 0 ? 16 : ((a & 7) == 0 ? 8 : 4);
-}
-
-__device__ __forceinline__ float4 load_quad(const float* p, int align) {
-  if (align == 16) return *reinterpret_cast<const float4*>(p);
-  if (align == 8) {
-    const float2 a = *reinterpret_cast<const float2*>(p), b = *reinterpret_cast<const float2*>(p + 2);
-    return make_float4(a.x, a.y, b.x, b.y);
-  }
-  return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-__device__ __forceinline__ void store_quad(float* p, int align, float4 v) {
-  if (align == 16) {
-    *reinterpret_cast<float4*>(p) = v;
-  } else if (align == 8) {
-    *reinterpret_cast<float2*>(p) = make_float2(v.x, v.y);
-    *reinterpret_cast<float2*>(p + 2) = make_float2(v.z, v.w);
-  } else {
-    p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
-  }
 }
 
 using round16_ns::round16;      // (round16.h: shared with the range census of the 16-bit backbone, range16.hip)

@@ -46,6 +46,35 @@ static inline int current_device() {
   return (d >= 0 && d < kMaxDevices) ? d : 0;
 }
 
+// Raises Kernel's dynamic LDS limit to `bytes` on the current device, before its first launch there and never again: the flags
+// and the results are statics of the instantiation, so the state is per (kernel, device).  0, or the hipError_t (message recorded).
+template <auto Kernel>
+int raise_lds(size_t bytes, const char* who) {
+  static PerDeviceOnce once;
+  static hipError_t err[kMaxDevices] = {};
+  const int dev = current_device();
+  std::call_once(once.flag[dev], [&] {
+    err[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (err[dev] != hipSuccess) {
+    set_error("%s: hipFuncSetAttribute(%zu B of LDS): %s", who, bytes, hipGetErrorString(err[dev]));
+    return (int)err[dev];
+  }
+  return 0;
+}
+
+// compute units of the current device (the grid size of the persistent kernels), cached per device; 256 if the runtime does not say
+inline int cu_count() {
+  static int cus[kMaxDevices] = {};
+  static PerDeviceOnce once;
+  const int dev = current_device();
+  std::call_once(once.flag[dev], [&] {
+    int v = 0;
+    cus[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  });
+  return cus[dev];
+}
+
 }  // namespace eavsr
 
 #define EAVSR_REQUIRE(cond, code, ...)      \

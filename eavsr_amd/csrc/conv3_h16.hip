@@ -15,18 +15,11 @@
 // Per chunk: ONE barrier; behind it the next chunk's weights are requested (LDS-DMA) and its patch loaded into registers
 // (thread = one aligned 4-pixel quad x 8 channels: eight 16-byte loads, rounded and stored as four ds_write_b128 after this
 // chunk's MFMAs), so global latency hides under the 36 MFMAs per wave.
-#include "common.h"
+#include "mfma.h"
 
 #include <hip/hip_bf16.h>
-#include <mutex>
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int G_TH = 16, G_TW = 32, G_CO = 64, G_CK = 16;
 constexpr int G_IH = G_TH + 2;                                  // patch rows y0-1 .. y0+16
@@ -58,12 +51,6 @@ template <> __device__ __forceinline__ unsigned pack2_h16<true>(float a, float b
 }
 template <> __device__ __forceinline__ unsigned pack2_h16<false>(float a, float b) {
   return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)a) | ((unsigned)__builtin_bit_cast(unsigned short, (_Float16)b) << 16);
-}
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 g_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  if (BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
 }
 
 #ifndef EAVSR_H16G_WAVES
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(512, EAVSR_H16G_WAVES) void conv3x3_h16g_kernel(G16
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) acc[m][t] = g_mfma<BF16>(av[m], bv[t], acc[m][t]);
+        for (int t = 0; t < 2; ++t) acc[m][t] = eavsr_mfma16<BF16>(av[m], bv[t], acc[m][t]);
     }
     if (more) {
       // the patch of the next chunk: its eight loads were issued before the weight requests (3 per wave, 2 for waves 2..7)
@@ -227,18 +214,7 @@ __global__ void pack_weight_h16g_kernel(const float* __restrict__ w, unsigned sh
 
 template <bool BF16>
 int launch_h16g(const G16Args& a, dim3 grid, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_h16g_kernel<BF16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv3x3_h16g: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv3x3_h16g_kernel<BF16>>(G_LDS_BYTES, "conv3x3_h16g")) return rc;
   hipLaunchKernelGGL(conv3x3_h16g_kernel<BF16>, grid, dim3(512), G_LDS_BYTES, st, a);
   return eavsr::launch_status("conv3x3_h16g");
 }

@@ -29,16 +29,11 @@
 // of waiting for a whole CU.  The 8 x 32 tile is kept: the chan_partial rows stay those of eavsr_conv3x3_x6s_tiles, and in the
 // configs[3] step (tools/gpu_train_precision_time.py, rocprofv3) a launch is 11.1 us against the exact kernel's 17.6 -- what is
 // left is the prologue load and the epilogue, so a smaller tile is the next thing to measure.
-#include "common.h"
+#include "mfma.h"
 
-#include <mutex>
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int Q_NW = 8, Q_TW = 32, Q_TH = 8;
 constexpr int Q_IW = Q_TW + 2, Q_IH = Q_TH + 2, Q_NPIX = Q_IW * Q_IH;      // 34 x 10 = 340 patch pixels
@@ -70,33 +65,10 @@ struct QArgs {
   float slope;
 };
 
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void q_split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-// two fp32 values rounded to nearest even into one packed bf16 pair (low half = first value): v_cvt_pk_bf16_f32, what
-// torch.Tensor.to(torch.bfloat16) computes (no truncation)
-__device__ __forceinline__ unsigned q_rne2(float a, float b) {
-  typedef float f2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{a, b}, b2_));
-}
-
 // the NP bf16 planes of two fp32 values
 template <int NP> __device__ __forceinline__ void q_planes2(float a, float b, unsigned (&pl)[NP]) {
-  if constexpr (NP == 3) q_split2(a, b, pl[0], pl[1], pl[2]);
-  else pl[0] = q_rne2(a, b);
-}
-
-__device__ __forceinline__ f32x16 q_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  if constexpr (NP == 3) eavsr_split2(a, b, pl[0], pl[1], pl[2]);
+  else pl[0] = eavsr_rne2(a, b);
 }
 
 #ifdef EAVSR_X6S_STAMPS
@@ -320,12 +292,12 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
       }
       if constexpr (NP == 3) {
         // the six partial products, smallest first: (A plane, B plane) = (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-        acc = q_mfma(acur[2], bcur[0], acc);
-        acc = q_mfma(acur[0], bcur[2], acc);
-        acc = q_mfma(acur[1], bcur[1], acc);
-        acc = q_mfma(acur[1], bcur[0], acc);
-        acc = q_mfma(acur[0], bcur[1], acc);
-        acc = q_mfma(acur[0], bcur[0], acc);
+        acc = eavsr_mfma_bf16(acur[2], bcur[0], acc);
+        acc = eavsr_mfma_bf16(acur[0], bcur[2], acc);
+        acc = eavsr_mfma_bf16(acur[1], bcur[1], acc);
+        acc = eavsr_mfma_bf16(acur[1], bcur[0], acc);
+        acc = eavsr_mfma_bf16(acur[0], bcur[1], acc);
+        acc = eavsr_mfma_bf16(acur[0], bcur[0], acc);
         if (!last || more) {
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
@@ -334,7 +306,7 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
           }
         }
       } else {
-        acc = q_mfma(acur[0], bcur[0], acc);                      // the one product of the rounded operands
+        acc = eavsr_mfma_bf16(acur[0], bcur[0], acc);                      // the one product of the rounded operands
         if (!last || more) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // the MFMA, then the next k-step's two reads
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
@@ -495,18 +467,7 @@ __global__ __launch_bounds__(512) void conv3x3_x6s_kernel(QArgs a) {
 template <int NCH, bool VEC, int NP>
 int launch_q(const QArgs& a, void* stream, const char* name) {
   using K = QCfg<NCH, NP>;
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_x6s_kernel<NCH, VEC, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)K::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("%s: hipFuncSetAttribute(%zu B of LDS): %s", name, K::LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv3x3_x6s_kernel<NCH, VEC, NP>>(K::LDS_BYTES, name)) return rc;
   const long blocks = (long)a.tiles_x * a.tiles_y * a.n;
   EAVSR_REQUIRE(blocks < (1L << 31), -1, "%s: too many tiles", name);
   dim3 grid((unsigned)blocks, eavsr::cdiv(a.cout, 32));

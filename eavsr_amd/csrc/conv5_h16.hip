@@ -14,17 +14,12 @@
 //   next pair behind the MFMAs of this one, one barrier per pair of taps (13 per tile).  The 16-row tile halves the weight re-streaming per pixel (98 MB of
 //   L2 -> LDS traffic per launch against 21 us of MFMA per tile).
 //   Output: fp32 NCHW (n, cout, h, w) -- the "heads" operand of eavsr_dcnv2_il16 / eavsr_affine_offsets_f32.
-#include "common.h"
+#include "mfma.h"
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
-#include <mutex>
 
 namespace {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int FT_H = 16, FT_W = 32, FR = 5, FPAD = 2;
 constexpr int FP_H = FT_H + 2 * FPAD, FP_W = FT_W + 2 * FPAD;   // 20 x 36 patch
@@ -51,16 +46,6 @@ template <> __device__ __forceinline__ unsigned short f_to_h16<true>(float v) {
 }
 template <> __device__ __forceinline__ unsigned short f_to_h16<false>(float v) {
   return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 f_mfma(const f32x4& a, const f32x4& b, const f32x16& c) {
-  if (BF16) {
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-  }
 }
 
 template <bool BF16>
@@ -154,8 +139,8 @@ __global__ __launch_bounds__(512, 2) void conv5x5_c64_h16_kernel(F16Args a) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const f32x4 af = *reinterpret_cast<const f32x4*>(wst + ((((cb * 2 + half) * FCO) + m * 32 + l31) << 4));
-          acc[0][m] = f_mfma<BF16>(af, b0, acc[0][m]);
-          acc[1][m] = f_mfma<BF16>(af, b1, acc[1][m]);
+          acc[0][m] = eavsr_mfma16<BF16>(af, b0, acc[0][m]);
+          acc[1][m] = eavsr_mfma16<BF16>(af, b1, acc[1][m]);
         }
       }
     }
@@ -198,18 +183,7 @@ __global__ void pack_weight5_h16_kernel(const float* __restrict__ w, unsigned sh
 
 template <bool BF16>
 int launch_conv5_h16(const F16Args& a, int blocks, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5x5_c64_h16_kernel<BF16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv5x5_c64_h16: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv5x5_c64_h16_kernel<BF16>>(F_LDS_BYTES, "conv5x5_c64_h16")) return rc;
   hipLaunchKernelGGL(conv5x5_c64_h16_kernel<BF16>, dim3(blocks), dim3(512), F_LDS_BYTES, st, a);
   return eavsr::launch_status("conv5x5_c64_h16");
 }

@@ -19,19 +19,15 @@
 //   Epilogue: fp32 accumulators (+ bias, ReLU, optional per-tile channel sums in fp32) are rounded to
 //   16 bits and stored from the registers (16 bytes = 8 consecutive channels per lane and store, after the two lanes of a
 //   pixel traded 4-channel runs by v_permlane32_swap).
-#include "common.h"
+#include "mfma.h"
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
 
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int HT_H = 8, HT_W = 32;                 // output tile: one row of 32 pixels per wave, 8 waves
 constexpr int HP_H = HT_H + 2, HP_W = HT_W + 2;    // patch with the 3x3 halo
@@ -97,16 +93,6 @@ template <> __device__ __forceinline__ float from_h16<false>(unsigned short v) {
 // v + (v of the lane the DPP control selects; 0 where there is none) as ONE v_add_f32_dpp (left to the compiler the adds are
 // SLP-packed into v_pk_add_f32 and every DPP move becomes its own instruction)
 #define H16_ADD_DPP(v, ctrl) asm volatile("v_add_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(v) : "v"(v))
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 mfma16(const f32x4& a, const f32x4& b, const f32x16& c) {
-  if (BF16) {
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-  }
-}
 
 
 // Ping-pong schedule (round 2): the workgroup's eight waves are two GROUPS of four (waves 0-3, 4-7 = one wave of each group on
@@ -222,8 +208,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_h16_kernel(H16Args a) {
             for (int m = 0; m < 2; ++m)
 #pragma unroll
               for (int qd = 0; qd < 4; ++qd) {
-                typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-                const u32x2_t xv = *reinterpret_cast<const u32x2_t*>(xrow + (m * 32 + 8 * qd) * 2);
+                const u32x2 xv = *reinterpret_cast<const u32x2*>(xrow + (m * 32 + 8 * qd) * 2);
                 xq[r][m][qd][0] = xv[0];
                 xq[r][m][qd][1] = xv[1];
               }
@@ -349,12 +334,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_h16_kernel(H16Args a) {
                 }
                 const auto s0 = __builtin_amdgcn_permlane32_swap(dw[0][0], dw[1][0], false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(dw[0][1], dw[1][1], false, false);
-                typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-                const u32x4_t v4 = {s0[0], s1[0], s0[1], s1[1]};
+                const u32x4 v4 = {s0[0], s1[0], s0[1], s1[1]};
 #ifdef EAVSR_H16_EXP_NO_STORE
                 if (v4[0] == 0x12344321u && v4[1] == 0x43211234u)
 #endif
-                if (ok) *reinterpret_cast<u32x4_t*>(orow + (m * 32 + 8 * (qe + half)) * 2) = v4;
+                if (ok) *reinterpret_cast<u32x4*>(orow + (m * 32 + 8 * (qe + half)) * 2) = v4;
               }
           }
           H16_STAMP(5);     // bias / activation / rounding / output stores
@@ -524,7 +508,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_h16_kernel(H16Args a) {
 #ifdef EAVSR_H16_EXP_NO_MFMA
 #define H16_MFMA(r_, m_, A_, B_) acc[r_][m_][0] += (A_)[0] + (B_)[1]
 #else
-#define H16_MFMA(r_, m_, A_, B_) acc[r_][m_] = mfma16<BF16>(A_, B_, acc[r_][m_])
+#define H16_MFMA(r_, m_, A_, B_) acc[r_][m_] = eavsr_mfma16<BF16>(A_, B_, acc[r_][m_])
 #endif
 #define H16_SLOT(SET, K, HASNEXT, NKY, NI)                                                                                \
   do {                                                                                                                    \
@@ -609,7 +593,6 @@ __device__ __forceinline__ float dot2_h16(unsigned a, unsigned b, float c) {
 template <bool BF16>
 __global__ __launch_bounds__(256) void conv3x3_c64to3_h16_kernel(L16Args a) {
   __shared__ __attribute__((aligned(16))) unsigned char s_patch[HP_BYTES];      // [row][col][8 x 16-byte blocks], blocks swizzled
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x;
   int t = blockIdx.x;
   const int tx = t % a.tiles_x;
@@ -622,9 +605,9 @@ __global__ __launch_bounds__(256) void conv3x3_c64to3_h16_kernel(L16Args a) {
     const int pp = e >> 3, sb = e & 7;
     const int r = pp / HP_W, c = pp - r * HP_W;
     const int gy = y0 + r, gx = x0 + c;
-    u32x4_t v = {0u, 0u, 0u, 0u};
-    if (gy >= 0 && gy < h && gx >= 0 && gx < w) v = *reinterpret_cast<const u32x4_t*>(xb + ((size_t)gy * w + gx) * 128 + sb * 16);
-    *reinterpret_cast<u32x4_t*>(s_patch + pp * 128 + ((sb ^ ((c >> 1) & 7)) << 4)) = v;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (gy >= 0 && gy < h && gx >= 0 && gx < w) v = *reinterpret_cast<const u32x4*>(xb + ((size_t)gy * w + gx) * 128 + sb * 16);
+    *reinterpret_cast<u32x4*>(s_patch + pp * 128 + ((sb ^ ((c >> 1) & 7)) << 4)) = v;
   }
   __syncthreads();
   const int r = tid >> 5, c = tid & 31;
@@ -639,7 +622,7 @@ __global__ __launch_bounds__(256) void conv3x3_c64to3_h16_kernel(L16Args a) {
       const unsigned* wt = wq + (ky * 3 + kx) * (8 * 3 * 4);
 #pragma unroll
       for (int sb = 0; sb < 8; ++sb) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(px + ((sb ^ swz) << 4));
+        const u32x4 v = *reinterpret_cast<const u32x4*>(px + ((sb ^ swz) << 4));
 #pragma unroll
         for (int co = 0; co < 3; ++co)
 #pragma unroll
@@ -735,19 +718,7 @@ __global__ void pack_weight_h16_kernel(const float* __restrict__ w, unsigned sho
 
 template <bool BF16, bool RESK = false, bool BORD = false>
 int launch_conv_h16(const H16Args& a, int blocks, int slices, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_h16_kernel<BF16, RESK, BORD>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, H_LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv3x3_c64_h16: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv3x3_c64_h16_kernel<BF16, RESK, BORD>>(H_LDS_BYTES, "conv3x3_c64_h16")) return rc;
   hipLaunchKernelGGL((conv3x3_c64_h16_kernel<BF16, RESK, BORD>), dim3(blocks, slices), dim3(512), H_LDS_BYTES, st, a);
   return eavsr::launch_status("conv3x3_c64_h16");
 }

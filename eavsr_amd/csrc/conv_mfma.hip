@@ -22,10 +22,9 @@
 //   optional per-tile channel sums for the channel attention (deterministic, no atomics).
 // LDS reads are conflict-free by construction: the 32 lanes of a half-wave read 32 consecutive floats.
 // The input is the virtual concatenation of up to 5 sources, so torch.cat never materialises.
-#include "common.h"
+#include "mfma.h"
 
 #include <atomic>
-#include <mutex>
 
 namespace {
 
@@ -88,8 +87,6 @@ struct ConvCfg {
   static constexpr size_t LDS_BYTES = (size_t)LDS_FLOATS * sizeof(float);
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <int KS, int MT, bool VEC, bool FUSE, int NT_>
 __global__ __launch_bounds__(512, 2) void conv2d_mfma_kernel(ConvArgs a) {
@@ -569,19 +566,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_small_kernel(ConvArgs a) {
 template <int MT, bool SPLIT = false>
 int launch_small(const ConvArgs& a, dim3 grid, hipStream_t st) {
   using Cfg = SmallCfg<MT>;
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_small_kernel<MT, SPLIT>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv2d: hipFuncSetAttribute(%zu B of LDS): %s", Cfg::LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv3x3_small_kernel<MT, SPLIT>>(Cfg::LDS_BYTES, "conv2d")) return rc;
   if (SPLIT) grid.y *= 2;
   hipLaunchKernelGGL((conv3x3_small_kernel<MT, SPLIT>), grid, dim3(64 * Cfg::NW), Cfg::LDS_BYTES, st, a);
   return eavsr::launch_status("conv2d");
@@ -608,19 +593,7 @@ inline int co_tile_of(int cout) { return cout <= 32 ? 32 : 64; }
 template <int KS, int MT, bool VEC, bool FUSE = false, int NT_ = 4>
 int launch_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
   using Cfg = ConvCfg<KS, MT, VEC, FUSE, NT_>;
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_mfma_kernel<KS, MT, VEC, FUSE, NT_>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv2d: hipFuncSetAttribute(%zu B of LDS): %s", Cfg::LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv2d_mfma_kernel<KS, MT, VEC, FUSE, NT_>>(Cfg::LDS_BYTES, "conv2d")) return rc;
   hipLaunchKernelGGL((conv2d_mfma_kernel<KS, MT, VEC, FUSE, NT_>), grid, dim3(64 * Cfg::NW), Cfg::LDS_BYTES, st, a);
   return eavsr::launch_status("conv2d");
 }

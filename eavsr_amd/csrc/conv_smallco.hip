@@ -10,7 +10,7 @@
 // thread owns 2 vertically adjacent pixels and keeps COUT x 2 accumulators; the slab's weights sit in LDS too
 // and are read back as 16-byte broadcasts, so the inner loop is one ds_read_b32 per input value (4 rows x 3
 // columns shared by the 2 pixels), one or two ds_read_b128 per tap and COUT FMAs per pixel and tap.
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
@@ -200,8 +200,6 @@ __global__ __launch_bounds__(256 * KZ) void conv3x3_smallco_kernel(SmallArgs a) 
 // Same products as conv3x3_smallco_kernel, channels in order; a channel's nine taps are summed column by column (the other kernel
 // goes row by row), so the two agree to rounding, not bit for bit.  Which one runs depends on the image (w % 4, alignment) and
 // on EAVSR_SMALLCO, never on the batch.
-typedef const __attribute__((address_space(1))) void* sl_gptr_t;
-typedef __attribute__((address_space(3))) void* sl_lptr_t;
 __device__ __attribute__((aligned(16))) float g_smallco_zero[4];
 
 constexpr int SL_C = 4;                                            // channels per stage
@@ -255,7 +253,7 @@ __global__ __launch_bounds__((TH / PXR) * TW) void conv3x3_smallco_lite_kernel(S
         const unsigned off = cbase + voff[i];
         const bool ok = voff[i] != 0xFFFFFFFFu && off < total4;      // channels past cin (the last stage of 18 -> 2) read zeros
         const char* src = ok ? xb + off : zero_src;
-        __builtin_amdgcn_global_load_lds((sl_gptr_t)src, (sl_lptr_t)(&s_in[stage][(i * NWV + wave) * 256]), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(&s_in[stage][(i * NWV + wave) * 256]), 16, 0, 0);
       }
     }
   };

@@ -11,9 +11,8 @@
 // that a second kernel adds up in a fixed order (deterministic, no atomics).
 // LDS operands are stored with ODD pitches so that the 32 lanes of a half-wave, which read 32 different
 // channels at the same pixel, hit 32 different banks.
-#include "common.h"
+#include "buffer.h"
 
-#include <mutex>
 #include <stdlib.h>
 #include <string.h>
 
@@ -344,53 +343,10 @@ template <int NP> struct Wx6Cfg {
   static constexpr size_t LDS_BYTES = OPERAND_BYTES > 3 * 4 * 1024 * 4 ? OPERAND_BYTES : 3 * 4 * 1024 * 4;
 };
 
-typedef unsigned wx_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned wx_u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 wx_bf16x8 __attribute__((ext_vector_type(8)));
-
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void wx_split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-typedef __amdgpu_buffer_rsrc_t wx_rsrc;
-constexpr unsigned WX_OOB = 0x80000000u;      // beyond every extent the launcher accepts (< 2^31 bytes per 32-channel image block)
-__device__ __forceinline__ wx_rsrc wx_make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ unsigned wx_smul(unsigned s_, int c) {      // c: a constant once the caller is unrolled
-  unsigned r;
-  asm volatile("s_mul_i32 %0, %1, %2" : "=s"(r) : "s"(s_), "i"(c));
-  return r;
-}
-__device__ __forceinline__ float wx_ld(wx_rsrc r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ f32x4 wx_ld4(wx_rsrc r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
-// two fp32 values rounded to nearest even into one packed bf16 pair (low half = first value): v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned wx_rne2(float a, float b) {
-  typedef float f2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{a, b}, b2_));
-}
-
 // the NP bf16 planes of two fp32 values: NP = 3 the exact split, NP = 1 the rounded value
 template <int NP> __device__ __forceinline__ void wx_planes2(float a, float b, unsigned (&pl)[NP]) {
-  if constexpr (NP == 3) wx_split2(a, b, pl[0], pl[1], pl[2]);
-  else pl[0] = wx_rne2(a, b);
-}
-
-__device__ __forceinline__ f32x16 wx_mfma(const wx_u32x4& a, const wx_u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wx_bf16x8, a), __builtin_bit_cast(wx_bf16x8, b), c, 0, 0, 0);
+  if constexpr (NP == 3) eavsr_split2(a, b, pl[0], pl[1], pl[2]);
+  else pl[0] = eavsr_rne2(a, b);
 }
 
 template <int NP>
@@ -441,23 +397,23 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
     const int bn = t / a.tiles_y;
     const int y0 = ty * TH, x0 = tx * TW;
     const int seg = bn / a.n, bl = bn - seg * a.n;      // wave-uniform
-    const wx_rsrc r_dy = wx_make_rsrc(a.dyv[seg] + ((size_t)bl * a.cout_total + a.co0 + 32 * mt) * plane, (unsigned)co_valid * upl4);
-    const wx_rsrc r_x = wx_make_rsrc(a.xv[seg] + ((size_t)bl * a.cin_src + a.ci0 + 32 * ct) * plane, (unsigned)ci_valid * upl4);
-    const unsigned vq = x0 + 4 * q8 < w ? vo_q : WX_OOB;      // (w % 4 == 0: the whole quad is inside or outside)
+    const eavsr_rsrc r_dy = eavsr_make_rsrc(a.dyv[seg] + ((size_t)bl * a.cout_total + a.co0 + 32 * mt) * plane, (unsigned)co_valid * upl4);
+    const eavsr_rsrc r_x = eavsr_make_rsrc(a.xv[seg] + ((size_t)bl * a.cin_src + a.ci0 + 32 * ct) * plane, (unsigned)ci_valid * upl4);
+    const unsigned vq = x0 + 4 * q8 < w ? vo_q : EAVSR_OOB;      // (w % 4 == 0: the whole quad is inside or outside)
     const unsigned so0 = (unsigned)(y0 * w + x0) * 4u;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      va[i] = y0 + i < h ? wx_ld4(r_dy, vq, so0 + wx_smul(uw4, i)) : f32x4{0.f, 0.f, 0.f, 0.f};
+      va[i] = y0 + i < h ? eavsr_buf_ld4(r_dy, vq, so0 + eavsr_smul(uw4, i)) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       const int gy = y0 - 1 + i;
-      vb[i] = (gy >= 0 && gy < h) ? wx_ld4(r_x, vq, so0 + wx_smul(uw4, i) - uw4) : f32x4{0.f, 0.f, 0.f, 0.f};
+      vb[i] = (gy >= 0 && gy < h) ? eavsr_buf_ld4(r_x, vq, so0 + eavsr_smul(uw4, i) - uw4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // (the scalar offset is not range-checked and must not go negative: the halo's row lives in the per-thread offset)
     const int hy = y0 - 1 + q8;
-    const unsigned vh_ = (q8 < 6 && hy >= 0 && hy < h) ? vo_c + (unsigned)hy * uw4 : WX_OOB;
-    vh[0] = x0 > 0 ? wx_ld(r_x, vh_, (unsigned)x0 * 4u - 4u) : 0.f;
-    vh[1] = x0 + TW < w ? wx_ld(r_x, vh_, (unsigned)x0 * 4u + TW * 4u) : 0.f;
+    const unsigned vh_ = (q8 < 6 && hy >= 0 && hy < h) ? vo_c + (unsigned)hy * uw4 : EAVSR_OOB;
+    vh[0] = x0 > 0 ? eavsr_buf_ld(r_x, vh_, (unsigned)x0 * 4u - 4u) : 0.f;
+    vh[1] = x0 + TW < w ? eavsr_buf_ld(r_x, vh_, (unsigned)x0 * 4u + TW * 4u) : 0.f;
   };
   float bsum = 0.f;      // this thread's share of sum(dY) of channel `chn` (the bias gradient rides along: dY is staged here anyway)
   auto stage = [&]() __attribute__((always_inline)) {
@@ -472,7 +428,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
       wx_planes2<NP>(va[i][2], va[i][3], p1);
       unsigned char* d = lds_a + i * 64;
 #pragma unroll
-      for (int p3 = 0; p3 < NP; ++p3) *reinterpret_cast<wx_u32x2*>(d + p3 * A_PLANE) = wx_u32x2{p0[p3], p1[p3]};
+      for (int p3 = 0; p3 < NP; ++p3) *reinterpret_cast<u32x2*>(d + p3 * A_PLANE) = u32x2{p0[p3], p1[p3]};
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -524,14 +480,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
     // scheduler hoists every read of the tile to the top and spills the accumulators)
     const unsigned char* ap = sA + l31 * A_PITCH + wave * 64 + kg * 16;
     const unsigned char* bp = sB + l31 * B_PITCH + wave * B_ROW + kg * 16;
-    wx_u32x4 av[NP], d03[NP], n03[NP];
-    wx_u32x2 d45[NP], n45[NP];
-    auto read_raw = [&](int g, wx_u32x4 (&r03)[NP], wx_u32x2 (&r45)[NP]) __attribute__((always_inline)) {
+    u32x4 av[NP], d03[NP], n03[NP];
+    u32x2 d45[NP], n45[NP];
+    auto read_raw = [&](int g, u32x4 (&r03)[NP], u32x2 (&r45)[NP]) __attribute__((always_inline)) {
       const int s_ = g / 3, ky = g - 3 * s_;
 #pragma unroll
       for (int p3 = 0; p3 < NP; ++p3) {
-        r03[p3] = *reinterpret_cast<const wx_u32x4*>(bp + p3 * B_PLANE + ky * B_ROW + s_ * 32);
-        r45[p3] = *reinterpret_cast<const wx_u32x2*>(bp + p3 * B_PLANE + ky * B_ROW + s_ * 32 + 16);
+        r03[p3] = *reinterpret_cast<const u32x4*>(bp + p3 * B_PLANE + ky * B_ROW + s_ * 32);
+        r45[p3] = *reinterpret_cast<const u32x2*>(bp + p3 * B_PLANE + ky * B_ROW + s_ * 32 + 16);
       }
     };
 #ifndef EAVSR_WX6_NO_READAHEAD
@@ -542,34 +498,34 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(WgradArgs a) {
       const int s_ = g / 3, ky = g - 3 * s_;
       if (ky == 0) {
 #pragma unroll
-        for (int p3 = 0; p3 < NP; ++p3) av[p3] = *reinterpret_cast<const wx_u32x4*>(ap + p3 * A_PLANE + s_ * 32);
+        for (int p3 = 0; p3 < NP; ++p3) av[p3] = *reinterpret_cast<const u32x4*>(ap + p3 * A_PLANE + s_ * 32);
       }
 #ifdef EAVSR_WX6_NO_READAHEAD      // A/B (with EAVSR_WX6_PREFETCH: 18 registers less)
       read_raw(g, d03, d45);
 #else
       if (g + 1 < 6) read_raw(g + 1, n03, n45);
 #endif
-      wx_u32x4 b0[NP], b1[NP], b2[NP];
+      u32x4 b0[NP], b1[NP], b2[NP];
 #pragma unroll
       for (int p3 = 0; p3 < NP; ++p3) {
         const unsigned s10 = __builtin_amdgcn_alignbyte(d03[p3][1], d03[p3][0], 2), s21 = __builtin_amdgcn_alignbyte(d03[p3][2], d03[p3][1], 2);
         const unsigned s32 = __builtin_amdgcn_alignbyte(d03[p3][3], d03[p3][2], 2), s43 = __builtin_amdgcn_alignbyte(d45[p3][0], d03[p3][3], 2);
         const unsigned s54 = __builtin_amdgcn_alignbyte(d45[p3][1], d45[p3][0], 2);
-        b0[p3] = wx_u32x4{s10, s21, s32, s43};                                  // elements c0 + 1 .. c0 + 8: tap kx = 0
-        b1[p3] = wx_u32x4{d03[p3][1], d03[p3][2], d03[p3][3], d45[p3][0]};      // c0 + 2 .. c0 + 9:  kx = 1
-        b2[p3] = wx_u32x4{s21, s32, s43, s54};                                  // c0 + 3 .. c0 + 10: kx = 2
+        b0[p3] = u32x4{s10, s21, s32, s43};                                  // elements c0 + 1 .. c0 + 8: tap kx = 0
+        b1[p3] = u32x4{d03[p3][1], d03[p3][2], d03[p3][3], d45[p3][0]};      // c0 + 2 .. c0 + 9:  kx = 1
+        b2[p3] = u32x4{s21, s32, s43, s54};                                  // c0 + 3 .. c0 + 10: kx = 2
       }
       // the six partial products, smallest first: (A plane, B plane) = (2,0) (0,2) (1,1) (1,0) (0,1) (0,0); NP = 1: the one product
 #define WX_TAP(T, B)                               \
       if constexpr (NP == 3) {                     \
-        acc[T] = wx_mfma(av[2], B[0], acc[T]);     \
-        acc[T] = wx_mfma(av[0], B[2], acc[T]);     \
-        acc[T] = wx_mfma(av[1], B[1], acc[T]);     \
-        acc[T] = wx_mfma(av[1], B[0], acc[T]);     \
-        acc[T] = wx_mfma(av[0], B[1], acc[T]);     \
-        acc[T] = wx_mfma(av[0], B[0], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[2], B[0], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[0], B[2], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[1], B[1], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[1], B[0], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[0], B[1], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[0], B[0], acc[T]);     \
       } else {                                     \
-        acc[T] = wx_mfma(av[0], B[0], acc[T]);     \
+        acc[T] = eavsr_mfma_bf16(av[0], B[0], acc[T]);     \
       }
 #ifdef EAVSR_WX6_EXP_NO_MFMA      // ablation (tools/gpu_wgrad_diag.py): operands read and shifted, not multiplied
 #pragma unroll
@@ -685,56 +641,20 @@ __global__ __launch_bounds__(512) void wgrad_reduce_kernel(const float* __restri
 template <int KS>
 int launch_wgrad(const WgradArgs& a, int blocks, hipStream_t st, int ci_blocks = 1) {
   using Cfg = WgCfg<KS>;
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<KS>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv_wgrad_kernel<KS>>(Cfg::LDS_BYTES, "conv_wgrad")) return rc;
   hipLaunchKernelGGL(conv_wgrad_kernel<KS>, dim3(blocks, ci_blocks), dim3(512), Cfg::LDS_BYTES, st, a);
   return eavsr::launch_status("conv_wgrad");
 }
 
 int launch_wgrad3(const WgradArgs& a, int blocks, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg3Cfg::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv_wgrad3_kernel>(Wg3Cfg::LDS_BYTES, "conv_wgrad")) return rc;
   hipLaunchKernelGGL(conv_wgrad3_kernel, dim3(blocks, 4), dim3(512), Wg3Cfg::LDS_BYTES, st, a);
   return eavsr::launch_status("conv_wgrad");
 }
 
 template <int NP>
 int launch_wgrad3_x6(const WgradArgs& a, int blocks, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3_x6_kernel<NP>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wx6Cfg<NP>::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv_wgrad3_x6_kernel<NP>>(Wx6Cfg<NP>::LDS_BYTES, "conv_wgrad")) return rc;
   hipLaunchKernelGGL(conv_wgrad3_x6_kernel<NP>, dim3(blocks, 4), dim3(256), Wx6Cfg<NP>::LDS_BYTES, st, a);
   return eavsr::launch_status("conv_wgrad");
 }

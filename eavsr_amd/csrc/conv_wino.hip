@@ -24,15 +24,9 @@
 //           (column ^ 16 (c & 1)) so that the four k-rows a wave reads at once fall on different banks
 //   epilogue in registers: output transform (24 additions per (co, tile)), + bias, activation, + residual, float2
 //   row stores, optional per-tile channel sums (deterministic).
-#include "common.h"
-
-#include <mutex>
+#include "mfma.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __attribute__((aligned(16))) float g_wino_zero[4];   // source of the zero-padding DMA lanes
 
@@ -500,26 +494,15 @@ extern "C" int eavsr_conv3x3_wino_f32(const eavsr_conv2d_desc* d, const float* w
   const long blocks = (long)a.tiles_x * a.tiles_y * d->n;
   EAVSR_REQUIRE(blocks < (1L << 31), -1, "conv3x3_wino: too many tiles");
   EAVSR_REQUIRE((long)d->h * d->w * 16 < (1L << 31), -1, "conv3x3_wino: image plane too large for 32-bit tile offsets");
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-    if (attr_err == hipSuccess)
-      attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv3x3_wino: hipFuncSetAttribute(%zu B of LDS): %s", LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
   // persistent workgroups: one per CU (the kernel needs > 80 KB of LDS), each walking blocks / grid.x tiles
   const long per_cot = blocks < 256 ? blocks : 256;
   dim3 grid((unsigned)per_cot, eavsr::cdiv(d->cout, 64));
-  if (fuse) hipLaunchKernelGGL(conv3x3_wino_kernel<true>, grid, dim3(64 * NW), F_LDS_BYTES, eavsr::as_stream(stream), a);
-  else hipLaunchKernelGGL(conv3x3_wino_kernel<false>, grid, dim3(64 * NW), LDS_BYTES, eavsr::as_stream(stream), a);
+  if (!fuse) {
+    if (int rc = eavsr::raise_lds<&conv3x3_wino_kernel<false>>(LDS_BYTES, "conv3x3_wino")) return rc;
+    hipLaunchKernelGGL(conv3x3_wino_kernel<false>, grid, dim3(64 * NW), LDS_BYTES, eavsr::as_stream(stream), a);
+  } else {
+    if (int rc = eavsr::raise_lds<&conv3x3_wino_kernel<true>>(F_LDS_BYTES, "conv3x3_wino")) return rc;
+    hipLaunchKernelGGL(conv3x3_wino_kernel<true>, grid, dim3(64 * NW), F_LDS_BYTES, eavsr::as_stream(stream), a);
+  }
   return eavsr::launch_status("conv3x3_wino");
 }

@@ -24,7 +24,7 @@
 //           that the operand reads run at the 256 B/clk of ds_read_b64 without bank conflicts
 //   epilogue in registers: output transform, + bias, activation, + residual, float4 row stores (one 256-byte line per
 //   16 lanes), optional per-tile channel sums (deterministic).
-#include "common.h"
+#include "buffer.h"
 
 // -DEAVSR_W4_REG_WEIGHTS: the weight operands straight from global memory into registers (buffer loads, re-requested for the
 // next chunk right after the MFMAs that consumed them) instead of the slab through LDS-DMA + ds_read_b64.  Bit-identical; 5 %
@@ -45,7 +45,6 @@
 #define EAVSR_W4_DUTYPRIO 1
 #endif
 
-#include <mutex>
 #include <type_traits>
 #include <cstdlib>
 #include <cstring>
@@ -62,34 +61,12 @@ static bool w6_grouped_schedule() {
 #endif
 }
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 __device__ __attribute__((aligned(16))) float g_wino4_zero[4];   // source of the zero-padding DMA lanes
 
-// Buffer addressing for the grouped kernel's epilogue (round 6; as csrc/dcnv2_il2.hip since round 5): a 128-bit resource per
-// (image, 64-channel block) of `out` / `residual`, ONE per-lane 32-bit offset register per tile, a scalar offset per (channel,
-// row) computed at the use.  The hardware's range check replaces the exec-mask regions: a lane right of the image holds W6_OOB
-// (its loads return zeros, its stores are dropped), a lane whose channel is >= cout lies beyond the resource's extent.
-typedef __amdgpu_buffer_rsrc_t w6_rsrc;
-constexpr unsigned W6_OOB = 0x80000000u;      // beyond every extent the launcher accepts (64 channels x plane x 4 B < 2^31)
-__device__ __forceinline__ w6_rsrc w6_make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 w6_ld4(w6_rsrc r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-// The store's offset goes through the VECTOR offset (one v_add per store), never through the scalar one.  A 128-bit buffer store
-// reads its data registers over the cycles after it issues, and a vector instruction that rewrites them too early corrupts the
-// store.  The compiler pads that hazard -- except for stores with a REGISTER scalar offset, which older parts exempt; gfx950 does
-// not honour the exemption: with `soffset` in a register the next channel's results landed in the previous channel's rows for the
-// last lanes of each row segment, run-dependent (found by tools/dbg/rsc_diff.py against the round-5 library; one wait state,
-// DESIGN.md 3.2).  With an immediate scalar offset the hazard recogniser does its job.
-__device__ __forceinline__ void w6_st4(w6_rsrc r, unsigned voff, unsigned off, f32x4 v) {
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, voff + off, 0, 0);
-}
+// Buffer addressing for the grouped kernel's epilogue (round 6; buffer.h): a 128-bit resource per (image, 64-channel block) of
+// `out` / `residual` (64 channels x plane x 4 B < 2^31), ONE per-lane 32-bit offset register per tile, a scalar offset per
+// (channel, row) computed at the use.  The hardware's range check replaces the exec-mask regions: a lane right of the image holds
+// EAVSR_OOB (its loads return zeros, its stores are dropped), a lane whose channel is >= cout lies beyond the resource's extent.
 
 struct W4Args {
   const float* src[5];
@@ -573,13 +550,11 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
   // every request has a whole iteration to land.
   // Buffer loads: resource = this launch's packed weights, voffset = the lane's byte offset inside a slab (+ the pair's
   // immediate), soffset = the slab's byte offset in a scalar register -- one instruction per request, no address arithmetic.
-  const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(wu_base), 0, (int)((size_t)(a.cin / CK) * U_ELEMS * sizeof(float)), 0x00020000);
+  const eavsr_rsrc u_rsrc = eavsr_make_rsrc(wu_base, (unsigned)((size_t)(a.cin / CK) * U_ELEMS * sizeof(float)));
   const int lane_uoff = (kq * 128 + 2 * ((cb * 16 + l15) ^ ((kq & 1) << 4))) * 4;
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
   auto load_u = [&](int soff, int i) __attribute__((always_inline)) {
     // the pair's offset goes into the SCALAR offset: a per-pair vector offset costs a register (or an add) per request
-    const u32x2_t t = __builtin_amdgcn_raw_buffer_load_b64(u_rsrc, lane_uoff, soff + i * (CK * 128 * 4), 0);
+    const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(u_rsrc, lane_uoff, soff + i * (CK * 128 * 4), 0);
     return __builtin_bit_cast(f32x2, t);      // (bit-casting t.x / t.y one by one is narrowed to a single dword load by this compiler)
   };
   f32x2 ur[NPOS / 2];
@@ -875,17 +850,17 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
         const int cblk = a.cout - cot * 64 < 64 ? a.cout - cot * 64 : 64;
         const size_t img_off = ((size_t)bn * a.cout + (size_t)cot * 64) * plane;
         const unsigned blk_bytes = (unsigned)((size_t)cblk * plane * sizeof(float));
-        const w6_rsrc r_out = w6_make_rsrc(a.out + img_off, blk_bytes);
+        const eavsr_rsrc r_out = eavsr_make_rsrc(a.out + img_off, blk_bytes);
         const bool has_res = a.residual != nullptr;
-        const w6_rsrc r_res = w6_make_rsrc(has_res ? a.residual + img_off : a.out + img_off, blk_bytes);
-        const unsigned lane_off = gx < w ? (unsigned)((((size_t)(cb * 16 + 4 * kq)) * plane + (size_t)gy0 * w + gx) * sizeof(float)) : W6_OOB;
+        const eavsr_rsrc r_res = eavsr_make_rsrc(has_res ? a.residual + img_off : a.out + img_off, blk_bytes);
+        const unsigned lane_off = gx < w ? (unsigned)((((size_t)(cb * 16 + 4 * kq)) * plane + (size_t)gy0 * w + gx) * sizeof(float)) : EAVSR_OOB;
         const unsigned plane_b = (unsigned)(plane * sizeof(float)), row_b = (unsigned)(w * sizeof(float));
         // F.pixel_shuffle(out, 2) written directly (eavsrp_model.py:343-347): channel co = 4 c' + 2 i + j goes to out'[c'][2 y + i][2 x + j].
         // This lane's four channels are ONE c' = co >> 2 with (i, j) = (rp, ch); its four pixels x .. x + 3 of the pair (ch = 0, 1)
         // become the eight adjacent floats 2 x .. 2 x + 7 of row 2 y + rp: two 16-byte stores.  Same resource (the image's 64-channel
         // block = 16 shuffled planes of 4 h w), another lane offset.
         const bool shuf = a.out_shuffle == 2;
-        const unsigned lane_off_ps = gx < w ? (unsigned)((((size_t)(cb * 4 + kq)) * 4 * plane + (size_t)(2 * gy0) * (2 * w) + 2 * gx) * sizeof(float)) : W6_OOB;
+        const unsigned lane_off_ps = gx < w ? (unsigned)((((size_t)(cb * 4 + kq)) * 4 * plane + (size_t)(2 * gy0) * (2 * w) + 2 * gx) * sizeof(float)) : EAVSR_OOB;
         const bool has_act = a.act != EAVSR_ACT_NONE;
         // The plain instantiation is branch-free in what it computes: a residual that is not there is sixteen zero registers (never
         // loaded), a scale that is not there is 1, the channel sums are always accumulated (and dropped at the end), the
@@ -905,7 +880,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
         auto load_rr = [&](int step) __attribute__((always_inline)) {      // step = 4 rp + dy
 #pragma unroll
           for (int ch = 0; ch < 2; ++ch)
-            rr[step & 1][ch] = w6_ld4(r_res, lane_off, (unsigned)(2 * (step >> 2) + ch) * plane_b + (unsigned)(step & 3) * row_b);
+            rr[step & 1][ch] = eavsr_buf_ld4(r_res, lane_off, (unsigned)(2 * (step >> 2) + ch) * plane_b + (unsigned)(step & 3) * row_b);
         };
         if (has_res) load_rr(0);
         f32x2 cs2[4] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}};
@@ -956,8 +931,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
             if (!RSC && shuf) {      // (no residual, no channel sums: the launcher checks)
               if (dy < rows) {
                 const unsigned so = (unsigned)(2 * dy + rp) * (2 * row_b);
-                w6_st4(r_out, lane_off_ps, so, f32x4{vc[0][0], vc[1][0], vc[0][1], vc[1][1]});
-                w6_st4(r_out, lane_off_ps, so + 16u, f32x4{vc[0][2], vc[1][2], vc[0][3], vc[1][3]});
+                eavsr_buf_st4(r_out, lane_off_ps, so, f32x4{vc[0][0], vc[1][0], vc[0][1], vc[1][1]});
+                eavsr_buf_st4(r_out, lane_off_ps, so + 16u, f32x4{vc[0][2], vc[1][2], vc[0][3], vc[1][3]});
               }
             } else {
 #pragma unroll
@@ -978,7 +953,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino6_kernel(W4Args a) {
                       brgt[r] += v[3];
                     }
                   }
-                  w6_st4(r_out, lane_off, (unsigned)r * plane_b + (unsigned)dy * row_b, o);
+                  eavsr_buf_st4(r_out, lane_off, (unsigned)r * plane_b + (unsigned)dy * row_b, o);
                 }
               }
             }
@@ -1350,53 +1325,31 @@ int launch_wino6(const eavsr_conv2d_desc* d, const float* weight_wino, void* str
   EAVSR_REQUIRE(R != 3 || (long)d->h * d->w * 64 * 4 < (1L << 31), -1,
                 "conv_wino6: image plane too large for the epilogue's 32-bit offsets (64 channels x h x w x 4 bytes must be < 2 GiB)");
   [[maybe_unused]] constexpr size_t LDS_FUSE = C::LDS_BYTES + 2 * C::IN_PAD * sizeof(float);
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino6_kernel<R, false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-#if EAVSR_LAB
-    if (R == 3 && attr_err == hipSuccess)
-      attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino6_kernel<3, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(WCfg<3>::LDS_BYTES + 2 * WCfg<3>::IN_PAD * sizeof(float)));
-#endif
-    if (R == 3 && attr_err == hipSuccess)
-      attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino6_kernel<3, false, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)WCfg<3>::LDS_BYTES);
-    if (R == 3 && attr_err == hipSuccess)
-      attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino6_kernel<3, false, true, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)WCfg<3>::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv_wino6: hipFuncSetAttribute(%zu B of LDS): %s", C::LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
   // persistent workgroups: one per CU, each walking blocks / grid.x tiles
   const long per_cot = blocks < 256 ? blocks : 256;
   dim3 grid((unsigned)per_cot, eavsr::cdiv(d->cout, 64));
   // EAVSR_WINO6_SCHED=lockstep: round 2's schedule (every wave the same program), the A/B reference of the ping-pong kernel
-  if (fuse) {
-#if EAVSR_LAB
-    if constexpr (R == 3)
-      hipLaunchKernelGGL((conv_wino6_kernel<3, true>), grid, dim3(64 * NW), LDS_FUSE, eavsr::as_stream(stream), a);
-#endif
-  } else {
-    // the grouped schedule (transform phases of two chunks, pure GEMM iterations): 3x3, an even number of 4-channel chunks;
-    // EAVSR_W4_GRP=0 keeps the duty-pair schedule (A/B switch)
-    const bool grp_on = w6_grouped_schedule();
-    if constexpr (R == 3) {
-      if (grp_on && (d->cin / CK) % 2 == 0) {
-        if (d->res_scale != nullptr)
-          hipLaunchKernelGGL((conv_wino6_kernel<3, false, true, true>), grid, dim3(64 * NW), C::LDS_BYTES, eavsr::as_stream(stream), a);
-        else
-          hipLaunchKernelGGL((conv_wino6_kernel<3, false, true>), grid, dim3(64 * NW), C::LDS_BYTES, eavsr::as_stream(stream), a);
-        return eavsr::launch_status("conv_wino6");
-      }
-    }
+  // the grouped schedule (transform phases of two chunks, pure GEMM iterations): 3x3, an even number of 4-channel chunks;
+  // EAVSR_W4_GRP=0 keeps the duty-pair schedule (A/B switch)
+  const bool grouped = R == 3 && !fuse && w6_grouped_schedule() && (d->cin / CK) % 2 == 0;
+  if (!fuse && !grouped) {
+    if (int rc = eavsr::raise_lds<&conv_wino6_kernel<R, false>>(C::LDS_BYTES, "conv_wino6")) return rc;
     hipLaunchKernelGGL((conv_wino6_kernel<R, false>), grid, dim3(64 * NW), C::LDS_BYTES, eavsr::as_stream(stream), a);
+  } else if (fuse) {
+#if EAVSR_LAB
+    if constexpr (R == 3) {
+      if (int rc = eavsr::raise_lds<&conv_wino6_kernel<3, true>>(LDS_FUSE, "conv_wino6")) return rc;
+      hipLaunchKernelGGL((conv_wino6_kernel<3, true>), grid, dim3(64 * NW), LDS_FUSE, eavsr::as_stream(stream), a);
+    }
+#endif
+  } else if constexpr (R == 3) {
+    if (d->res_scale == nullptr) {
+      if (int rc = eavsr::raise_lds<&conv_wino6_kernel<3, false, true>>(C::LDS_BYTES, "conv_wino6")) return rc;
+      hipLaunchKernelGGL((conv_wino6_kernel<3, false, true>), grid, dim3(64 * NW), C::LDS_BYTES, eavsr::as_stream(stream), a);
+    } else {
+      if (int rc = eavsr::raise_lds<&conv_wino6_kernel<3, false, true, true>>(C::LDS_BYTES, "conv_wino6")) return rc;
+      hipLaunchKernelGGL((conv_wino6_kernel<3, false, true, true>), grid, dim3(64 * NW), C::LDS_BYTES, eavsr::as_stream(stream), a);
+    }
   }
   return eavsr::launch_status("conv_wino6");
 }

@@ -27,16 +27,9 @@
 //     zero tap: 4 %] into two stages; the slab barrier sits one k-step before the slab changes, so that the next slab's first A
 //     operands are prefetched like any other.
 // The main loop is LDS reads and MFMAs only: 6 + 3 MT reads of 16 bytes per 12 MT MFMAs and wave, operands read one k-step ahead.
-#include "common.h"
-
-#include <mutex>
+#include "mfma.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int S_NW = 8, S_TW = 32;
 // KS: kernel size (7, 5); MT: 32-channel output tiles per workgroup; NT: image rows per wave (tile = 8 NT rows x 32 pixels).
@@ -73,30 +66,10 @@ struct C7Args {
   int sig_from;      // output channels >= sig_from (a multiple of 8; -1: none) get the sigmoid instead of `act`
 };
 
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void s_split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-__device__ __forceinline__ f32x16 s_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef _Float16 s_h16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x16 s_mfma_f16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(s_h16x8, a), __builtin_bit_cast(s_h16x8, b), c, 0, 0, 0);
-}
 // two fp32 values rounded (nearest even) to one packed 16-bit pair: DT 1 = fp16, 2 = bf16
 template <int DT> __device__ __forceinline__ unsigned s_round2(float a, float b) {
   if (DT == 1) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)a) | ((unsigned)__builtin_bit_cast(unsigned short, (_Float16)b) << 16);
-  typedef float f2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{a, b}, b2_));
+  return eavsr_rne2(a, b);
 }
 
 #ifdef EAVSR_C7_STAMPS
@@ -196,7 +169,7 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
       for (int c = 0; c < 4; ++c) {
         if constexpr (NP == 3) {
           unsigned h2, m2, l2;
-          s_split2(pv[i][2 * c], pv[i][2 * c + 1], h2, m2, l2);
+          eavsr_split2(pv[i][2 * c], pv[i][2 * c + 1], h2, m2, l2);
           pl[0][c] = h2; pl[1][c] = m2; pl[2][c] = l2;
         } else {
           pl[0][c] = s_round2<DT>(pv[i][2 * c], pv[i][2 * c + 1]);
@@ -329,16 +302,16 @@ __global__ __launch_bounds__(512) void conv_x6_kernel(C7Args a) {
         for (int m = 0; m < MT; ++m) {
           f32x16 c_ = acc[m][t];
           if constexpr (NP == 3) {
-            c_ = s_mfma(acur[2][m], bcur[t][0], c_);
-            c_ = s_mfma(acur[0][m], bcur[t][2], c_);
-            c_ = s_mfma(acur[1][m], bcur[t][1], c_);
-            c_ = s_mfma(acur[1][m], bcur[t][0], c_);
-            c_ = s_mfma(acur[0][m], bcur[t][1], c_);
-            c_ = s_mfma(acur[0][m], bcur[t][0], c_);
+            c_ = eavsr_mfma_bf16(acur[2][m], bcur[t][0], c_);
+            c_ = eavsr_mfma_bf16(acur[0][m], bcur[t][2], c_);
+            c_ = eavsr_mfma_bf16(acur[1][m], bcur[t][1], c_);
+            c_ = eavsr_mfma_bf16(acur[1][m], bcur[t][0], c_);
+            c_ = eavsr_mfma_bf16(acur[0][m], bcur[t][1], c_);
+            c_ = eavsr_mfma_bf16(acur[0][m], bcur[t][0], c_);
           } else if constexpr (DT == 1) {
-            c_ = s_mfma_f16(acur[0][m], bcur[t][0], c_);
+            c_ = eavsr_mfma_f16(acur[0][m], bcur[t][0], c_);
           } else {
-            c_ = s_mfma(acur[0][m], bcur[t][0], c_);
+            c_ = eavsr_mfma_bf16(acur[0][m], bcur[t][0], c_);
           }
           acc[m][t] = c_;
         }
@@ -441,7 +414,7 @@ __global__ void pack7_kernel(const float* __restrict__ wt, u32x4* __restrict__ p
     }
     if (np == 3) {
       unsigned h2, m2, l2;
-      s_split2(v[0], v[1], h2, m2, l2);
+      eavsr_split2(v[0], v[1], h2, m2, l2);
       o[c] = pl == 0 ? h2 : pl == 1 ? m2 : l2;
     } else {
       o[c] = dt == 1 ? s_round2<1>(v[0], v[1]) : s_round2<2>(v[0], v[1]);
@@ -490,7 +463,7 @@ __global__ void pack7_multi_kernel(PackMultiArgs a, int cout, int cin, int kk, i
     }
     if constexpr (NP == 3) {
       unsigned h2, m2, l2;
-      s_split2(v[0], v[1], h2, m2, l2);
+      eavsr_split2(v[0], v[1], h2, m2, l2);
       o[c] = pl == 0 ? h2 : pl == 1 ? m2 : l2;
     } else {
       o[c] = s_round2<2>(v[0], v[1]);
@@ -501,24 +474,12 @@ __global__ void pack7_multi_kernel(PackMultiArgs a, int cout, int cin, int kk, i
 
 int mt_of(int cout) { return cout > 32 ? 2 : 1; }
 
-// compute units of the current device (0: unknown -- nobody walks tiles then)
-int cu_count() {
-  static int cus_pd[eavsr::kMaxDevices] = {};
-  static eavsr::PerDeviceOnce once_pd;
-  const int dev_ = eavsr::current_device();
-  std::call_once(once_pd.flag[dev_], [&] {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess && v > 0) cus_pd[dev_] = v;
-  });
-  return cus_pd[dev_];
-}
-
 // The persistent form's grid: a workgroup owns a CU's LDS, so `slots` = CUs / output-channel tiles workgroups per channel tile are
 // resident at once; `tiles` of them take rounds = ceil(tiles / slots) whoever hands them out.  The grid is the FEWEST workgroups
 // that still finish in `rounds` tiles each (every one walks rounds or rounds - 1 tiles).  0: one tile per workgroup, as launched
-// before -- a launch of one round, an odd number of chunks, a device that does not say how many CUs it has.
+// before -- a launch of one round, an odd number of chunks.
 int persist_grid(long tiles, int cot_n, int cin) {
-  const int slots = cu_count() / cot_n;
+  const int slots = eavsr::cu_count() / cot_n;
   if (slots < 1 || tiles <= slots || (cin >> 3) % 2) return 0;
   const long rounds = (tiles + slots - 1) / slots;
   return (int)((tiles + rounds - 1) / rounds);
@@ -528,18 +489,7 @@ template <int KS, int MT, int NT, int WMT, int NP = 3, int DT = 0, bool PERSIST 
 int launch7(const C7Args& a, void* stream, int grid_x = 0) {
   using K = C7<KS, MT, NT, NP>;
   static_assert(!PERSIST || K::NSLAB % 2 == 0, "the slab ring must come round to stage 0 at a tile's start");
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x6_kernel<KS, MT, NT, WMT, NP, DT, PERSIST>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv_f32x6: hipFuncSetAttribute(%zu B of LDS): %s", K::LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv_x6_kernel<KS, MT, NT, WMT, NP, DT, PERSIST>>(K::LDS_BYTES, "conv_f32x6")) return rc;
   C7Args b = a;
   b.tiles_y = eavsr::cdiv(a.h, K::TH);
   const long blocks = (long)b.tiles_x * b.tiles_y * b.n;

@@ -17,16 +17,11 @@
 // reads the 8 channels of pixel n shifted by ITS tap (2s + g), splits them in registers (44 vector instructions per
 // 18 MFMAs, hidden in their shadows: the bf16 MFMA holds the vector issue for 8 of its 32 cycles) and multiplies.
 // Tap 9 does not exist: its weights are zero (10 % of the MFMAs are padding).
-#include "common.h"
+#include "mfma.h"
 
-#include <mutex>
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct CxArgs {
   const float* src[5];
@@ -55,21 +50,6 @@ constexpr int W_IT = (W_SEGS + NW - 1) / NW;
 constexpr int BUF = IN_PAD + W_U4 * 4;                   // floats per pipeline stage
 constexpr int LDS_FLOATS = 2 * BUF + NW * 64;
 constexpr size_t LDS_BYTES = (size_t)LDS_FLOATS * sizeof(float);
-
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 __global__ __launch_bounds__(512, 2) void conv3x3_x9_kernel(CxArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -184,7 +164,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x9_kernel(CxArgs a) {
 #pragma unroll
       for (int c = 0; c < CK / 2; ++c) {
         unsigned h2, m2, l2;
-        split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
+        eavsr_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
         bo[0][c] = h2; bo[1][c] = m2; bo[2][c] = l2;
       }
     };
@@ -223,15 +203,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x9_kernel(CxArgs a) {
         for (int mt = 0; mt < 2; ++mt) {
           f32x16 c_ = acc[mt][t];
           // the nine partial products, smallest terms first
-          c_ = mfma_bf16(wa[2][mt], bcur[2], c_);
-          c_ = mfma_bf16(wa[2][mt], bcur[1], c_);
-          c_ = mfma_bf16(wa[1][mt], bcur[2], c_);
-          c_ = mfma_bf16(wa[2][mt], bcur[0], c_);
-          c_ = mfma_bf16(wa[0][mt], bcur[2], c_);
-          c_ = mfma_bf16(wa[1][mt], bcur[1], c_);
-          c_ = mfma_bf16(wa[1][mt], bcur[0], c_);
-          c_ = mfma_bf16(wa[0][mt], bcur[1], c_);
-          c_ = mfma_bf16(wa[0][mt], bcur[0], c_);
+          c_ = eavsr_mfma_bf16(wa[2][mt], bcur[2], c_);
+          c_ = eavsr_mfma_bf16(wa[2][mt], bcur[1], c_);
+          c_ = eavsr_mfma_bf16(wa[1][mt], bcur[2], c_);
+          c_ = eavsr_mfma_bf16(wa[2][mt], bcur[0], c_);
+          c_ = eavsr_mfma_bf16(wa[0][mt], bcur[2], c_);
+          c_ = eavsr_mfma_bf16(wa[1][mt], bcur[1], c_);
+          c_ = eavsr_mfma_bf16(wa[1][mt], bcur[0], c_);
+          c_ = eavsr_mfma_bf16(wa[0][mt], bcur[1], c_);
+          c_ = eavsr_mfma_bf16(wa[0][mt], bcur[0], c_);
           acc[mt][t] = c_;
         }
         // placement: the far reads first, then every MFMA followed by 3 of the split's vector instructions
@@ -348,19 +328,7 @@ extern "C" int eavsr_conv3x3_f32x9(const eavsr_conv2d_desc* d, const void* weigh
   const long blocks = (long)a.tiles_x * a.tiles_y * d->n;
   EAVSR_REQUIRE(blocks < (1L << 31), -1, "conv3x3_f32x9: too many tiles");
   EAVSR_REQUIRE((long)d->h * d->w * 16 < (1L << 31), -1, "conv3x3_f32x9: image plane too large for 32-bit tile offsets");
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_x9_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("conv3x3_f32x9: hipFuncSetAttribute(%zu B of LDS): %s", LDS_BYTES, hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&conv3x3_x9_kernel>(LDS_BYTES, "conv3x3_f32x9")) return rc;
   dim3 grid((unsigned)blocks, eavsr::cdiv(d->cout, 64));
   hipLaunchKernelGGL(conv3x3_x9_kernel, grid, dim3(64 * NW), LDS_BYTES, eavsr::as_stream(stream), a);
   return eavsr::launch_status("conv3x3_f32x9");

@@ -24,11 +24,10 @@
 //      written as one partial slab per (workgroup, group); dcn_bwd_dw_reduce adds the slabs in a fixed order (no atomics).
 //
 // Specialised to the model's configuration (64 -> 64 channels, 8 deformable groups of 8 channels, 3 x 3, stride / pad / dilation 1).
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int B_C = 64, B_CO = 64, B_DG = 8;
 constexpr int B_TH = 4, B_TW = 16;              // tile: one 16-pixel row per wave, 4 waves

@@ -16,7 +16,7 @@
 // HBM traffic per pixel (fp32, cin = cout = 64, dg = 8): 64 + 144 + 72 + 64 floats = 1376 B; the input
 // patch is re-read through L1/L2 by the 9 taps (data-dependent gathers, neighbouring lanes hit the
 // same lines).  The per-(pixel, tap) corner indices / weights are computed once per 4-channel chunk.
-#include "common.h"
+#include "buffer.h"
 
 #include <stdlib.h>
 
@@ -31,15 +31,6 @@ struct DcnArgs {
   float* out;
   int n, cin, h, w, cout, dg, cpg, cin_pad, tiles_x, tiles_y;
 };
-
-// load through a wave-uniform base + 32-bit BYTE offset: lowers to `global_load_dword v, v_off, s[base]`
-// (an element index would have to be shifted in 64 bits, which forces per-lane 64-bit addresses)
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ float ld_b(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 constexpr int DT_H = 4, DT_W = 32, DT_PX = DT_H * DT_W;  // 128 pixels per workgroup, one row per wave
 constexpr int DCK = 4;                                   // channels per chunk (half a deformable group at cpg = 8)
@@ -97,9 +88,9 @@ __global__ __launch_bounds__(256, 4) void dcnv2_kernel(DcnArgs a) {
 #pragma unroll
     for (int j = 0; j < TAPS_PER_THREAD; ++j) {
       const unsigned tap = (unsigned)min(tap0 + 2 * j, DKK - 1);
-      oy[j] = ld_b(offb, (2u * tap * uplane + pix) * 4u);
-      ox[j] = ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
-      mk[j] = ld_b(mkb, (tap * uplane + pix) * 4u);
+      oy[j] = eavsr_ld_b(offb, (2u * tap * uplane + pix) * 4u);
+      ox[j] = eavsr_ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
+      mk[j] = eavsr_ld_b(mkb, (tap * uplane + pix) * 4u);
     }
     const float* xp = a.x + ((size_t)bn * a.cin + c0) * plane;
     __syncthreads();  // the previous chunk's contraction is done with s_col / s_w
@@ -141,10 +132,10 @@ __global__ __launch_bounds__(256, 4) void dcnv2_kernel(DcnArgs a) {
 #pragma unroll
       for (int c = 0; c < DCK; ++c) {
         const float* q = xp + (size_t)c * plane;  // uniform
-        float v = w1 * ld_b(q, i1);
-        v += w2 * ld_b(q, i2);
-        v += w3 * ld_b(q, i3);
-        v += w4 * ld_b(q, i4);
+        float v = w1 * eavsr_ld_b(q, i1);
+        v += w2 * eavsr_ld_b(q, i2);
+        v += w3 * eavsr_ld_b(q, i3);
+        v += w4 * eavsr_ld_b(q, i4);
         vals[c] = v * mk[j];
       }
       if (tap < DKK) {
@@ -224,7 +215,6 @@ constexpr int PATCH_IT = PATCH_SEGS / 4;  // pieces per wave
 //   * column tile, weight slab and window are three distinct LDS objects, so the compiler may move gathers
 //     across column stores; 52 KB LDS and <= 168 VGPRs keep three workgroups per CU
 // ---------------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifdef EAVSR_DCN_STAMPS
 // diagnostic build only (tools/build_dcn_diag.sh): cycles of wave 0 / wave 2 of every workgroup per phase
 __device__ unsigned long long g_dcn_stamps[16];
@@ -330,9 +320,9 @@ __global__ __launch_bounds__(256, 3) void dcnv2_grp_kernel(DcnArgs a) {
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
       const unsigned tap = (unsigned)(tap0 + 2 * j);
-      fy[j] = ld_b(offb, (2u * tap * uplane + pix) * 4u);
-      fx[j] = ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
-      fm[j] = ld_b(mkb, (tap * uplane + pix) * 4u);
+      fy[j] = eavsr_ld_b(offb, (2u * tap * uplane + pix) * 4u);
+      fx[j] = eavsr_ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
+      fm[j] = eavsr_ld_b(mkb, (tap * uplane + pix) * 4u);
     }
   };
   // per-slot sampling state of the current deformable group (positions are shared by its 8 channels)
@@ -383,9 +373,9 @@ __global__ __launch_bounds__(256, 3) void dcnv2_grp_kernel(DcnArgs a) {
         const int tap = tap0 + 2 * j;
         const int ti = tap / 3, tj = tap - 3 * ti;
         // rare path: the offsets are read again (the prefetch registers already hold the next group's)
-        const float fy = ld_b(offb, (2u * (unsigned)tap * uplane + pix) * 4u);
-        const float fx = ld_b(offb, ((2u * (unsigned)tap + 1u) * uplane + pix) * 4u);
-        const float fm = ld_b(mkb, ((unsigned)tap * uplane + pix) * 4u);
+        const float fy = eavsr_ld_b(offb, (2u * (unsigned)tap * uplane + pix) * 4u);
+        const float fx = eavsr_ld_b(offb, ((2u * (unsigned)tap + 1u) * uplane + pix) * 4u);
+        const float fm = eavsr_ld_b(mkb, ((unsigned)tap * uplane + pix) * 4u);
         const float py = eavsr_sample_pos((float)(gy - 1 + ti) + fy, h);
         const float px = eavsr_sample_pos((float)(gx - 1 + tj) + fx, w);
         const float fy0 = floorf(py), fx0 = floorf(px);
@@ -405,10 +395,10 @@ __global__ __launch_bounds__(256, 3) void dcnv2_grp_kernel(DcnArgs a) {
 #pragma unroll
         for (int c = 0; c < DCK; ++c) {
           const float* q = xp + (size_t)c * plane;
-          float v = w1 * ld_b(q, i1);
-          v += w2 * ld_b(q, i2);
-          v += w3 * ld_b(q, i3);
-          v += w4 * ld_b(q, i4);
+          float v = w1 * eavsr_ld_b(q, i1);
+          v += w2 * eavsr_ld_b(q, i2);
+          v += w3 * eavsr_ld_b(q, i3);
+          v += w4 * eavsr_ld_b(q, i4);
           s_col[(c * DKK + tap) * DT_PX + p] = v * fm;
         }
       }

@@ -24,20 +24,11 @@
 // MFMA mapping (v_mfma_f32_32x32x16_bf16): M = 32 output channels (2 tiles), N = 32 pixels of one image row,
 // k-step = 16 k = 2 taps x 8 channels of one group; lane (n = lane & 31, kg = lane >> 5) samples pixel n for tap
 // 2 s + kg of k-step s and feeds its 8 blended, split values straight from registers (no column tile in LDS).
-#include "common.h"
+#include "buffer.h"
 
-#include <mutex>
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float ld_b(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 constexpr int IT_ROWS = 8, IT_W = 32;                 // pixel tile: one 32-pixel row per wave
 constexpr int IG = 8;                                 // channels per group = k of one tap
@@ -61,21 +52,6 @@ struct ILArgs {
   float* out;            // (n, cout, h, w)
   int n, cin, h, w, cout, dg, cpg, opg_shift, tiles_x, tiles_y, ntiles;   // opg_shift: log2(octets per deformable group)
 };
-
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void il_split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-__device__ __forceinline__ f32x16 il_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 #ifdef EAVSR_IL_STAMPS
 // diagnostic build only (tools/build_il_diag.sh): shader cycles per phase, summed over wave 0 and wave 4 of every workgroup
@@ -226,10 +202,10 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
     (void)pb_; (void)o; (void)lastslot;
     return;
 #endif
-    pm[s] = ld_b(reinterpret_cast<const float*>(pb_.msk + (size_t)(2 * s) * pl4), lastslot ? o.p4 : o.pm);
+    pm[s] = eavsr_ld_b(reinterpret_cast<const float*>(pb_.msk + (size_t)(2 * s) * pl4), lastslot ? o.p4 : o.pm);
     if (!HEADS) {
-      pa[s] = ld_b(reinterpret_cast<const float*>(pb_.off + (size_t)(4 * s) * pl4), lastslot ? o.p4 : o.po);
-      pb[s] = ld_b(reinterpret_cast<const float*>(pb_.off + (size_t)(4 * s + 1) * pl4), lastslot ? o.p4 : o.po);
+      pa[s] = eavsr_ld_b(reinterpret_cast<const float*>(pb_.off + (size_t)(4 * s) * pl4), lastslot ? o.p4 : o.po);
+      pb[s] = eavsr_ld_b(reinterpret_cast<const float*>(pb_.off + (size_t)(4 * s + 1) * pl4), lastslot ? o.p4 : o.po);
     }
   };
   auto load_affine = [&](const PBase& pb_, const POff& o) __attribute__((always_inline)) {
@@ -240,9 +216,9 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
 #endif
     if (HEADS) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) tf[j] = ld_b(reinterpret_cast<const float*>(pb_.aff + (size_t)j * pl4), o.p4);
+      for (int j = 0; j < 4; ++j) tf[j] = eavsr_ld_b(reinterpret_cast<const float*>(pb_.aff + (size_t)j * pl4), o.p4);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) tf[4 + j] = ld_b(reinterpret_cast<const float*>(pb_.trn + (size_t)j * pl4), o.p4);
+      for (int j = 0; j < 2; ++j) tf[4 + j] = eavsr_ld_b(reinterpret_cast<const float*>(pb_.trn + (size_t)j * pl4), o.p4);
     }
   };
 
@@ -452,7 +428,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
 #ifdef EAVSR_IL_EXP_NO_SPLIT
       h2 = __float_as_uint(v[0]); m2 = __float_as_uint(v[1]); l2 = h2 ^ m2;
 #else
-      il_split2(v[0], v[1], h2, m2, l2);
+      eavsr_split2(v[0], v[1], h2, m2, l2);
 #endif
       bop[t & 1][0][c] = h2; bop[t & 1][1][c] = m2; bop[t & 1][2][c] = l2;
     };
@@ -465,7 +441,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
       constexpr int TA6[6] = {2, 0, 1, 1, 0, 0}, TB6[6] = {0, 2, 1, 0, 1, 0};
       const int mt = i / NPROD, j = i % NPROD;
       const int ta = NPROD == 9 ? TA9[j] : TA6[j], tb = NPROD == 9 ? TB9[j] : TB6[j];
-      ac[mt] = il_mfma(av[ta * 2 + mt], b[tb], ac[mt]);
+      ac[mt] = eavsr_mfma_bf16(av[ta * 2 + mt], b[tb], ac[mt]);
 #endif
     };
     constexpr int NM = 2 * NPROD, CH = NM / 6;      // MFMAs per k-step; per chunk (2 for x6, 3 for x9)
@@ -549,18 +525,18 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
             const float* hb = a.offset + (size_t)bn * 15 * a.dg * plane;
             float tt[6];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) tt[j] = ld_b(hb, ((unsigned)(dgi * 4 + j) * uplane + pix) * 4u);
+            for (int j = 0; j < 4; ++j) tt[j] = eavsr_ld_b(hb, ((unsigned)(dgi * 4 + j) * uplane + pix) * 4u);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) tt[4 + j] = ld_b(hb, ((unsigned)(4 * a.dg + dgi * 2 + j) * uplane + pix) * 4u);
+            for (int j = 0; j < 2; ++j) tt[4 + j] = eavsr_ld_b(hb, ((unsigned)(4 * a.dg + dgi * 2 + j) * uplane + pix) * 4u);
             dy = (tt[0] * ryt + tt[1] * rxt) - ryt + tt[4];
             dx = (tt[2] * ryt + tt[3] * rxt) - rxt + tt[5];
-            m = 1.f / (1.f + __expf(-ld_b(hb, ((unsigned)(6 * a.dg + dgi * 9) * uplane + (unsigned)tap * uplane + pix) * 4u)));
+            m = 1.f / (1.f + __expf(-eavsr_ld_b(hb, ((unsigned)(6 * a.dg + dgi * 9) * uplane + (unsigned)tap * uplane + pix) * 4u)));
           } else {
             const float* offb = a.offset + ((size_t)bn * a.dg + dgi) * 18 * plane;
             const float* mkb = a.mask + ((size_t)bn * a.dg + dgi) * 9 * plane;
-            dy = ld_b(offb, (2u * (unsigned)tap * uplane + pix) * 4u);
-            dx = ld_b(offb, ((2u * (unsigned)tap + 1u) * uplane + pix) * 4u);
-            m = ld_b(mkb, ((unsigned)tap * uplane + pix) * 4u);
+            dy = eavsr_ld_b(offb, (2u * (unsigned)tap * uplane + pix) * 4u);
+            dx = eavsr_ld_b(offb, ((2u * (unsigned)tap + 1u) * uplane + pix) * 4u);
+            m = eavsr_ld_b(mkb, ((unsigned)tap * uplane + pix) * 4u);
           }
           const float py = eavsr_sample_pos((fgy + ryt) + dy, h);
           const float px = eavsr_sample_pos((fgx + rxt) + dx, w);
@@ -590,7 +566,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il_kernel(ILArgs a) {
 #pragma unroll
         for (int c = 0; c < IG / 2; ++c) {
           unsigned h2, m2, l2;
-          il_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
+          eavsr_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
           b[0][c] = h2; b[1][c] = m2; b[2][c] = l2;
         }
         const u32x4* ws = wst + t * (3 * 2 * 64);
@@ -642,19 +618,7 @@ __global__ __launch_bounds__(256) void nchw_to_il8_kernel(const float* __restric
 
 template <int NPROD, bool HEADS>
 int launch_il(const ILArgs& a, dim3 grid, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&dcnv2_il_kernel<NPROD, HEADS>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)ILDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("dcnv2_il: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&dcnv2_il_kernel<NPROD, HEADS>>(ILDS_BYTES, "dcnv2_il")) return rc;
   hipLaunchKernelGGL((dcnv2_il_kernel<NPROD, HEADS>), grid, dim3(512), ILDS_BYTES, st, a);
   return eavsr::launch_status("dcnv2_il");
 }
@@ -712,17 +676,7 @@ extern "C" int eavsr_dcnv2_il_f32(const float* x_il8, const float* offset_or_hea
   const long tiles = (long)a.tiles_x * a.tiles_y * n;
   EAVSR_REQUIRE(tiles < (1L << 31), -1, "dcnv2_il: too many tiles");
   a.ntiles = (int)tiles;
-  int cus = 256;
-  {
-    static int cu_cache[eavsr::kMaxDevices] = {};
-    const int dev = eavsr::current_device();
-    if (cu_cache[dev] == 0) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cu_cache[dev] = v;
-      else cu_cache[dev] = 256;
-    }
-    cus = cu_cache[dev];
-  }
+  const int cus = eavsr::cu_count();
   dim3 grid((unsigned)(tiles < cus ? tiles : cus), eavsr::cdiv(cout, 64));
   hipStream_t st = eavsr::as_stream(stream);
   if (nprod == 9) return heads ? launch_il<9, true>(a, grid, st) : launch_il<9, false>(a, grid, st);

@@ -12,25 +12,15 @@
 //     the 12 / 18 of the fp32-faithful kernel, and no operand split -- the kernel is bound by the sampler's vector work,
 //     not by the matrix pipe
 //   * output fp32 NCHW (the 1x1 fusion conv that follows takes fp32 sources), bias added in fp32.
-#include "common.h"
-
-#include <mutex>
+#include "buffer.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // parameter load as (wave-uniform base in a scalar register pair) + (32-bit lane offset): `global_load_dword v, v_off, s[base]` -- left
 // alone the compiler forms a 64-bit vector address per load with a quarter-rate v_mad_u64_u32 (20 per (tile, group) step); the base
-// goes through an empty asm as an integer (csrc/dcnv2_il2.hip's ld_b)
+// goes through an empty asm as an integer, which buffer.h's eavsr_ld_b does not do (that one serves the per-lane bases of the rare
+// fix-up path here)
 typedef const __attribute__((address_space(1))) char* h_gcp;
-__device__ __forceinline__ float ld_b16v(const float* base, unsigned byte_off) {      // per-lane base (the rare fix-up path)
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 __device__ __forceinline__ float ld_b16(const float* base, unsigned byte_off) {
   unsigned long long b = reinterpret_cast<unsigned long long>(base);
   asm volatile("" : "+s"(b));
@@ -82,12 +72,6 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, h2));
   }
-}
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 mfma_h(const u32x4& a, const u32x4& b, const f32x16& c) {
-  if (BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
 }
 
 template <bool BF16, bool HEADS>
@@ -305,8 +289,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
     for (int t = 0; t < HSTEPS; ++t) {
       if (t + 1 < HSTEPS) setup_gather(t + 1);
       const u32x4 a0 = wst[(t * 2 + 0) * 64], a1 = wst[(t * 2 + 1) * 64];
-      acc[0] = mfma_h<BF16>(a0, bcur, acc[0]);
-      acc[1] = mfma_h<BF16>(a1, bcur, acc[1]);
+      acc[0] = eavsr_mfma16<BF16>(a0, bcur, acc[0]);
+      acc[1] = eavsr_mfma16<BF16>(a1, bcur, acc[1]);
       if (t + 1 < HSTEPS) {
         blend(bnext);
         bcur = bnext;
@@ -330,18 +314,18 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
             const char* hb = reinterpret_cast<const char*>(a.offset) + (size_t)bn * 15 * a.dg * pl4;
             float tt[6];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) tt[j] = ld_b16v(reinterpret_cast<const float*>(hb + (size_t)(dgi * 4 + j) * pl4), pix * 4u);
+            for (int j = 0; j < 4; ++j) tt[j] = eavsr_ld_b(reinterpret_cast<const float*>(hb + (size_t)(dgi * 4 + j) * pl4), pix * 4u);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) tt[4 + j] = ld_b16v(reinterpret_cast<const float*>(hb + (size_t)(4 * a.dg + dgi * 2 + j) * pl4), pix * 4u);
+            for (int j = 0; j < 2; ++j) tt[4 + j] = eavsr_ld_b(reinterpret_cast<const float*>(hb + (size_t)(4 * a.dg + dgi * 2 + j) * pl4), pix * 4u);
             dy = (tt[0] * ryt + tt[1] * rxt) - ryt + tt[4];
             dx = (tt[2] * ryt + tt[3] * rxt) - rxt + tt[5];
-            m = eavsr_sigmoid_fast(ld_b16v(reinterpret_cast<const float*>(hb + (size_t)(6 * a.dg + dgi * 9 + tap) * pl4), pix * 4u));
+            m = eavsr_sigmoid_fast(eavsr_ld_b(reinterpret_cast<const float*>(hb + (size_t)(6 * a.dg + dgi * 9 + tap) * pl4), pix * 4u));
           } else {
             const char* ob = reinterpret_cast<const char*>(a.offset) + ((size_t)bn * a.dg + dgi) * 18 * pl4;
             const char* mb = reinterpret_cast<const char*>(a.mask) + ((size_t)bn * a.dg + dgi) * 9 * pl4;
-            dy = ld_b16v(reinterpret_cast<const float*>(ob + (size_t)(2 * tap) * pl4), pix * 4u);
-            dx = ld_b16v(reinterpret_cast<const float*>(ob + (size_t)(2 * tap + 1) * pl4), pix * 4u);
-            m = ld_b16v(reinterpret_cast<const float*>(mb + (size_t)tap * pl4), pix * 4u);
+            dy = eavsr_ld_b(reinterpret_cast<const float*>(ob + (size_t)(2 * tap) * pl4), pix * 4u);
+            dx = eavsr_ld_b(reinterpret_cast<const float*>(ob + (size_t)(2 * tap + 1) * pl4), pix * 4u);
+            m = eavsr_ld_b(reinterpret_cast<const float*>(mb + (size_t)tap * pl4), pix * 4u);
           }
           const float py = eavsr_sample_pos((fgy + ryt) + dy, h), px = eavsr_sample_pos((fgx + rxt) + dx, w);
           if (!(py > -1.f && px > -1.f && py < (float)h && px < (float)w)) m = 0.f;
@@ -372,8 +356,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il16_kernel(IL16Args a) {
           for (int c = 0; c < 4; ++c) b[c] = pack2<BF16>(v[2 * c], v[2 * c + 1]);
         }
         const u32x4 a0 = wst[(t * 2 + 0) * 64], a1 = wst[(t * 2 + 1) * 64];
-        acc[0] = mfma_h<BF16>(a0, b, acc[0]);
-        acc[1] = mfma_h<BF16>(a1, b, acc[1]);
+        acc[0] = eavsr_mfma16<BF16>(a0, b, acc[0]);
+        acc[1] = eavsr_mfma16<BF16>(a1, b, acc[1]);
       }
     }
 
@@ -503,17 +487,7 @@ extern "C" int eavsr_dcnv2_il16(const void* x_il8_h16, const float* offset_or_he
   const long tiles = (long)a.tiles_x * a.tiles_y * n;
   EAVSR_REQUIRE(tiles < (1L << 31), -1, "dcnv2_il16: too many tiles");
   a.ntiles = (int)tiles;
-  int cus = 256;
-  {
-    static int cu_cache[eavsr::kMaxDevices] = {};
-    const int dev = eavsr::current_device();
-    if (cu_cache[dev] == 0) {
-      int v = 0;
-      cu_cache[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    cus = cu_cache[dev];
-  }
-  const long slots = cus;           // one persistent workgroup per CU (at 128 registers for two per CU the kernel spills)
+  const long slots = eavsr::cu_count();        // one persistent workgroup per CU (at 128 registers for two per CU the kernel spills)
   dim3 grid((unsigned)(tiles < slots ? tiles : slots), eavsr::cdiv(cout, 64));
   hipStream_t st = eavsr::as_stream(stream);
   if (dtype == 2) return heads ? launch_il16<true, true>(a, grid, st) : launch_il16<true, false>(a, grid, st);

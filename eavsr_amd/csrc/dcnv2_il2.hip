@@ -26,16 +26,9 @@
 //     stores and parameter loads through scalar bases.
 // Results differ from dcnv2_il.hip only by the re-association that the new k-step composition implies (and, in heads
 // mode, by <= 1 ulp of the mask from v_rcp_f32); tests compare both against the oracle and an fp64 evaluation.
-#include "common.h"
-
-#include <mutex>
+#include "buffer.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int JT_ROWS = 8, JT_W = 32;                // pixel tile: one 32-pixel row per wave
 constexpr int JG = 8;                                // channels per group = k of one tap
@@ -69,54 +62,7 @@ struct IL2Args {
   int n, cin, h, w, cout, dg, opg_shift, tiles_x, tiles_y, ntiles;
 };
 
-// Every global access of the pipeline is a BUFFER instruction (round 5): a 128-bit resource (base + extent, four scalar
-// registers, rebuilt once per tile) + one per-lane 32-bit offset register that lives as long as the tile + one scalar offset
-// computed where it is used (one s_mul_i32 / s_add_i32).  The round-4 form (global_load / global_store / global_load_lds
-// with 64-bit addresses) cost 4 scalar + 1-2 vector instructions per access for address arithmetic, a branch + two
-// compares + two selects per window request of a border tile (zero padding) and an exec-mask region per store; here the
-// hardware's range check does both jobs: a lane whose offset register holds J_OOB reads zeros (also into LDS) and its
-// store is dropped.  The loop is bound by instruction ISSUE (one instruction per ~4 cycles and SIMD over both resident
-// waves, scalar and branch instructions included: DESIGN.md 4b-r5), so every instruction removed is time.
-typedef __amdgpu_buffer_rsrc_t j_rsrc;
-constexpr unsigned J_OOB = 0x80000000u;      // beyond every extent the launcher accepts (< 2^31 bytes)
-__device__ __forceinline__ j_rsrc j_make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-// scalar offset = c * s where c is a compile-time constant: computed AT the use by one s_mul_i32 the optimizer cannot hoist
-// (hoisted, the ~60 distinct products of a pair step become long-lived scalar registers, spill, and a spilled scalar costs
-// VECTOR instructions: v_readlane / v_writelane)
-__device__ __forceinline__ unsigned j_smul(unsigned s, int c) {      // c: a constant once the caller is inlined / unrolled
-  unsigned r;
-  asm volatile("s_mul_i32 %0, %1, %2" : "=s"(r) : "s"(s), "i"(c));
-  return r;
-}
-__device__ __forceinline__ float j_ld(j_rsrc r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ f32x4 j_ld4(j_rsrc r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ void j_st(j_rsrc r, unsigned voff, unsigned soff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-}
-__device__ __forceinline__ void j_dma16(j_rsrc r, unsigned voff, unsigned soff, char* lds_dst) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lptr_t)lds_dst, 16, voff, soff, 0, 0);
-}
-
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void j_split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-__device__ __forceinline__ f32x16 j_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+// Every global access of the pipeline is a BUFFER instruction (round 5): buffer.h says why.
 
 // sampling position of one (pixel, tap): the one place where it is computed (pipeline set-up and global fix-up must take
 // the same in-window decision, so the products and sums are spelled out: no contraction choice is left to the compiler)
@@ -194,7 +140,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 
   // ---- window DMA: piece p = i * 8 + wave (p < 30) is 64 sixteen-byte units e = p * 64 + lane of [half][row][col] -------
   // Per lane and piece: (row, column) inside the window and the unit's byte offset from the window origin; per TILE (below)
-  // the unit's byte offset inside a group's IL8 image, or J_OOB where the unit lies outside the image: the buffer range check
+  // the unit's byte offset inside a group's IL8 image, or EAVSR_OOB where the unit lies outside the image: the buffer range check
   // then writes zeros into LDS, which IS the sampler's corner-wise zero padding and its validity gate.
   constexpr int WIN_IT = (JWIN_SEGS + 7) / 8;   // 4
   int prc[WIN_IT];
@@ -217,9 +163,9 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 
   // buffer resources: the weight slab of this output-channel tile (fixed); of the NEXT pair step's image: its IL8 groups, its
   // heads (or offset) planes, its mask planes (explicit mode)
-  const j_rsrc r_w = j_make_rsrc(a.wpair + (size_t)cot * npairs * JPAIR_U4, (unsigned)npairs * (unsigned)(JPAIR_U4 * 16));
-  j_rsrc r_x, r_h, r_m;
-  j_rsrc r_xc;      // the IL8 groups of the CURRENT pair step's image (the rare path of the gather reads it)
+  const eavsr_rsrc r_w = eavsr_make_rsrc(a.wpair + (size_t)cot * npairs * JPAIR_U4, (unsigned)npairs * (unsigned)(JPAIR_U4 * 16));
+  eavsr_rsrc r_x, r_h, r_m;
+  eavsr_rsrc r_xc;      // the IL8 groups of the CURRENT pair step's image (the rare path of the gather reads it)
 
   // ---- contexts: the pair step being contracted ("cc") and the one after it ("nn": set up, gathered, loaded ahead) -------
   struct Ctx {
@@ -261,20 +207,20 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
     c.fgy = (float)gy;
     c.fgx = (float)gx;
     c.P = 0;
-    r_x = j_make_rsrc(a.xil + (size_t)c.bn * ngroups * plane * JG, (unsigned)ngroups * grp_b);
-    r_h = j_make_rsrc(a.offset + (size_t)c.bn * (HEADS ? 15 : 18) * D * plane, (unsigned)((HEADS ? 15 : 18) * D) * upl4);
-    if (!HEADS) r_m = j_make_rsrc(a.mask + (size_t)c.bn * 9 * D * plane, (unsigned)(9 * D) * upl4);
+    r_x = eavsr_make_rsrc(a.xil + (size_t)c.bn * ngroups * plane * JG, (unsigned)ngroups * grp_b);
+    r_h = eavsr_make_rsrc(a.offset + (size_t)c.bn * (HEADS ? 15 : 18) * D * plane, (unsigned)((HEADS ? 15 : 18) * D) * upl4);
+    if (!HEADS) r_m = eavsr_make_rsrc(a.mask + (size_t)c.bn * 9 * D * plane, (unsigned)(9 * D) * upl4);
     const int ylo = c.wy0, xlo = c.wx0;
     const unsigned torg = (unsigned)((ylo * w + xlo) * 32);      // wraps for windows that begin before the image: so does the sum
 #pragma unroll
     for (int i = 0; i < WIN_IT; ++i) {
       const bool ok = (unsigned)(ylo + (prc[i] >> 8)) < (unsigned)h && (unsigned)(xlo + (prc[i] & 255)) < (unsigned)w;
-      winvo[i] = ok ? poff[i] + torg : J_OOB;
+      winvo[i] = ok ? poff[i] + torg : EAVSR_OOB;
     }
   };
   auto issue_win = [&](int i, unsigned xso, int wslot) __attribute__((always_inline)) {
     if (i < 3 || wave < JWIN_SEGS - 24)      // piece i * 8 + wave < 30 (wave-uniform)
-      j_dma16(r_x, winvo[i], xso, smem + wslot + i * 8192 + wv1k);      // wslot: the slot's byte address in LDS
+      eavsr_buf_dma16(r_x, winvo[i], xso, smem + wslot + i * 8192 + wv1k);      // wslot: the slot's byte address in LDS
   };
   // weights of the pair slab at `wso`: set "Ib" = k-steps 0,1,2,3 (24 pieces, i = 0..2) and k-step 8 (6 pieces, i = 3, waves
   // 0..5) -> regions A, U3[q], U8[q];  set "Ia" = k-steps 4..7 (24 pieces, i = 0..2) -> region B2
@@ -282,13 +228,13 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
     if (i < 3) {
       // pieces 18.. (i = 2, waves 2..7) are k-step 3: parity slot q
       const int dsto = JL_A + i * 8192 + (i == 2 ? q * jks_w2 : 0);
-      j_dma16(r_w, wA, wso + (unsigned)(i * 8192) + wv1k, smem + dsto + wv1k);
+      eavsr_buf_dma16(r_w, wA, wso + (unsigned)(i * 8192) + wv1k, smem + dsto + wv1k);
     } else if (wave < 6) {
-      j_dma16(r_w, wA, wso + (unsigned)(8 * JKS_B) + wv1k, smem + JL_U8 + q * JKS_B + wv1k);
+      eavsr_buf_dma16(r_w, wA, wso + (unsigned)(8 * JKS_B) + wv1k, smem + JL_U8 + q * JKS_B + wv1k);
     }
   };
   auto issue_wgt_ia = [&](int i, unsigned wso) __attribute__((always_inline)) {
-    j_dma16(r_w, wA, wso + (unsigned)(4 * JKS_B + i * 8192) + wv1k, smem + JL_B2 + i * 8192 + wv1k);
+    eavsr_buf_dma16(r_w, wA, wso + (unsigned)(4 * JKS_B + i * 8192) + wv1k, smem + JL_B2 + i * 8192 + wv1k);
   };
 
   int ti_ = 0;
@@ -304,9 +250,9 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
   unsigned n_pm, n_po2, n_pmX, n_poX;
   unsigned n_poj[4];      // heads: the pixel's offset in plane j of a group's transform / translation block (no scalar arithmetic per load)
   auto lane_voffs = [&]() __attribute__((always_inline)) {
-    // a lane without a pixel must contribute nothing: its MASK offsets hold J_OOB, the range check makes the value zero
+    // a lane without a pixel must contribute nothing: its MASK offsets hold EAVSR_OOB, the range check makes the value zero
     // (HEADS == 1 takes logits: there the set-up gates the activated value instead)
-    const unsigned pom = (HEADS == 1 || nn.ok) ? nn.po : J_OOB;
+    const unsigned pom = (HEADS == 1 || nn.ok) ? nn.po : EAVSR_OOB;
     n_pm = pom + (kg ? upl4 : 0u);
     n_po2 = nn.po + (kg ? 2u * upl4 : 0u);
     // ... and of k-step 4 (kg = 0: tap 8 of the even group; kg = 1: tap 0 of the odd group): in one deformable group the
@@ -326,24 +272,24 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
     // keeps both in scratch memory.)
     const unsigned vm = u == 4 ? 0u + n_pmX : 0u + n_pm, vo = u == 4 ? 0u + n_poX : 0u + n_po2;
     const unsigned sm0 = n_sm[0], sm1 = n_sm[1], so0 = n_st[0], so1 = n_st[1];
-    const unsigned x8 = u == 4 ? (same_dg ? 0u : j_smul(upl4, 8)) : 0u;
+    const unsigned x8 = u == 4 ? (same_dg ? 0u : eavsr_smul(upl4, 8)) : 0u;
     if (HEADS) {
-      const unsigned so = u == 4 ? sm0 + x8 : (par0 ? sm1 : sm0) + (tap0 ? j_smul(upl4, tap0) : 0u);
-      pm[u] = j_ld(r_h, vm, so);
+      const unsigned so = u == 4 ? sm0 + x8 : (par0 ? sm1 : sm0) + (tap0 ? eavsr_smul(upl4, tap0) : 0u);
+      pm[u] = eavsr_buf_ld(r_h, vm, so);
     } else {
-      const unsigned so2 = u == 4 ? so0 + 2u * x8 : (par0 ? so1 : so0) + (tap0 ? j_smul(upl4, 2 * tap0) : 0u);
-      const unsigned sm = u == 4 ? sm0 + x8 : (par0 ? sm1 : sm0) + (tap0 ? j_smul(upl4, tap0) : 0u);
-      pa[u] = j_ld(r_h, vo, so2);
-      pb[u] = j_ld(r_h, vo, so2 + upl4);
-      pm[u] = j_ld(r_m, vm, sm);
+      const unsigned so2 = u == 4 ? so0 + 2u * x8 : (par0 ? so1 : so0) + (tap0 ? eavsr_smul(upl4, 2 * tap0) : 0u);
+      const unsigned sm = u == 4 ? sm0 + x8 : (par0 ? sm1 : sm0) + (tap0 ? eavsr_smul(upl4, tap0) : 0u);
+      pa[u] = eavsr_buf_ld(r_h, vo, so2);
+      pb[u] = eavsr_buf_ld(r_h, vo, so2 + upl4);
+      pm[u] = eavsr_buf_ld(r_m, vm, sm);
     }
   };
   auto load_tf = [&](float (&tf)[6], int par) __attribute__((always_inline)) {
     if (HEADS) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) tf[j] = j_ld(r_h, n_poj[j], par ? 0u + n_st[1] : 0u + n_st[0]);
+      for (int j = 0; j < 4; ++j) tf[j] = eavsr_buf_ld(r_h, n_poj[j], par ? 0u + n_st[1] : 0u + n_st[0]);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) tf[4 + j] = j_ld(r_h, n_poj[j], par ? 0u + n_sr[1] : 0u + n_sr[0]);
+      for (int j = 0; j < 2; ++j) tf[4 + j] = eavsr_buf_ld(r_h, n_poj[j], par ? 0u + n_sr[1] : 0u + n_sr[0]);
     }
   };
   constexpr int M_LOADS = HEADS ? 1 : 3;      // vector-memory instructions of one load_m
@@ -429,7 +375,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
   };
   // the four corners (channel half `half`) of k-step u's sample: from the LDS window; lanes outside it read the image itself
   // with corner-wise zero padding (their corner weights are gated once, with the low half)
-  auto gather = [&](int u, int half, const Ctx& c, j_rsrc rxc) __attribute__((always_inline)) {
+  auto gather = [&](int u, int half, const Ctx& c, eavsr_rsrc rxc) __attribute__((always_inline)) {
 #ifdef EAVSR_IL2_EXP_NO_GATHER
 #pragma unroll
     for (int j = 0; j < 4; ++j) gat[j] = f32x4{pos[u % 3].w1, pos[u % 3].w2, (float)(pos[u % 3].ad + half), pos[u % 3].w4};
@@ -481,10 +427,10 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
         // the lane's group of the pair: 2 P (+ 1 for the odd group: the kg = 1 lanes of k-step 4, every lane past it)
         const unsigned so = (unsigned)(2 * c.P + (u > 4 ? 1 : 0)) * grp_b;
         const unsigned vb = (u == 4 && kg ? grp_b : 0u) + (unsigned)(half * 16);
-        tq[0] = j_ld4(rxc, vb + (unsigned)(cy0 * w + cx0) * 32u, so);
-        tq[1] = j_ld4(rxc, vb + (unsigned)(cy0 * w + cx1) * 32u, so);
-        tq[2] = j_ld4(rxc, vb + (unsigned)(cy1 * w + cx0) * 32u, so);
-        tq[3] = j_ld4(rxc, vb + (unsigned)(cy1 * w + cx1) * 32u, so);
+        tq[0] = eavsr_buf_ld4(rxc, vb + (unsigned)(cy0 * w + cx0) * 32u, so);
+        tq[1] = eavsr_buf_ld4(rxc, vb + (unsigned)(cy0 * w + cx1) * 32u, so);
+        tq[2] = eavsr_buf_ld4(rxc, vb + (unsigned)(cy1 * w + cx0) * 32u, so);
+        tq[3] = eavsr_buf_ld4(rxc, vb + (unsigned)(cy1 * w + cx1) * 32u, so);
       }
       // the loads complete HERE, inside the rare branch: past the join nothing waits on vector memory (window DMA, tile
       // stores and parameter loads stay in flight on the common path)
@@ -522,7 +468,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 #ifdef EAVSR_IL2_EXP_NO_SPLIT
     h2 = __float_as_uint(v[0]); m2 = __float_as_uint(v[1]); l2 = h2 ^ m2;
 #else
-    j_split2(v[0], v[1], h2, m2, l2);
+    eavsr_split2(v[0], v[1], h2, m2, l2);
 #endif
     bop[u % 3][0][c] = h2; bop[u % 3][1][c] = m2; bop[u % 3][2][c] = l2;
   };
@@ -535,7 +481,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 #ifdef EAVSR_IL2_EXP_NO_MFMA
     ac[mt][i & 15] += __uint_as_float(b[tb][i & 3] ^ av[ta * 2 + mt][i & 3]);
 #else
-    ac[mt] = j_mfma(av[ta * 2 + mt], b[tb], ac[mt]);
+    ac[mt] = eavsr_mfma_bf16(av[ta * 2 + mt], b[tb], ac[mt]);
 #endif
   };
   auto init_acc = [&]() __attribute__((always_inline)) {
@@ -550,14 +496,14 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
   };
   // finished tile: lane (n, kg) holds channels m * 32 + (e & 3) + 8 (e >> 2) + 4 kg of its pixel.  One buffer store per
   // value: the resource covers this tile's (up to) 64 output planes, the channel is a scalar offset (one s_mul_i32), the lane
-  // part one register for the whole tile; a lane without a pixel holds J_OOB there and its stores are dropped by the range
+  // part one register for the whole tile; a lane without a pixel holds EAVSR_OOB there and its stores are dropped by the range
   // check (no exec-mask region per store)
   bool st_pending = false;
   int st_bn = 0;
-  unsigned st_vo = J_OOB;
+  unsigned st_vo = EAVSR_OOB;
   auto store_tile = [&]() __attribute__((always_inline)) {
     const int nco = min(64, a.cout - cot * 64);
-    const j_rsrc r_o = j_make_rsrc(a.out + ((size_t)st_bn * a.cout + (size_t)cot * 64) * plane, (unsigned)nco * upl4);
+    const eavsr_rsrc r_o = eavsr_make_rsrc(a.out + ((size_t)st_bn * a.cout + (size_t)cot * 64) * plane, (unsigned)nco * upl4);
 #ifdef EAVSR_IL2_EXP_NO_STORE
     if (never) {
 #else
@@ -569,7 +515,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int cu = m * 32 + (e & 3) + 8 * (e >> 2);
-            j_st(r_o, st_vo, cu ? j_smul(upl4, cu) : 0u, acc[m][e]);
+            eavsr_buf_st(r_o, st_vo, cu ? eavsr_smul(upl4, cu) : 0u, acc[m][e]);
           }
       } else {
 #pragma unroll
@@ -577,7 +523,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int cu = m * 32 + (e & 3) + 8 * (e >> 2);
-            j_st(r_o, cu + 4 * kg < nco ? st_vo : J_OOB, cu ? j_smul(upl4, cu) : 0u, acc[m][e]);
+            eavsr_buf_st(r_o, cu + 4 * kg < nco ? st_vo : EAVSR_OOB, cu ? eavsr_smul(upl4, cu) : 0u, acc[m][e]);
           }
       }
     }
@@ -781,7 +727,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_il2_kernel(IL2Args a) {
     if (cc.P + 1 == npairs) {      // the tile is complete: its accumulators leave at the top of the next k-step 0
       st_pending = true;
       st_bn = cc.bn;
-      st_vo = cc.ok ? cc.po + (kg ? 4u * upl4 : 0u) : J_OOB;
+      st_vo = cc.ok ? cc.po + (kg ? 4u * upl4 : 0u) : EAVSR_OOB;
     }
     sE = sEn;
     sO = sOn;
@@ -822,25 +768,13 @@ __global__ void pack_il2_kernel(const float* __restrict__ wt, unsigned* __restri
     v1 = wt[((size_t)co * cin + grp * JG + 2 * j + 1) * 9 + tap];
   }
   unsigned hi, mid, lo;
-  j_split2(v0, v1, hi, mid, lo);
+  eavsr_split2(v0, v1, hi, mid, lo);
   out[e] = term == 0 ? hi : (term == 1 ? mid : lo);
 }
 
 template <int NPROD, int HEADS>
 int launch_il2(const IL2Args& a, dim3 grid, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&dcnv2_il2_kernel<NPROD, HEADS>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)JLDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("dcnv2_il2: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&dcnv2_il2_kernel<NPROD, HEADS>>(JLDS_BYTES, "dcnv2_il2")) return rc;
   hipLaunchKernelGGL((dcnv2_il2_kernel<NPROD, HEADS>), grid, dim3(512), JLDS_BYTES, st, a);
   return eavsr::launch_status("dcnv2_il2");
 }
@@ -883,7 +817,7 @@ extern "C" int eavsr_dcnv2_il2_f32(const float* x_il8, const float* offset_or_he
   EAVSR_REQUIRE(cpg % 8 == 0, -2, "dcnv2_il2: %d channels per deformable group unsupported (must be a multiple of 8)", cpg);
   EAVSR_REQUIRE(cin % 16 == 0, -2, "dcnv2_il2: cin %d must be a multiple of 16 (groups are contracted in pairs)", cin);
   EAVSR_REQUIRE(nprod == 6 || nprod == 9, -2, "dcnv2_il2: nprod %d (6 or 9)", nprod);
-  // every per-image extent is a buffer resource addressed with 32-bit offsets, and J_OOB (2^31) must lie beyond each of them
+  // every per-image extent is a buffer resource addressed with 32-bit offsets, and EAVSR_OOB (2^31) must lie beyond each of them
   EAVSR_REQUIRE((long)h * w * 4 * cin < (1L << 31), -1, "dcnv2_il2: one image of x exceeds 2 GiB");
   EAVSR_REQUIRE((long)h * w * 4 * (heads ? 15 : 18) * deform_groups < (1L << 31), -1, "dcnv2_il2: one image of the heads / offsets exceeds 2 GiB");
   EAVSR_REQUIRE((long)h * w * 4 * 64 < (1L << 31), -1, "dcnv2_il2: 64 output planes exceed 2 GiB");
@@ -904,17 +838,7 @@ extern "C" int eavsr_dcnv2_il2_f32(const float* x_il8, const float* offset_or_he
   const long tiles = (long)a.tiles_x * a.tiles_y * n;
   EAVSR_REQUIRE(tiles < (1L << 31), -1, "dcnv2_il2: too many tiles");
   a.ntiles = (int)tiles;
-  int cus = 256;
-  {
-    static int cu_cache[eavsr::kMaxDevices] = {};
-    const int dev = eavsr::current_device();
-    if (cu_cache[dev] == 0) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cu_cache[dev] = v;
-      else cu_cache[dev] = 256;
-    }
-    cus = cu_cache[dev];
-  }
+  const int cus = eavsr::cu_count();
   dim3 grid((unsigned)(tiles < cus ? tiles : cus), eavsr::cdiv(cout, 64));
   hipStream_t st = eavsr::as_stream(stream);
   EAVSR_REQUIRE(heads >= 0 && heads <= 2, -1, "dcnv2_il2: heads %d (0, 1 or 2)", heads);

@@ -15,16 +15,9 @@
 //
 // Reference semantics: mmcv.ops.modulated_deform_conv2d as called at models/networks.py:627-630, optionally with the affine
 // -> offsets expansion and mask sigmoid of AdaptBlockOffset (networks.py:302-315) folded in ("heads" mode); see dcnv2_il.hip.
-#include "common.h"
-
-#include <mutex>
+#include "mfma.h"
 
 namespace {
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float wld(const char* base, unsigned byte_off) {
   return *reinterpret_cast<const float*>(base + byte_off);
@@ -52,20 +45,6 @@ struct WSArgs {
   float* out;            // (n, cout, h, w)
   int n, cin, h, w, cout, dg, opg_shift, tiles_x, tiles_y, ntiles;
 };
-
-__device__ __forceinline__ void ws_split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
-__device__ __forceinline__ f32x16 ws_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 template <int NPROD, bool HEADS>
 __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
@@ -230,8 +209,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
             for (int j = 0; j < NPROD; ++j) {
               const int ta = NPROD == 9 ? TA9[j] : TA6[j], tb = NPROD == 9 ? TB9[j] : TB6[j];
 #ifndef EAVSR_WS_EXP_NO_MFMA
-              acc[0][mt] = ws_mfma(av[ta * 2 + mt], b0[tb], acc[0][mt]);
-              acc[1][mt] = ws_mfma(av[ta * 2 + mt], b1[tb], acc[1][mt]);
+              acc[0][mt] = eavsr_mfma_bf16(av[ta * 2 + mt], b0[tb], acc[0][mt]);
+              acc[1][mt] = eavsr_mfma_bf16(av[ta * 2 + mt], b1[tb], acc[1][mt]);
 #else
               acc[0][mt][j] += __uint_as_float(av[ta * 2 + mt][0] ^ b0[tb][1]);
               acc[1][mt][j] += __uint_as_float(av[ta * 2 + mt][2] ^ b1[tb][3]);
@@ -269,8 +248,8 @@ __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
 #pragma unroll
         for (int j = 0; j < NPROD; ++j) {
           const int ta = NPROD == 9 ? TA9[j] : TA6[j], tb = NPROD == 9 ? TB9[j] : TB6[j];
-          acc[0][mt] = ws_mfma(av[ta * 2 + mt], b0[tb], acc[0][mt]);
-          acc[1][mt] = ws_mfma(av[ta * 2 + mt], b1[tb], acc[1][mt]);
+          acc[0][mt] = eavsr_mfma_bf16(av[ta * 2 + mt], b0[tb], acc[0][mt]);
+          acc[1][mt] = eavsr_mfma_bf16(av[ta * 2 + mt], b1[tb], acc[1][mt]);
         }
       int pbn, py0, px0;
       tile_of(my_tiles - 1, pbn, py0, px0);
@@ -467,7 +446,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
 #ifdef EAVSR_WS_EXP_NO_SPLIT
           h2 = __float_as_uint(v[2 * c]); m2 = __float_as_uint(v[2 * c + 1]); l2 = h2 ^ m2;
 #else
-          ws_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
+          eavsr_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
 #endif
           bt[0][c] = h2; bt[1][c] = m2; bt[2][c] = l2;
         }
@@ -495,18 +474,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_ws_kernel(WSArgs a) {
 
 template <int NPROD, bool HEADS>
 int launch_ws(const WSArgs& a, dim3 grid, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&dcnv2_ws_kernel<NPROD, HEADS>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)WLDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("dcnv2_ws: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&dcnv2_ws_kernel<NPROD, HEADS>>(WLDS_BYTES, "dcnv2_ws")) return rc;
   hipLaunchKernelGGL((dcnv2_ws_kernel<NPROD, HEADS>), grid, dim3(512), WLDS_BYTES, st, a);
   return eavsr::launch_status("dcnv2_ws");
 }
@@ -539,16 +507,7 @@ extern "C" int eavsr_dcnv2_ws_f32(const float* x_il8, const float* offset_or_hea
   const long tiles = (long)a.tiles_x * a.tiles_y * n;
   EAVSR_REQUIRE(tiles < (1L << 31), -1, "dcnv2_ws: too many tiles");
   a.ntiles = (int)tiles;
-  int cus = 256;
-  {
-    static int cu_cache[eavsr::kMaxDevices] = {};
-    const int dev = eavsr::current_device();
-    if (cu_cache[dev] == 0) {
-      int v = 0;
-      cu_cache[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    cus = cu_cache[dev];
-  }
+  const int cus = eavsr::cu_count();
   dim3 grid((unsigned)(tiles < cus ? tiles : cus), eavsr::cdiv(cout, 64));
   hipStream_t st = eavsr::as_stream(stream);
   if (nprod == 9) return heads ? launch_ws<9, true>(a, grid, st) : launch_ws<9, false>(a, grid, st);

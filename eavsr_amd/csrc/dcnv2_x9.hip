@@ -24,21 +24,11 @@
 // Workgroup = 512 threads = 8 rows x 32 pixels, one per CU (123 KB LDS: 2 window stages + 2 weight stages).
 //
 // Reference semantics: mmcv.ops.modulated_deform_conv2d as called at models/networks.py:627-630 (see dcnv2.hip).
-#include "common.h"
+#include "buffer.h"
 
-#include <mutex>
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float ld_b(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 __device__ __attribute__((aligned(16))) float g_x9_zero[4];
 
@@ -65,23 +55,7 @@ struct X9Args {
   int n, cin, h, w, cout, dg, cpg, tiles_x, tiles_y;
 };
 
-// exact three-way split of two fp32 values into packed bf16 pairs (low half = first value)
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  const float ra = a - __uint_as_float(ua & 0xFFFF0000u), rb = b - __uint_as_float(ub & 0xFFFF0000u);
-  const unsigned uma = __float_as_uint(ra), umb = __float_as_uint(rb);
-  const float la = ra - __uint_as_float(uma & 0xFFFF0000u), lb = rb - __uint_as_float(umb & 0xFFFF0000u);
-  // v_perm_b32: bytes 2,3 of the first value into the low half, bytes 2,3 of the second into the high half
-  hi = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  mid = __builtin_amdgcn_perm(umb, uma, 0x07060302u);
-  lo = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
-
 #if EAVSR_LAB      // the round-1 NCHW kernel with all nine partial products: lab build only; the weight packing below is shared with eavsr_dcnv2_il_f32
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* s_patch = smem;                                                   // [2][XPATCH_F]
@@ -171,9 +145,9 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
     oy[s] = 0.25f; ox[s] = 0.25f; mk[s] = 0.5f;
     (void)offb; (void)mkb; (void)tap;
 #else
-    oy[s] = ld_b(offb, (2u * tap * uplane + pix) * 4u);
-    ox[s] = ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
-    mk[s] = ld_b(mkb, (tap * uplane + pix) * 4u);
+    oy[s] = eavsr_ld_b(offb, (2u * tap * uplane + pix) * 4u);
+    ox[s] = eavsr_ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u);
+    mk[s] = eavsr_ld_b(mkb, (tap * uplane + pix) * 4u);
 #endif
   };
 
@@ -261,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
 #pragma unroll
       for (int c = 0; c < XG / 2; ++c) {
         unsigned h2, m2, l2;
-        split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
+        eavsr_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
         bop[t & 1][0][c] = h2; bop[t & 1][1][c] = m2; bop[t & 1][2][c] = l2;
       }
     };
@@ -271,15 +245,15 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
       for (int mt = 0; mt < 2; ++mt) {
         const u32x4 ah = ws[(0 * 2 + mt) * 64], am = ws[(1 * 2 + mt) * 64], al = ws[(2 * 2 + mt) * 64];
         // the nine partial products, smallest terms first
-        acc[mt] = mfma_bf16(al, b[2], acc[mt]);
-        acc[mt] = mfma_bf16(al, b[1], acc[mt]);
-        acc[mt] = mfma_bf16(am, b[2], acc[mt]);
-        acc[mt] = mfma_bf16(al, b[0], acc[mt]);
-        acc[mt] = mfma_bf16(ah, b[2], acc[mt]);
-        acc[mt] = mfma_bf16(am, b[1], acc[mt]);
-        acc[mt] = mfma_bf16(am, b[0], acc[mt]);
-        acc[mt] = mfma_bf16(ah, b[1], acc[mt]);
-        acc[mt] = mfma_bf16(ah, b[0], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(al, b[2], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(al, b[1], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(am, b[2], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(al, b[0], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(ah, b[2], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(am, b[1], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(am, b[0], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(ah, b[1], acc[mt]);
+        acc[mt] = eavsr_mfma_bf16(ah, b[0], acc[mt]);
       }
     };
     stage_a(0);
@@ -318,9 +292,9 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
         if (mine) {
           const unsigned tap = (unsigned)min(2 * t + kgrp, XK - 1);
           const int ti = (int)tap / 3, tj = (int)tap - 3 * ti;
-          const float py = eavsr_sample_pos((float)(gy - 1 + ti) + ld_b(offb, (2u * tap * uplane + pix) * 4u), h);
-          const float px = eavsr_sample_pos((float)(gx - 1 + tj) + ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u), w);
-          const float m = ld_b(mkb, (tap * uplane + pix) * 4u);
+          const float py = eavsr_sample_pos((float)(gy - 1 + ti) + eavsr_ld_b(offb, (2u * tap * uplane + pix) * 4u), h);
+          const float px = eavsr_sample_pos((float)(gx - 1 + tj) + eavsr_ld_b(offb, ((2u * tap + 1u) * uplane + pix) * 4u), w);
+          const float m = eavsr_ld_b(mkb, (tap * uplane + pix) * 4u);
           const float fy0 = floorf(py), fx0 = floorf(px);
           const float lh = py - fy0, lw = px - fx0;
           const float hm = (1.f - lh) * m, lm = lh * m, hw = 1.f - lw;
@@ -338,10 +312,10 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
 #pragma unroll
           for (int c = 0; c < XG; ++c) {
             const float* qc = xg + (size_t)c * plane;
-            float tv = w1 * ld_b(qc, i1);
-            tv += w2 * ld_b(qc, i2);
-            tv += w3 * ld_b(qc, i3);
-            tv += w4 * ld_b(qc, i4);
+            float tv = w1 * eavsr_ld_b(qc, i1);
+            tv += w2 * eavsr_ld_b(qc, i2);
+            tv += w3 * eavsr_ld_b(qc, i3);
+            tv += w4 * eavsr_ld_b(qc, i4);
             v[c] = tv;
           }
         }
@@ -349,22 +323,22 @@ __global__ __launch_bounds__(512, 2) void dcnv2_x9_kernel(X9Args a) {
 #pragma unroll
         for (int c = 0; c < XG / 2; ++c) {
           unsigned h2, m2, l2;
-          split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
+          eavsr_split2(v[2 * c], v[2 * c + 1], h2, m2, l2);
           b[0][c] = h2; b[1][c] = m2; b[2][c] = l2;
         }
         const u32x4* ws = wst + t * (3 * 2 * 64);
         for (int mt = 0; mt < 2; ++mt) {
           const u32x4 ah = ws[(0 * 2 + mt) * 64], am = ws[(1 * 2 + mt) * 64], al = ws[(2 * 2 + mt) * 64];
           f32x16 c_ = acc[mt];
-          c_ = mfma_bf16(al, b[2], c_);
-          c_ = mfma_bf16(al, b[1], c_);
-          c_ = mfma_bf16(am, b[2], c_);
-          c_ = mfma_bf16(al, b[0], c_);
-          c_ = mfma_bf16(ah, b[2], c_);
-          c_ = mfma_bf16(am, b[1], c_);
-          c_ = mfma_bf16(am, b[0], c_);
-          c_ = mfma_bf16(ah, b[1], c_);
-          c_ = mfma_bf16(ah, b[0], c_);
+          c_ = eavsr_mfma_bf16(al, b[2], c_);
+          c_ = eavsr_mfma_bf16(al, b[1], c_);
+          c_ = eavsr_mfma_bf16(am, b[2], c_);
+          c_ = eavsr_mfma_bf16(al, b[0], c_);
+          c_ = eavsr_mfma_bf16(ah, b[2], c_);
+          c_ = eavsr_mfma_bf16(am, b[1], c_);
+          c_ = eavsr_mfma_bf16(am, b[0], c_);
+          c_ = eavsr_mfma_bf16(ah, b[1], c_);
+          c_ = eavsr_mfma_bf16(ah, b[0], c_);
           acc[mt] = c_;
         }
       }
@@ -412,7 +386,7 @@ __global__ void pack_x9_kernel(const float* __restrict__ wt, unsigned* __restric
     v1 = wt[((size_t)co * cin + g * XG + 2 * j + 1) * XK + tap];
   }
   unsigned hi, mid, lo;
-  split2(v0, v1, hi, mid, lo);
+  eavsr_split2(v0, v1, hi, mid, lo);
   out[e] = pl == 0 ? hi : (pl == 1 ? mid : lo);
 }
 
@@ -452,19 +426,7 @@ extern "C" int eavsr_dcnv2_f32x9(const float* x, const float* offset, const floa
   a.tiles_y = eavsr::cdiv(h, XT_ROWS);
   const long blocks = (long)a.tiles_x * a.tiles_y * n;
   EAVSR_REQUIRE(blocks < (1L << 31), -1, "dcnv2_f32x9: too many tiles");
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&dcnv2_x9_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)XLDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("dcnv2_f32x9: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&dcnv2_x9_kernel>(XLDS_BYTES, "dcnv2_f32x9")) return rc;
   dim3 grid((unsigned)blocks, eavsr::cdiv(cout, 64));
   hipLaunchKernelGGL(dcnv2_x9_kernel, grid, dim3(512), XLDS_BYTES, eavsr::as_stream(stream), a);
   return eavsr::launch_status("dcnv2_f32x9");

@@ -10,7 +10,7 @@
 // HBM-bound: (c + 2 + c) * 4 bytes per pixel.  One thread per pixel column (64 lanes along W so
 // every load/store row segment is coalesced), 16 channels per thread; the 4 corner weights and
 // indices are computed once per pixel and reused across channels.
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
@@ -182,20 +182,18 @@ __global__ __launch_bounds__(256) void flow_warp_pair_kernel(
         op[0] = f32x4{v[0], v[1], v[2], v[3]};
         op[1] = f32x4{v[4], v[5], v[6], v[7]};
       } else {      // 2: fp16, 3: bf16 -- one 16-byte unit per (pixel, octet), each value rounded once
-        typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        typedef float f2_ __attribute__((ext_vector_type(2)));
-        u32x4_ pk;
+        u32x4 pk;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (b_il8 == 3) {
             typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
-            pk[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{v[2 * e], v[2 * e + 1]}, b2_));
+            pk[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2 * e], v[2 * e + 1]}, b2_));
           } else {
             typedef _Float16 h2_ __attribute__((ext_vector_type(2)));
-            pk[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2_{v[2 * e], v[2 * e + 1]}, h2_));
+            pk[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2 * e], v[2 * e + 1]}, h2_));
           }
         }
-        reinterpret_cast<u32x4_*>(outb)[unit] = pk;
+        reinterpret_cast<u32x4*>(outb)[unit] = pk;
       }
     }
     return;

@@ -10,15 +10,13 @@
 //   CHW source (F, C, h, w): the layout does not change, so the whole tensor is one flat run of samples.
 //   HWC source (F, h, w, 3): a lane reads the 12 bytes of 4 pixels and stores one float4 into each of the three planes; needs
 //     h * w % 4 == 0 for the planes to start 16-byte aligned, a scalar kernel covers the rest.
-#include "common.h"
+#include "pixel.h"
 
 #include <stdint.h>
 
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ float unit(uint32_t v) { return (float)v / 255.0f; }
 
 __device__ __forceinline__ float4 unit4(uint32_t word) {
   return make_float4(unit(word & 255u), unit((word >> 8) & 255u), unit((word >> 16) & 255u), unit(word >> 24));

@@ -17,7 +17,7 @@
 // per-sample loads otherwise -- under a window, x0 and a pitch that is no multiple of 4 make that the common case.  The quads right
 // of that -- the reflected columns, a few percent of a frame -- are per-sample loads.
 // blockIdx.y = channel (planes), blockIdx.z = frame: no division anywhere; the row loop is a grid-stride loop in size_t.
-#include "common.h"
+#include "pixel.h"
 
 #include <stdint.h>
 
@@ -27,8 +27,6 @@ constexpr int kLanes = 64;      // threadIdx.x: along the row
 constexpr int kRows = 4;        // threadIdx.y: one wave per row
 
 enum { kU8Planes = 0, kU8Interleaved = 1, kF32Planes = 2 };
-
-__device__ __forceinline__ float unit(uint32_t v) { return (float)v / 255.0f; }
 
 // source index of output index i (i >= 0) on an axis of s samples: inside [0, s)
 __device__ __forceinline__ uint32_t src_index(uint32_t i, uint32_t s, int edge) {

@@ -17,7 +17,7 @@
 // come from the staged samples the tile OWNS (the 64 x 32 samples at its origin; the last tile of a row / column also owns the
 // apron), so every sample is counted and written once.  ONE (ssim, sse) pair per workgroup is written with ordinary stores; a second
 // kernel sums a frame's pairs in a fixed order.  No atomics: two calls on the same input are bitwise equal.
-#include "common.h"
+#include "pixel.h"
 
 #include <math.h>
 
@@ -39,8 +39,6 @@ struct Partial {      // one per workgroup; 16 bytes
   double ssim;
   int64_t sse;
 };
-
-__device__ __forceinline__ float quantise(float v, float scale) { return rintf(fminf(fmaxf(v * scale, 0.f), 255.f)); }
 
 // value of moment M (x, y, x^2, y^2, xy) at one sample; the quantised samples are integers <= 255: exact
 template <int M>

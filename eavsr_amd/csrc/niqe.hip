@@ -20,7 +20,7 @@
 // niqe_half: the antialiased resize of the fp64 plane from host-built (index, weight) tables (eavsr_amd/niqe.py resize_tables),
 // rows (along H) first, then columns, each one fp64 accumulation in tap order: a workgroup computes the row pass of 8 output rows
 // over the columns its 32 output columns read into LDS, then the column pass from LDS.
-#include "common.h"
+#include "pixel.h"
 
 #include <math.h>
 
@@ -37,8 +37,6 @@ constexpr int kHY = 8, kHX = 32;           // niqe_half: output samples per work
 struct Window {
   double g[kTaps];
 };
-
-__device__ __forceinline__ float quantise(float v, float scale) { return rintf(fminf(fmaxf(v * scale, 0.f), 255.f)); }
 
 // BT.601 studio-range luma of an 8-bit pixel in integers: 16 + round_half_even((65481 R + 128553 G + 24966 B) / 255000)
 __device__ __forceinline__ int luma601(int r, int g, int b) {
@@ -199,19 +197,6 @@ __global__ __launch_bounds__(kThreads) void niqe_half_kernel(const double* __res
   }
 }
 
-template <typename K>
-int raise_lds(K kernel, eavsr::PerDeviceOnce& once, hipError_t* errs, const char* what) {
-  const int dev = eavsr::current_device();      // hipFuncSetAttribute is per device: once per (kernel, device)
-  std::call_once(once.flag[dev], [&] {
-    errs[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-  });
-  if (errs[dev] != hipSuccess) {
-    eavsr::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(errs[dev]));
-    return (int)errs[dev];
-  }
-  return 0;
-}
-
 size_t moments_lds(int p, size_t sample) {
   return ((size_t)p * p + 2 * (size_t)(kStrip + 2 * kHalo) * p + kWaves * kMaps * kPerMap) * 8 + (size_t)(p + 2 * kHalo) * (p + 2 * kHalo) * sample;
 }
@@ -235,14 +220,12 @@ extern "C" int eavsr_niqe_moments(const void* src, int32_t src_f64, float scale,
   Window win;
   for (int k = 0; k < kTaps; ++k) win.g[k] = window[k];
   const dim3 grid(blocks_w, blocks_h, N);
-  static eavsr::PerDeviceOnce once32, once64;
-  static hipError_t err32[eavsr::kMaxDevices] = {}, err64[eavsr::kMaxDevices] = {};
   if (src_f64) {
-    if (int rc = raise_lds(&niqe_moments_kernel<double, double>, once64, err64, "niqe_moments")) return rc;
+    if (int rc = eavsr::raise_lds<&niqe_moments_kernel<double, double>>(kMaxLds, "niqe_moments")) return rc;
     hipLaunchKernelGGL((niqe_moments_kernel<double, double>), grid, dim3(kThreads), lds, eavsr::as_stream(stream), (const double*)src, scale,
                        C, H, W, y0, x0, block, win, luma_out, moments);
   } else {
-    if (int rc = raise_lds(&niqe_moments_kernel<float, float>, once32, err32, "niqe_moments")) return rc;
+    if (int rc = eavsr::raise_lds<&niqe_moments_kernel<float, float>>(kMaxLds, "niqe_moments")) return rc;
     hipLaunchKernelGGL((niqe_moments_kernel<float, float>), grid, dim3(kThreads), lds, eavsr::as_stream(stream), (const float*)src, scale, C,
                        H, W, y0, x0, block, win, luma_out, moments);
   }
@@ -260,9 +243,7 @@ extern "C" int eavsr_niqe_half_f64(const double* in, double* out, const int32_t*
                 kHX, span, kMaxLds / (kHY * 8));
   EAVSR_REQUIRE(eavsr::cdiv(h, kHY) <= 65535, -2, "niqe_half: %d output rows, at most %d", h, 65535 * kHY);
   EAVSR_REQUIRE((((uintptr_t)in | (uintptr_t)out | (uintptr_t)row_w | (uintptr_t)col_w) & 7) == 0, -2, "niqe_half: fp64 pointers must be 8-byte aligned");
-  static eavsr::PerDeviceOnce once;
-  static hipError_t errs[eavsr::kMaxDevices] = {};
-  if (int rc = raise_lds(&niqe_half_kernel, once, errs, "niqe_half")) return rc;
+  if (int rc = eavsr::raise_lds<&niqe_half_kernel>(kMaxLds, "niqe_half")) return rc;
   const dim3 grid(eavsr::cdiv(w, kHX), eavsr::cdiv(h, kHY), N);
   hipLaunchKernelGGL(niqe_half_kernel, grid, dim3(kThreads), (size_t)span * kHY * 8, eavsr::as_stream(stream), in, H, W, row_idx, row_w,
                      (int)row_taps, col_idx, col_w, (int)col_taps, col_lo, (int)span, h, w, out);

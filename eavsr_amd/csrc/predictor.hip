@@ -14,9 +14,8 @@
 //     T and the translation t become the 9 sampling offsets  T . R - R + t  with the regular grid R,
 //     written in mmcv channel order g*18 + 2k + {0: y, 1: x}; the mask logits get their sigmoid
 //     (networks.py:313-314).  Pure streaming.
-#include "common.h"
+#include "mfma.h"
 
-#include <mutex>
 
 namespace {
 
@@ -103,7 +102,6 @@ __global__ __launch_bounds__(256) void adapt_frontend_kernel(
 // columns left of the tile, so it arrives as aligned 16-byte loads (3 per thread instead of 11 scalar ones with their index
 // arithmetic); each stage evaluates groups of 4 adjacent columns -- a stencil row is one ds_read_b128 + one b128 / b64 for 4
 // outputs x 3 taps instead of one ds_read_b32 per FMA.  2 x 64 x 180 x 320: 50 -> see DESIGN.md 4g.
-typedef float pf32x2 __attribute__((ext_vector_type(2)));
 constexpr int GP_W = FT_W + 8;        // patch columns x0 - 4 .. x0 + 67 (72, 16-byte rows)
 constexpr int GM_W = FT_W + 4;        // mid columns x0 - 1 .. x0 + 66 (68: 17 groups of 4; the last two are never used)
 __global__ __launch_bounds__(256) void adapt_frontend_v4_kernel(
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(256) void adapt_frontend_v4_kernel(
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
           const f32x4 a4 = *reinterpret_cast<const f32x4*>(&s_mid[ch][r + ky][4 * g]);
-          const pf32x2 b2v = *reinterpret_cast<const pf32x2*>(&s_mid[ch][r + ky][4 * g + 4]);
+          const f32x2 b2v = *reinterpret_cast<const f32x2*>(&s_mid[ch][r + ky][4 * g + 4]);
           const float p[6] = {a4[0], a4[1], a4[2], a4[3], b2v[0], b2v[1]};
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx) {
@@ -533,18 +531,7 @@ extern "C" int eavsr_flow_level_f32(const float* x, const float* h_hr, const flo
   const size_t lds = (size_t)(5 * LR * LP + 18 * 18 * LOP + c * 96) * sizeof(float);
   EAVSR_REQUIRE(lds <= 160 * 1024, -2, "flow_level: %d channels need %zu bytes of LDS", c, lds);
   if (lds > 64 * 1024) {
-    static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-    const int dev_ = eavsr::current_device();
-    static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-    hipError_t& attr_err = attr_err_pd[dev_];
-    std::call_once(once_pd.flag[dev_], [&] {
-      attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&flow_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024);
-    });
-    if (attr_err != hipSuccess) {
-      eavsr::set_error("flow_level: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-      return (int)attr_err;
-    }
+    if (int rc = eavsr::raise_lds<&flow_level_kernel>(160 * 1024, "flow_level")) return rc;
   }
   hipLaunchKernelGGL(flow_level_kernel, dim3((unsigned)nblk), dim3(256), lds, eavsr::as_stream(stream), x, h_hr, w1, b1, w2, b2,
                      w_heads, b_heads, w_trans, b_trans, out, c, h, w, tiles_x, tiles_y);

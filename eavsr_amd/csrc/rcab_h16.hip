@@ -21,19 +21,13 @@
 //   result bit for bit.
 //   Every global access is a buffer instruction: patch units outside the image read zeros through the range check (the
 //   convolution's zero padding: no fill code, no border branch), stores of lanes without a pixel are dropped by it.
-#include "common.h"
+#include "buffer.h"
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
-
-typedef _Float16 r_h16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* r_lptr;
-typedef __amdgpu_buffer_rsrc_t r_rsrc;
-typedef unsigned r_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RT_H = 8, RT_W = 32;                    // output tile
 constexpr int RI_H = RT_H + 4, RI_W = RT_W + 4;       // input patch 12 x 36
@@ -54,7 +48,6 @@ constexpr int RL_RED = RL_W + RW_SLOTS * RW_GRAN;     // [8 waves][64] channel s
 constexpr int RL_BIAS = RL_RED + 8 * 64 * 4;          // [2][64]
 constexpr int R_LDS_BYTES = RL_BIAS + 2 * 64 * 4;     // 156,672
 constexpr int RN1 = (RM_PIX + 31) / 32;               // 11 N-tiles of conv-1
-constexpr unsigned R_OOB = 0x80000000u;
 
 #ifdef EAVSR_RCAB_STAMPS
 // diagnostic build only: shader cycles per phase, summed over wave 0 of every workgroup
@@ -97,12 +90,7 @@ __device__ __forceinline__ f32x16 r_mfma(const f32x4& a, const f32x4& b, const f
   d[0] += a[0] + b[1];
   return d;
 #endif
-  if (BF16) {
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(r_h16x8, a), __builtin_bit_cast(r_h16x8, b), c, 0, 0, 0);
-  }
+  return eavsr_mfma16<BF16>(a, b, c);
 }
 
 #define R_ADD_DPP(v, ctrl) asm volatile("v_add_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(v) : "v"(v))
@@ -114,7 +102,7 @@ __device__ __forceinline__ f32x4 r_lds4(unsigned addr) {
 template <bool BF16>
 __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const unsigned lds0 = (unsigned)(unsigned long long)(r_lptr)smem;
+  const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
   float* s_red = reinterpret_cast<float*>(smem + RL_RED);
   float* s_bias = reinterpret_cast<float*>(smem + RL_BIAS);
 
@@ -133,8 +121,8 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
 #endif
   if (tid < 128) s_bias[tid] = tid < 64 ? (a.bias1 ? a.bias1[tid] : 0.f) : (a.bias2 ? a.bias2[tid - 64] : 0.f);
 
-  const r_rsrc r_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wp1), 0, RW_CONV, 0x00020000);
-  const r_rsrc r_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wp2), 0, RW_CONV, 0x00020000);
+  const eavsr_rsrc r_w1 = eavsr_make_rsrc(a.wp1, RW_CONV);
+  const eavsr_rsrc r_w2 = eavsr_make_rsrc(a.wp2, RW_CONV);
   const unsigned img_bytes = (unsigned)h * (unsigned)w * 128u;
   const unsigned wv = (unsigned)lane * 16u;
   // granule `q` (0..3 conv-1, 4..7 conv-2) into ring slot `slot`: 18 one-KiB pieces, piece i * 8 + wave (waves 0, 1 three, the
@@ -143,11 +131,11 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
 #ifdef EAVSR_RCAB_EXP_NO_WDMA      // timing ablation (results wrong)
     if (a.n >= 0) return;
 #endif
-    const r_rsrc rw = q < 4 ? r_w1 : r_w2;
+    const eavsr_rsrc rw = q < 4 ? r_w1 : r_w2;
     const unsigned so = (unsigned)((q & 3) * RW_GRAN);
     const int piece = i * 8 + wave;
     if (i < 2 || wave < 2)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (r_lptr)(smem + RL_W + slot * RW_GRAN + piece * 1024), 16, wv, so + (unsigned)(piece * 1024), 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(smem + RL_W + slot * RW_GRAN + piece * 1024), 16, wv, so + (unsigned)(piece * 1024), 0, 0);
   };
   auto req_w = [&](int q, int slot) __attribute__((always_inline)) {
 #pragma unroll
@@ -166,15 +154,14 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
     bn = t / a.tiles_y;
   };
   // the next tile's patch: context set once (resource of its image, patch origin), then one piece per call
-  r_rsrc rx_n;
+  eavsr_rsrc rx_n;
   int py0_n = 0, px0_n = 0;
   auto patch_ctx = [&](int j) __attribute__((always_inline)) {      // (j past the run: the last tile once more, never read)
     int bn, ty, tx;
     tile_at(j, bn, ty, tx);
     py0_n = ty * RT_H - 2;
     px0_n = tx * RT_W - 2;
-    rx_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.x) + (size_t)bn * img_bytes), 0,
-                                             (int)img_bytes, 0x00020000);
+    rx_n = eavsr_make_rsrc(reinterpret_cast<const char*>(a.x) + (size_t)bn * img_bytes, img_bytes);
   };
   auto req_patch1 = [&](int i) __attribute__((always_inline)) {
     if (i < 6 || wave < RI_SEGS - 48) {
@@ -183,8 +170,8 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
       const int pr = pp / RI_W, pc = pp - pr * RI_W;
       const int gy = py0_n + pr, gx = px0_n + pc;
       const bool ok = (unsigned)gy < (unsigned)h && (unsigned)gx < (unsigned)w;
-      const unsigned vo = ok ? (unsigned)(gy * w + gx) * 128u + (unsigned)((sb ^ ((pc >> 1) & 7)) << 4) : R_OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_n, (r_lptr)(smem + RL_IN + (i * 8 + wave) * 1024), 16, vo, 0, 0, 0);
+      const unsigned vo = ok ? (unsigned)(gy * w + gx) * 128u + (unsigned)((sb ^ ((pc >> 1) & 7)) << 4) : EAVSR_OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_n, (lptr_t)(smem + RL_IN + (i * 8 + wave) * 1024), 16, vo, 0, 0, 0);
     }
   };
 
@@ -296,8 +283,8 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
   // It is DEFERRED: a tile's accumulators stay in registers and its four chunks run behind the first MFMAs of the NEXT tile's
   // conv-1 (k-steps 0..3 of granule 0, ahead of that granule's meeting, so the counted waits see the stores where they were).
   f32x16 acc2[2];
-  r_rsrc ro_p = r_w1;      // the pending tile's output resource, lane offset (R_OOB: no pixel) and sample
-  unsigned vo_p = R_OOB;
+  eavsr_rsrc ro_p = r_w1;      // the pending tile's output resource, lane offset (EAVSR_OOB: no pixel) and sample
+  unsigned vo_p = EAVSR_OOB;
   bool ok_p = false;
   int bn_p = -1;
   auto epi2_chunk = [&](int c) __attribute__((always_inline)) {
@@ -319,7 +306,7 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
     // the lane pair (l31, half 0 | 1) trades 4-channel runs so that a lane stores 16 contiguous bytes (conv_h16.hip)
     const auto s0 = __builtin_amdgcn_permlane32_swap(dw[0][0], dw[1][0], false, false);
     const auto s1 = __builtin_amdgcn_permlane32_swap(dw[0][1], dw[1][1], false, false);
-    const r_u32x4 v4 = {s0[0], s1[0], s0[1], s1[1]};
+    const u32x4 v4 = {s0[0], s1[0], s0[1], s1[1]};
     __builtin_amdgcn_raw_buffer_store_b128(v4, ro_p, vo_p + (unsigned)((m * 32 + 8 * (qe + half)) * 2), 0, 0);
   };
 
@@ -454,8 +441,7 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
             }
             const unsigned d0 = ((unsigned)pk[0] | ((unsigned)pk[1] << 16)) & keep, d1 = ((unsigned)pk[2] | ((unsigned)pk[3] << 16)) & keep;
             if (pv) {
-              typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-              *reinterpret_cast<__attribute__((address_space(3))) u32x2_t*>(pbase + (unsigned)(((m1 * 4 + qd) ^ swz) << 4)) = u32x2_t{d0, d1};
+              *reinterpret_cast<__attribute__((address_space(3))) u32x2*>(pbase + (unsigned)(((m1 * 4 + qd) ^ swz) << 4)) = u32x2{d0, d1};
             }
           }
         }
@@ -543,8 +529,8 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
     {
       const int gy = ty * RT_H + wave, gx = tx * RT_W + l31;
       ok_p = gy < h && gx < w;
-      ro_p = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.out) + (size_t)bn * img_bytes, 0, (int)img_bytes, 0x00020000);
-      vo_p = ok_p ? (unsigned)(gy * w + gx) * 128u : R_OOB;
+      ro_p = eavsr_make_rsrc(reinterpret_cast<char*>(a.out) + (size_t)bn * img_bytes, img_bytes);
+      vo_p = ok_p ? (unsigned)(gy * w + gx) * 128u : EAVSR_OOB;
       bn_p = bn;
       if (first_bn < 0) first_bn = bn;
     }
@@ -574,19 +560,7 @@ __global__ __launch_bounds__(512, 2) void rcab_convs_h16_kernel(RcabArgs a) {
 
 template <bool BF16>
 int launch_rcab_h16(const RcabArgs& a, int blocks, hipStream_t st) {
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  std::once_flag& once = once_pd.flag[dev_];
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once, [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&rcab_convs_h16_kernel<BF16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS_BYTES);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("rcab_convs_h16: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&rcab_convs_h16_kernel<BF16>>(R_LDS_BYTES, "rcab_convs_h16")) return rc;
   hipLaunchKernelGGL(rcab_convs_h16_kernel<BF16>, dim3(blocks), dim3(512), R_LDS_BYTES, st, a);
   return eavsr::launch_status("rcab_convs_h16");
 }

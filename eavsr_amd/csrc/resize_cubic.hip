@@ -32,7 +32,7 @@
 //
 // Addressing: the plane's base offset is size_t; offsets inside a plane are 32-bit (H W <= 2^31 - 1 is required).
 // Planes and tiles share grid x: F C tiles <= 2^24 - 1 workgroups (x 256 lanes stays below 2^32 work-items).
-#include "common.h"
+#include "pixel.h"
 
 #include <stdint.h>
 
@@ -46,8 +46,6 @@ constexpr int kSlack = 7;             // source samples of a tile of T outputs: 
 constexpr int kMaxNX = kMaxRatio * (kTX - 1) + kSlack, kMaxNY = kMaxRatio * (kTY - 1) + kSlack;
 constexpr int kMaxLds = kMaxNY * (((kMaxNX + 6) / 4) * 4 + kTX * 4);      // 98044 bytes at ratio 8 in both axes
 constexpr long long kMaxBlocks = (1ll << 24) - 1;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 struct Taps {
   int ofs;
@@ -178,18 +176,7 @@ extern "C" int eavsr_resize_cubic_u8(const uint8_t* in, uint8_t* out, const int3
   const int nx_cap = span_cap(W, w, kTX), ny_cap = span_cap(H, h, kTY);
   const size_t lds_bytes = (size_t)ny_cap * (kTX * 4 + ((nx_cap + 6) / 4) * 4);
 
-  static eavsr::PerDeviceOnce once_pd;   // hipFuncSetAttribute is per device: once per (kernel, device)
-  const int dev_ = eavsr::current_device();
-  static hipError_t attr_err_pd[eavsr::kMaxDevices] = {};
-  hipError_t& attr_err = attr_err_pd[dev_];
-  std::call_once(once_pd.flag[dev_], [&] {
-    attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&resize_cubic_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   kMaxLds);
-  });
-  if (attr_err != hipSuccess) {
-    eavsr::set_error("resize_cubic_u8: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
-    return (int)attr_err;
-  }
+  if (int rc = eavsr::raise_lds<&resize_cubic_u8_kernel>(kMaxLds, "resize_cubic_u8")) return rc;
   const int vec = (w % 4 == 0) && (((uintptr_t)out) & 3) == 0;
   hipLaunchKernelGGL(resize_cubic_u8_kernel, dim3((unsigned)blocks), dim3(kThreads), lds_bytes, eavsr::as_stream(stream), in, out, xofs,
                      xcoef, yofs, ycoef, (size_t)F * C * H * W, H, W, h, w, tiles_x, tiles, nx_cap, ny_cap, vec);

@@ -19,7 +19,7 @@
 // the right and lower neighbour of fw) stay inside a few neighbouring rows.  A lane sums its pixels in row order, the wave sums its
 // lanes by a fixed butterfly, lane 0 of wave 0 the four waves in order: ONE (err, epe, count) record per workgroup, written with
 // ordinary stores; a second kernel sums a pair's records in a fixed order.  No atomics: two calls on the same input are bitwise equal.
-#include "common.h"
+#include "pixel.h"
 
 #include <math.h>
 
@@ -34,8 +34,6 @@ struct Partial {      // one per workgroup; 24 bytes
   double epe;
   int64_t count;
 };
-
-__device__ __forceinline__ float quantise(float v, float scale) { return rintf(fminf(fmaxf(v * scale, 0.f), 255.f)); }
 
 struct Taps {      // the four samples of a bilinear read and their weights
   size_t o00, o01, o10, o11;

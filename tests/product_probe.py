@@ -54,7 +54,7 @@ _TOP = np.uint32(0xFFFF0000)
 
 
 def split3(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """s_split2 / wx_split2 / il_split2: hi = the top 16 bits of x, mid = the top 16 bits of x - hi, lo = x - hi - mid (fp32
+    """eavsr_split2 (csrc/mfma.h): hi = the top 16 bits of x, mid = the top 16 bits of x - hi, lo = x - hi - mid (fp32
     subtractions, both exact)"""
     x = np.ascontiguousarray(x, dtype=np.float32)
     hi = floats(bits(x) & _TOP)
